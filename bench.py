@@ -3,7 +3,13 @@
 (BASELINE.json metric), with the achieved HBM GB/s of the dominant stage against the roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wgs|s1] [--genome BASES] [--passes S]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  --full adds
+what the headline does not need: HIP-event brackets around the kernels during the timed steps (the roofline figures), the
+self-check after the timed region, the per-rank exchange report of N > 1, the CPU baseline and the end-to-end leg.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; dump_outputs).
 
 Default workload = BASELINE.json configs[2] (the config the metric is quoted on): synthetic 30x WGS trio,
 3.1 Gb random genome, 3.1e8 pairs of 150 bp per sample (6.2e8 reads), 0.5 % substitution errors, 2 % low-
@@ -298,6 +304,53 @@ def end_to_end(n_pairs=32_000_000):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def step_outputs(res, extra):
+    """What a caller of the timed path receives from one step, as arrays of exact integers: the mutant k-mers in (pos,key)
+    order (canonical 2-bit keys as [high, low] 32-bit halves: k = 31 keys do not fit a float64's mantissa), the k-mer count
+    histogram and the record count of every sample, and the subject's pulled reads -- wgs: the indices of the reads with a
+    hit bit in the filter's masks (rank 0's blocks, in block order); s1: the indices of the pulled pairs."""
+    keys = np.asarray(res["mutant_keys"], dtype=np.uint64)
+    out = {"mutant_keys": np.stack([keys >> np.uint64(32), keys & np.uint64(0xFFFFFFFF)], axis=1),
+           "histograms": np.stack([np.asarray(h, dtype=np.uint64) for h in res["histos"]]),
+           "records_per_sample": np.asarray(res["n_records"], dtype=np.uint64)}
+    if "hit_masks" in res:
+        hits, base = [], 0
+        for b, mask in zip(extra["_samples"][0], res["hit_masks"]):
+            m = np.asarray(mask[:(b.n + 63) // 64], dtype=np.uint64)
+            w = np.flatnonzero(m)
+            bits = np.unpackbits(m[w].view(np.uint8).reshape(-1, 8), axis=1, bitorder="little").astype(bool)
+            idx = (w[:, None] * 64 + np.arange(64))[bits]
+            hits.append(base + idx[idx < b.n])
+            base += b.n
+        out["hit_reads"] = np.concatenate(hits) if hits else np.zeros(0, np.int64)
+    else:
+        out["pulled_pairs"] = np.flatnonzero(res["pulled"])
+    return out
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy in float64 (every value is an integer below 2^53: exact).  Should the arrays pass DUMP_BYTES in all,
+    the larger ones are cut to a fixed, seeded sample of their rows (sorted, the same rows for the same output)."""
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_BYTES // 8
+    names = sorted(arrays, key=lambda n: arrays[n].size)
+    sampled = {}
+    for i, name in enumerate(names):
+        a = np.asarray(arrays[name])
+        row = max(1, a.size // max(len(a), 1)) if a.ndim > 1 else 1
+        fit = left // (len(names) - i) // row
+        if len(a) > fit:
+            rows = np.sort(np.random.default_rng(SEED).choice(len(a), fit, replace=False))
+            sampled[name] = [len(a), int(fit)]
+            a = a[rows]
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
+        left -= a.size
+    return sampled
+
+
 def run_s1(args, ctx, rank, world, dist, torch):
     """BASELINE.json configs[1]: 1 M x 150 bp reads per sample (per GPU), the round-1 workload."""
     from rufus_amd import capi
@@ -401,12 +454,17 @@ def main():
     ap.add_argument("--passes", type=int, default=0, help="wgs: minimizer-shard passes (0 = plan from free HBM)")
     ap.add_argument("--dense-reads", action="store_true",
                     help="wgs: keep the read blocks in the dense form (68 B per 150 bp read instead of 43)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline figures (HIP-event brackets in the timed steps), the self-check, the N > 1 exchange "
+                         "report, the CPU baseline and the end-to-end leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) print the cpu_baseline object and exit")
     ap.add_argument("--end-to-end-only", action="store_true", help="(internal) print the end_to_end object and exit")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the self-check after the timed region (rufus_amd.wgs.self_check: three more steps)")
+                    help="--full: skip the self-check after the timed region (rufus_amd.wgs.self_check: three more steps)")
     ap.add_argument("--e2e-pairs", type=int, default=32_000_000,
                     help="read pairs per sample of the end-to-end leg (refused when the text would not fit the container's memory)")
     ap.add_argument("--inner", action="store_true", help="(internal) the GPU part only, run by the launcher below")
@@ -434,7 +492,8 @@ def main():
         for ln in out[:-1]:
             print(ln)
         line = json.loads(out[-1])
-        legs(args, line)
+        if args.full:
+            legs(args, line)
         print(json.dumps(line))
         return
 
@@ -484,9 +543,11 @@ def main():
 
     # HIP-event brackets (rfx_prof_*) on the library's stream around every launch of the count chain and the
     # filter.  A bracket costs ~10-30 us of host time: nothing against the multi-second WGS step, so there they
-    # stay on for the whole timed region; on the 4 ms S1 step only during the last timed step.
-    ctx.prof_filter(K2_CHAIN + ("k_filter",))
-    ctx.prof(True)
+    # stay on for the whole timed region; on the 4 ms S1 step only during the last timed step.  (--full only: the headline
+    # needs none of them.)
+    if args.full:
+        ctx.prof_filter(K2_CHAIN + ("k_filter",))
+        ctx.prof(True)
     for w_ in range(args.warmup):
         res = step()
         # After the first (untimed) step the peak of a step is known: what the device has left beside it (up to 93 % of its
@@ -525,9 +586,10 @@ def main():
                     pool = min(head, need)
                     extra["_trio"].map_budget = pool
                     extra["run_map_budget_bytes"] = pool
-    live_all = args.workload != "s1"
-    ctx.prof(live_all)
-    ctx.prof_reset()
+    live_all = args.full and args.workload != "s1"
+    if args.full:
+        ctx.prof(live_all)
+        ctx.prof_reset()
     # No cyclic-GC pass of the interpreter inside the timed region: the synthetic reads are millions of Python objects, a
     # full collection over them takes 40-80 ms, and where it lands depends on the allocation count so far (on a box's
     # first run, which compiles the .pyc files, it fell outside the 20 timed S1 steps; on every later run inside the
@@ -538,7 +600,7 @@ def main():
     t0 = time.perf_counter()
     step_ms = []
     for i in range(args.steps):
-        if not live_all and i == args.steps - 1:
+        if args.full and not live_all and i == args.steps - 1:
             ctx.prof(True)
         t_s = time.perf_counter()
         res = step()
@@ -548,12 +610,19 @@ def main():
     gc.enable()
     if os.environ.get("RFX_BENCH_STEP_TIMES"):
         print("bench.py step wall ms: " + json.dumps(step_ms), file=sys.stderr, flush=True)
-    prof = ctx.prof_dict()
-    prof_steps = args.steps if live_all else 1
-    ctx.prof(False)
+    if args.full:
+        prof = ctx.prof_dict()
+        prof_steps = args.steps if live_all else 1
+        ctx.prof(False)
+    # What the last timed step computed, before anything else runs the path again (the wgs hit masks are views of the
+    # library's page-locked buffers: the next run overwrites them).
+    if args.dump_outputs and rank == 0:
+        sampled = dump_outputs(args.dump_outputs, step_outputs(res, extra))
+        if sampled:
+            print("bench.py --dump-outputs: sampled rows (of, kept): " + json.dumps(sampled), file=sys.stderr, flush=True)
     # After the timed region: the run proves itself (size-independent properties -- at 3.1 Gb nothing else can).
     checks = None
-    if args.workload != "s1" and not args.no_check:
+    if args.full and args.workload != "s1" and not args.no_check:
         from rufus_amd import wgs
         t_chk = time.perf_counter()
         checks = wgs.self_check(ctx, extra["_trio"], extra["_samples"], extra["_sys"], res, extra["_pairs"][0], MIN_Q)
@@ -565,6 +634,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.full and world > 1:
         # what the first real SCALE run is checked by at a glance: every rank's view of the group and what it exchanged
         mine = torch.tensor([rank, local, dist.get_world_size(), int(getattr(trio_, "exchange_sent", 0)),
                              int(getattr(trio_, "exchange_received", 0))], dtype=torch.int64, device="cuda")
@@ -576,17 +646,6 @@ def main():
                               for x in (y.tolist() for y in allr)]}
 
     if rank == 0:
-        # K2+K3 (count -> sorted records) is the dominant stage: a chain of launches per sample (super-k-mer
-        # partition of every read block, refinement of the partition, LDS count of every minimizer bin,
-        # partition + sort of the survivors).  The algorithmic bytes of SURVEY 8(d) K2 cover the stage as a
-        # whole, so one "launch" = the chain of one sample, its duration = the SUM of its kernels' durations.
-        k2 = [n for n in K2_CHAIN if n in prof and prof[n][1]]
-        n_chains = n_samples * prof_steps
-        parts = {n: prof[n][0] / n_chains for n in k2}
-        chain_ms = sum(parts.values())
-        bytes_per_launch = algorithmic_bytes_per_read(k=k_used) * reads_per_launch
-        achieved = bytes_per_launch / (chain_ms * 1e-3) / 1e9 if chain_ms else 0.0
-        f_ms = prof["k_filter"][0] / prof_steps if "k_filter" in prof and prof["k_filter"][1] else 0.0
         line = {
             "metric": f"reads/sec through k-mer count+filter at k={k_used}",
             "value": reads_per_step * args.steps / dt,
@@ -608,36 +667,50 @@ def main():
                        **({"one_device_dry_run": f"{world} ranks share device 0 over {dist.get_backend()}: the N-rank path is "
                                                  "exercised, the value is NOT a scaling measurement"} if args.one_device and world > 1 else {}),
                        "hbm_peak_bytes": ctx.mem_stats()["peak"], "hbm_mapped_bytes": ctx.mem_stats()["mapped"]},
-            "roofline": {"bound": "hbm", "kernel": "count chain of one sample: " + "+".join(k2), "achieved": achieved,
-                         "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": None,
-                         "avg_launch_ms": chain_ms, "avg_launch_ms_by_kernel": {n: round(v, 3) for n, v in parts.items()},
-                         "launches": n_chains, "reads_per_launch": reads_per_launch,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "launches_by_kernel_per_chain": {n: round(prof[n][1] / n_chains, 1) for n in k2}},
-            # K5 (read filter) against the same roofline: SURVEY 8(d) prices it at 61 B/read of streaming
-            "roofline_filter": {"bound": "hbm", "kernel": "k_filter", "achieved": 61.0 * reads_filtered / world / (f_ms * 1e-3) / 1e9,
-                                "peak": 8000.0, "unit": "GB/s",
-                                "frac": 61.0 * reads_filtered / world / (f_ms * 1e-3) / 1e9 / 8000.0,
-                                "ms_per_step": f_ms, "algorithmic_bytes_per_step": 61 * reads_filtered // world,
-                                "note": "rank 0's share"} if f_ms else None,
         }
-        # HBM traffic of the chain: PMC counters cannot be collected inside this run (rocprofv3 wraps the process), so the
-        # line quotes the newest profiles/rNN_pmc_<workload>.json -- but only if it was taken on THIS build: the file
-        # carries the fingerprint of the kernel sources it was measured with (kernel_source_fingerprint(); the snapshot a
-        # GPU box gets has no .git to ask), and a stale one is refused (traffic stays null, the reason is in the line).
-        import glob
-        pmc_files = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_pmc_{args.workload}.json")))
-        pmc_path = pmc_files[-1] if pmc_files else ""          # the newest round's counters
-        if pmc_path:
-            pmc = json.load(open(pmc_path))
-            fp = kernel_source_fingerprint()
-            if pmc.get("kernel_sources_sha16") != fp:
-                line["roofline"]["traffic_source"] = (f"{os.path.basename(pmc_path)} refused: taken on kernel sources "
-                                                      f"{pmc.get('kernel_sources_sha16')}, this build is {fp}")
-            elif pmc.get("genome") in (None, getattr(args, "genome", None)) and "_chain" in pmc:
-                line["roofline"]["traffic"] = pmc["_chain"]["hbm_bytes_per_sample"]
-                line["roofline"]["traffic_source"] = (os.path.basename(pmc_path) + f" (commit {pmc.get('commit')}, kernel sources "
-                                                      f"{fp}): " + pmc["_chain"].get("source", ""))
+        if args.full:
+            # K2+K3 (count -> sorted records) is the dominant stage: a chain of launches per sample (super-k-mer
+            # partition of every read block, refinement of the partition, LDS count of every minimizer bin,
+            # partition + sort of the survivors).  The algorithmic bytes of SURVEY 8(d) K2 cover the stage as a
+            # whole, so one "launch" = the chain of one sample, its duration = the SUM of its kernels' durations.
+            k2 = [n for n in K2_CHAIN if n in prof and prof[n][1]]
+            n_chains = n_samples * prof_steps
+            parts = {n: prof[n][0] / n_chains for n in k2}
+            chain_ms = sum(parts.values())
+            bytes_per_launch = algorithmic_bytes_per_read(k=k_used) * reads_per_launch
+            achieved = bytes_per_launch / (chain_ms * 1e-3) / 1e9 if chain_ms else 0.0
+            f_ms = prof["k_filter"][0] / prof_steps if "k_filter" in prof and prof["k_filter"][1] else 0.0
+            line.update({
+                "roofline": {"bound": "hbm", "kernel": "count chain of one sample: " + "+".join(k2), "achieved": achieved,
+                             "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": None,
+                             "avg_launch_ms": chain_ms, "avg_launch_ms_by_kernel": {n: round(v, 3) for n, v in parts.items()},
+                             "launches": n_chains, "reads_per_launch": reads_per_launch,
+                             "algorithmic_bytes_per_launch": bytes_per_launch,
+                             "launches_by_kernel_per_chain": {n: round(prof[n][1] / n_chains, 1) for n in k2}},
+                # K5 (read filter) against the same roofline: SURVEY 8(d) prices it at 61 B/read of streaming
+                "roofline_filter": {"bound": "hbm", "kernel": "k_filter", "achieved": 61.0 * reads_filtered / world / (f_ms * 1e-3) / 1e9,
+                                    "peak": 8000.0, "unit": "GB/s",
+                                    "frac": 61.0 * reads_filtered / world / (f_ms * 1e-3) / 1e9 / 8000.0,
+                                    "ms_per_step": f_ms, "algorithmic_bytes_per_step": 61 * reads_filtered // world,
+                                    "note": "rank 0's share"} if f_ms else None,
+            })
+            # HBM traffic of the chain: PMC counters cannot be collected inside this run (rocprofv3 wraps the process), so the
+            # line quotes the newest profiles/rNN_pmc_<workload>.json -- but only if it was taken on THIS build: the file
+            # carries the fingerprint of the kernel sources it was measured with (kernel_source_fingerprint(); a copy of the
+            # tree may have no .git to ask), and a stale one is refused (traffic stays null, the reason is in the line).
+            import glob
+            pmc_files = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_pmc_{args.workload}.json")))
+            pmc_path = pmc_files[-1] if pmc_files else ""          # the newest round's counters
+            if pmc_path:
+                pmc = json.load(open(pmc_path))
+                fp = kernel_source_fingerprint()
+                if pmc.get("kernel_sources_sha16") != fp:
+                    line["roofline"]["traffic_source"] = (f"{os.path.basename(pmc_path)} refused: taken on kernel sources "
+                                                          f"{pmc.get('kernel_sources_sha16')}, this build is {fp}")
+                elif pmc.get("genome") in (None, getattr(args, "genome", None)) and "_chain" in pmc:
+                    line["roofline"]["traffic"] = pmc["_chain"]["hbm_bytes_per_sample"]
+                    line["roofline"]["traffic_source"] = (os.path.basename(pmc_path) + f" (commit {pmc.get('commit')}, kernel sources "
+                                                          f"{fp}): " + pmc["_chain"].get("source", ""))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

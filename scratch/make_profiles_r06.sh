@@ -59,12 +59,12 @@ if [ "${SQ:-1}" = 1 ]; then
 bash scratch/r6_sq.sh > $O/sq.log 2>&1; cp gpurun_out/r6_sq.txt $O/r06_sq_counters_1g.txt; head -30 $O/r06_sq_counters_1g.txt
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-timeout 1700 python3 bench.py --gpus 1 --steps ${STEPS:-20} --warmup 5 > $O/bench.log 2> $O/bench.err; tail -1 $O/bench.log > $O/r06_bench.json
+timeout 1700 python3 bench.py --gpus 1 --steps ${STEPS:-20} --warmup 5 --full > $O/bench.log 2> $O/bench.err; tail -1 $O/bench.log > $O/r06_bench.json
 python3 -c "
 import json; d=json.load(open('$O/r06_bench.json')); print(d['value'], d['roofline']['frac'], d['roofline']['avg_launch_ms'], d['roofline'].get('traffic'), d['roofline_filter']['frac'], d['config'].get('checks')); print(json.dumps(d.get('end_to_end'))[:700])"
 tail -2 $O/bench.err
 fi
 if [ "${EXTRA:-1}" = 1 ]; then
-timeout 300 python bench.py --workload s1 --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $O/s1.log 2>/dev/null; tail -1 $O/s1.log > $O/r06_bench_s1.json; cut -c1-220 $O/r06_bench_s1.json
-timeout 1200 python bench.py --workload tn --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $O/tn.log 2>$O/tn.err; tail -1 $O/tn.log > $O/r06_bench_tn_full.json; cut -c1-220 $O/r06_bench_tn_full.json; tail -2 $O/tn.err
+timeout 300 python bench.py --workload s1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-end-to-end > $O/s1.log 2>/dev/null; tail -1 $O/s1.log > $O/r06_bench_s1.json; cut -c1-220 $O/r06_bench_s1.json
+timeout 1200 python bench.py --workload tn --steps 5 --warmup 2 --full --no-cpu-baseline --no-end-to-end > $O/tn.log 2>$O/tn.err; tail -1 $O/tn.log > $O/r06_bench_tn_full.json; cut -c1-220 $O/r06_bench_tn_full.json; tail -2 $O/tn.err
 fi

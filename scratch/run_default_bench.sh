@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/bench_default; mkdir -p $O
 S=$(date +%s)
-timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.log 2> $O/bench.err
+timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.log 2> $O/bench.err
 echo "bench wall $(( $(date +%s) - S )) s rc=$?"
 tail -1 $O/bench.log > $O/r02_bench.json
 python3 - <<PY

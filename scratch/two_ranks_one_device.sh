@@ -4,7 +4,7 @@
 # usage: two_ranks_one_device.sh [genome=1000000000]
 cd "$GRAFT_REPO_ROOT" || exit 1
 G=${1:-1000000000}
-F="--genome $G --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end"
+F="--genome $G --steps 3 --warmup 1 --full --no-cpu-baseline --no-end-to-end"
 summ() { python3 -c "
 import json,sys
 d=json.loads([l for l in open('$1') if l.startswith('{')][-1]); c=d['config']

@@ -676,7 +676,7 @@ def test_bench_two_ranks_share_the_device(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    flags = ["--genome", "60000000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-end-to-end", "--no-check"]
+    flags = ["--genome", "60000000", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-end-to-end", "--no-check"]
     one = subprocess.run([sys.executable, "bench.py", "--inner"] + flags, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert one.returncode == 0, one.stderr[-2000:]
     ref = json.loads(one.stdout.decode().strip().splitlines()[-1])
