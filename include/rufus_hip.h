@@ -447,6 +447,36 @@ int rfx_unique_to_subject(rfx_ctx*, const rfx_records* subject, const rfx_record
 rfx_records* rfx_records_subtract(rfx_ctx*, const rfx_records* a, const rfx_records* const* others, int n_others,
                                   uint32_t min_count, uint32_t max_count);
 
+/* The same net semantics (jf/jellyfish/merge_files.cc:69-155 + scripts/CheckJellyHashList.sh:12) WITHOUT the (pos,key)
+ * order, for a driver that needs of a sample's count only the histogram, the number of records and the set
+ * difference (a trio on one device).  (pos,key) is the order of jellyfish's FILE (sorted_dumper.hpp:80-112); a set
+ * difference needs only that both sides are grouped alike, and they are before any sort: every instance of a k-mer has
+ * the same minimizer, hence the same fine minimizer bin in every sample, and the leaf leaves its survivors bin after bin.
+ *
+ * rfx_count_finish_binned stands in for rfx_count_finish (count_main.cc:318-324 -L/-U, histo_main.cc:33-89): the
+ * survivors with lower <= count <= upper stay where the leaf staged them, grouped by fine minimizer bin (2^bits bins,
+ * rfx_binned_bits: chosen by the table, samples of different depth may differ -- bins are prefixes of one hash, so
+ * the coarser side's bin is 2^d whole bins of the other); histo as for rfx_count_finish.  MSP tables that were given
+ * their read blocks directly, over all positions, one device; shard passes (rfx_count_set_shard) and run maps as ever.
+ * A table of more than 4 GB of records is consumed.  NULL on error. */
+typedef struct rfx_binned rfx_binned;
+typedef struct rfx_candidates rfx_candidates;
+rfx_binned* rfx_count_finish_binned(rfx_table*, uint64_t lower, uint64_t upper, uint64_t* histo /* RFX_HISTO_BINS */);
+uint64_t rfx_binned_size(const rfx_binned*); /* number of records */
+int rfx_binned_bits(const rfx_binned*);
+void rfx_binned_free(rfx_binned*);
+/* rfx_records_subtract(subject, {control}, min_count, max_count), bin against bin: the survivors of `subject` with
+ * min_count <= count <= max_count that `control` (NULL: nobody) does not hold, as a candidate list.  Both of the same
+ * shard and k.  The subject's store is used up (counts of fallen candidates may be overwritten): strike once. */
+rfx_candidates* rfx_binned_strike(rfx_ctx*, rfx_binned* subject, const rfx_binned* control, uint32_t min_count,
+                                  uint32_t max_count);
+/* rfx_records_subtract(candidates, {control}, 0, ~0) for every further control: its keys are struck off the list */
+int rfx_candidates_strike(rfx_candidates*, const rfx_binned* control);
+/* entries of the list (struck ones included); _get: all of them, a struck one as ~0 -- canonical keys, no order */
+uint64_t rfx_candidates_size(const rfx_candidates*);
+int rfx_candidates_get(const rfx_candidates*, uint64_t* keys_out);
+void rfx_candidates_free(rfx_candidates*);
+
 /* ---------------------------------------------------------------------------------------------
  * K5: read filter (src/RUFUS.Filter.cpp:196-277, src/RUFUS.Filter.ss.cpp:164-203)
  * ------------------------------------------------------------------------------------------- */

@@ -23,7 +23,7 @@ import sys
 NOT_CHAIN = frozenset((
     "k_synth_reads", "k_copy16",
     "k_flag_absent", "k_flag_absent_tiled", "k_fa_bounds", "k_flag_gather", "k_flag_range", "k_flag_rank", "k_flag_present",
-    "k_compact_count", "k_compact_scatter", "k_scan_u64", "k_query",
+    "k_compact_count", "k_compact_scatter", "k_scan_u64", "k_query", "k_strike_bins", "k_strike_cands",
     "k_filter", "k_filter_q", "k_filter_p", "k_filter_fast", "k_filter_big", "k_hits_mask", "k_mask_count", "k_set_bitmap",
     "k_set_bitmap_big", "k_set_bitmap_q", "k_set_bitmap_p",
     "k_set_insert", "k_set_bitmap_packed", "k_records_checksum", "k_records_verify", "k_check_sorted",
@@ -37,7 +37,7 @@ NOT_CHAIN = frozenset((
 CHAIN_KNOWN = frozenset((
     "k_msp_part1", "k_msp_replay", "k_msp_count", "k_col_sums", "k_bin_group_sums", "k_bin_offsets", "k_scan_tail", "k_scan_sums",
     "k_scan_apply", "k_part2", "k_flag_if_gt", "k_slice_tag", "k_bin_hist", "k_bin_hist_stamp", "k_bin_hist_multi", "k_msp_leaf",
-    "k_surv_place", "k_surv_hist", "k_surv_sort", "k_histo_bins", "k_bin_count", "k_part1", "k_leaf", "k_leaf_compact", "k_bin_scatter",
+    "k_surv_place", "k_surv_hist", "k_surv_sort", "k_histo_bins", "k_histo_staged", "k_bin_count", "k_part1", "k_leaf", "k_leaf_compact", "k_bin_scatter",
     "k_tmp_start", "k_split_bins", "k_coarse_counts", "k_histo", "k_count_reads", "k_count_pairs", "k_table_pairs", "k_tile_count",
     "k_tile_scan", "k_tile_emit",
 ))

@@ -55,6 +55,15 @@ SIGNATURES = {
     "rfx_prof_names": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "rfx_reads_device_bytes": (C.c_uint64, [C.c_void_p]),
     "rfx_records_subtract": (C.c_void_p, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32]),
+    "rfx_count_finish_binned": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),
+    "rfx_binned_size": (C.c_uint64, [C.c_void_p]),
+    "rfx_binned_bits": (C.c_int, [C.c_void_p]),
+    "rfx_binned_free": (None, [C.c_void_p]),
+    "rfx_binned_strike": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rfx_candidates_strike": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rfx_candidates_size": (C.c_uint64, [C.c_void_p]),
+    "rfx_candidates_get": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_candidates_free": (None, [C.c_void_p]),
     "rfx_reads_upload": (C.c_void_p, [C.c_void_p, u64p, u32p, u32p, u32p, u32p, C.c_uint32]),
     "rfx_reads_free": (None, [C.c_void_p]),
     "rfx_reads_count": (C.c_uint32, [C.c_void_p]),
@@ -702,6 +711,12 @@ class CountTable:
         rec = Records(self.ctx, lib().rfx_count_finish(self._h, lower, upper, _p(h, u64p)))
         return (rec, h) if want_histo else rec
 
+    def finish_binned(self, lower: int = 0, upper: int = 2**64 - 1, want_histo: bool = False):
+        """The finish of a trio's count: the survivors stay grouped by fine minimizer bin (Binned), no (pos,key) sort."""
+        h = np.zeros(HISTO_BINS, dtype=np.uint64) if want_histo else None
+        b = Binned(self.ctx, lib().rfx_count_finish_binned(self._h, lower, upper, _p(h, u64p)))
+        return (b, h) if want_histo else b
+
     def finish_begin(self, lower: int = 0, upper: int = 2**64 - 1, want_histo: bool = False):
         """Queue the finish; returns a handle for finish_end().  Several tables can be queued before the
         first finish_end() waits."""
@@ -756,6 +771,60 @@ def records_subtract(ctx: Context, a: Records, others, min_count: int = 0, max_c
     """Records of `a` with min_count <= count <= max_count that occur in none of `others` (device resident)."""
     arr = (C.c_void_p * max(1, len(others)))(*[f._h for f in others])
     return Records(ctx, lib().rfx_records_subtract(ctx._h, a._h, arr, len(others), min_count, max_count))
+
+
+class Binned:
+    """A table's surviving (key, count) pairs where the count left them, minimizer bin after minimizer bin
+    (rfx_count_finish_binned): all a set difference needs, a k-mer's bin being the same in every sample."""
+
+    def __init__(self, ctx: Context, handle):
+        if not handle:
+            raise RufusError("binned records: " + lib().rfx_last_error().decode())
+        self.ctx, self._h = ctx, handle
+
+    def __len__(self):
+        return int(lib().rfx_binned_size(self._h))
+
+    @property
+    def bits(self):
+        return lib().rfx_binned_bits(self._h)
+
+    def free(self):
+        if self._h:
+            lib().rfx_binned_free(self._h)
+            self._h = None
+
+
+class Candidates:
+    """What a strike left of a subject's survivors (device resident; the keys come out in no particular order)."""
+
+    def __init__(self, ctx: Context, handle):
+        if not handle:
+            raise RufusError("candidates: " + lib().rfx_last_error().decode())
+        self.ctx, self._h = ctx, handle
+
+    def __len__(self):
+        """Candidates listed by the first strike (those a later control struck out included)."""
+        return int(lib().rfx_candidates_size(self._h))
+
+    def strike(self, control: Binned):
+        _check(lib().rfx_candidates_strike(self._h, control._h), "rfx_candidates_strike")
+
+    def keys(self) -> np.ndarray:
+        k = np.zeros(len(self), np.uint64)
+        _check(lib().rfx_candidates_get(self._h, _p(k, u64p)), "rfx_candidates_get")
+        return k[k != np.uint64(0xFFFFFFFFFFFFFFFF)]
+
+    def free(self):
+        if self._h:
+            lib().rfx_candidates_free(self._h)
+            self._h = None
+
+
+def binned_strike(ctx: Context, subject: Binned, control, min_count: int = 0, max_count: int = 0xFFFFFFFF) -> Candidates:
+    """Survivors of `subject` with min_count <= count <= max_count that `control` (a Binned, or None) does not hold."""
+    return Candidates(ctx, lib().rfx_binned_strike(ctx._h, subject._h, control._h if control is not None else None,
+                                                   min_count, max_count))
 
 
 OVL_SAM, OVL_CONTIG, OVL_REGION = 0, 1, 2

@@ -1833,6 +1833,13 @@ struct rfx_finish {
   std::vector<const uint64_t*> h_ptrs;
   std::vector<uint32_t> h_cur;
   std::vector<unsigned int> pflags;
+  // binned finish (rfx_count_finish_binned): the leaf's staging pool is sized for all survivors and kept, with the
+  // (chunk, offset) marks of every fine minimizer bin from bin_lo to bin_hi (of 2^bin_bits)
+  bool binned = false;
+  rfxk::msp_stage bstage;
+  uint2* bin_at = nullptr;
+  uint32_t bin_lo = 0, bin_hi = 0;
+  int bin_bits = 0;
 };
 
 // Survivors the leaf will stage per k-mer instance: what the last emit on this ctx saw (+30 %), else the first guess of
@@ -1842,27 +1849,30 @@ static uint64_t msp_surv_key(uint64_t lower, uint64_t kmers) { return (kmers >> 
 // table of this size saw -- else the last emit on this ctx -- is the guess (+30 %); the first emit assumes a quarter
 // (singletons dropped; 8 % for big inputs, where a rerun is cheaper than the memory) or 60 %.  A guess that is too
 // small costs one rerun with the capacity the cursors report.
-static double msp_surv_guess(rfx_ctx* c, uint64_t lower, uint64_t kmers) {
+static double msp_surv_guess(rfx_ctx* c, uint64_t lower, uint64_t kmers, double margin = 1.3) {
   double seen = c->msp_surv_frac[lower >= 2 ? 1 : 0];
   if (kmers >= (1ull << 28)) {  // (small tables: the last emit's ratio, as ever -- their sizes say little)
     auto it = c->msp_surv_by_size.find(msp_surv_key(lower, kmers));
     if (it != c->msp_surv_by_size.end()) seen = it->second;
   }
-  double frac = seen > 0 ? seen * 1.3 : (lower >= 2 ? (kmers > (1ull << 32) ? 0.08 : 0.25) : 0.6);
+  double frac = seen > 0 ? seen * margin : (lower >= 2 ? (kmers > (1ull << 32) ? 0.08 : 0.25) : 0.6);
   if (const char* ev = getenv("RFX_MSP_SURV_FRAC")) frac = atof(ev);
   return frac;
 }
 
 // the staging pool of a table's leaf launches (rfxk::msp_stage): keys, counts, and ONE zeroed block of fills + per-launch counters
-static int leaf_stage_alloc(rfx_ctx* c, uint32_t chunk, uint32_t n_chunks, uint32_t launches, rfxk::msp_stage* st) {
+// (binned: fill[n_chunks .. 2 n_chunks) = the chunk a workgroup went on with, rfxk::binned_view)
+static int leaf_stage_alloc(rfx_ctx* c, uint32_t chunk, uint32_t n_chunks, uint32_t launches, rfxk::msp_stage* st,
+                            bool binned = false) {
+  const size_t n_fill = (size_t)n_chunks * (binned ? 2 : 1);
   st->chunk = chunk;
   st->n_chunks = n_chunks;
   st->keys = (uint64_t*)dmalloc(c, (size_t)n_chunks * chunk * 8);
   st->counts = (uint32_t*)dmalloc(c, (size_t)n_chunks * chunk * 4);
-  st->fill = (uint32_t*)dmalloc(c, ((size_t)n_chunks + launches) * 4);
-  st->more = st->fill ? st->fill + n_chunks : nullptr;
+  st->fill = (uint32_t*)dmalloc(c, (n_fill + launches) * 4);
+  st->more = st->fill ? st->fill + n_fill : nullptr;
   if (!st->keys || !st->counts || !st->fill) return RFX_E_NOMEM;
-  HIPCHK(hipMemsetAsync(st->fill, 0, ((size_t)n_chunks + launches) * 4, c->stream));
+  HIPCHK(hipMemsetAsync(st->fill, 0, (n_fill + launches) * 4, c->stream));
   return RFX_OK;
 }
 static void leaf_stage_free(rfx_ctx* c, rfxk::msp_stage* st) {  // (stream-ordered pool: reused only by later work of the stream)
@@ -2022,11 +2032,31 @@ static int msp_leaf_refined(rfx_finish* f, int to_bits, const std::vector<std::v
   const uint64_t est_surv = R ? (uint64_t)((double)kmers * msp_surv_guess(c, f->lower, kmers) * (double)max_chunk_all / (double)R) : 0;
   rfxk::msp_leaf_plan(c, (uint32_t)std::min<size_t>((size_t)max_np * Ftot, 1u << 30), geo, max_chunk_all, est_surv, f->stage_extra,
                       &lgrid, &lchunk, &lpool);
+  if (f->binned) {
+    // The pool is the result: a chunk for every workgroup (each goes on from launch to launch where it stopped), + what
+    // all the table's survivors fill when every chunk is left at its emptiest, + what an earlier attempt came short by.
+    // It waits beside the next sample's count, so the margin on the survivors per instance the last emit saw is 12 %,
+    // not the 30 % of a store that lives for one emit (the same sample in the next step: the very ratio).
+    lchunk = rfxk::msp_leaf_chunk_kept(lchunk);
+    const uint64_t est_all = (uint64_t)((double)kmers * msp_surv_guess(c, f->lower, kmers, 1.12));
+    uint64_t more = est_all / rfxk::msp_leaf_chunk_room(geo, lchunk) + 16 + f->stage_extra;
+    if (getenv("RFX_LEAF_STAGE_TEST")) more = f->stage_extra;
+    lpool = (uint32_t)std::min<uint64_t>((uint64_t)lgrid + more, 1u << 30);
+    f->bin_bits = to_bits;
+    f->bin_lo = p_first * Ftot;
+    f->bin_hi = p_end * Ftot;
+    // (+ lgrid bins: a launch leaves the marks its workgroups' next bins begin at, the last launch behind the last bin)
+    const size_t at_bytes = ((size_t)(f->bin_hi - f->bin_lo) + lgrid) * 2 * sizeof(uint2);
+    f->bin_at = (uint2*)dmalloc(c, at_bytes);
+    if (!f->bin_at) { drop(); dfree(c, d_ptrs); return RFX_E_NOMEM; }
+    HIPCHK(hipMemsetAsync(f->bin_at, 0xFF, at_bytes, c->stream));  // (all ones: no launch came to the bin)
+  }
   rfxk::msp_stage stage;
   {
-    const int src = leaf_stage_alloc(c, lchunk, lpool, (uint32_t)cut.size(), &stage);
+    const int src = leaf_stage_alloc(c, lchunk, lpool, f->binned ? 1 : (uint32_t)cut.size(), &stage, f->binned);
     if (src) { drop(); dfree(c, d_ptrs); leaf_stage_free(c, &stage); return src; }
   }
+  if (f->binned) f->bstage = stage;  // (from here on the caller's: msp_binned_drop)
   for (size_t ci = 0; ci + 1 < cut.size(); ++ci) {
     const uint32_t p0 = cut[ci], np = cut[ci + 1] - cut[ci];
     const size_t n2 = (size_t)np * Ftot;
@@ -2100,11 +2130,17 @@ static int msp_leaf_refined(rfx_finish* f, int to_bits, const std::vector<std::v
     if (!chunk_all) continue;
     const uint64_t** d = d_ptrs + 3 * nleaf * ci;
     const hipError_t e = upload(c, d, ptrs.data(), 3 * nleaf * sizeof(void*));
-    if (e != hipSuccess) { drop(); dfree(c, d_ptrs); leaf_stage_free(c, &stage); return hip_fail(e, "msp_leaf_refined"); }
+    if (e != hipSuccess) {
+      drop();
+      dfree(c, d_ptrs);
+      if (!f->binned) leaf_stage_free(c, &stage);
+      return hip_fail(e, "msp_leaf_refined");
+    }
     rfxk::msp_leaf(c, d, d + nleaf, (int)nleaf, ptrs[0], ptrs[nleaf], (uint32_t)n2, t->k, t->canonical, t->lut_t, t->ntab,
                    sel_bits, 2 * t->k - 7, t->pos_lo, t->pos_hi, f->lower, f->upper, f->aw, f->ac, cur, (uint32_t)f->cap,
                    cur + ncur, cur + ncur + 1, cur + ncur + 2, geo, (const uint32_t* const*)(d + 2 * nleaf),
-                   (const uint32_t*)ptrs[2 * nleaf], stage, (uint32_t)ci, std::min<uint32_t>(lgrid, (uint32_t)n2));
+                   (const uint32_t*)ptrs[2 * nleaf], stage, (uint32_t)ci, std::min<uint32_t>(lgrid, (uint32_t)n2),
+                   f->binned ? f->bin_at + 2 * ((size_t)p0 * Ftot - f->bin_lo) : nullptr);
   }
   if (getenv("RFX_STAGE_DEBUG")) {  // (chunks each launch took beyond its workgroups' first ones)
     std::vector<uint32_t> more(cut.size(), 0);
@@ -2117,7 +2153,7 @@ static int msp_leaf_refined(rfx_finish* f, int to_bits, const std::vector<std::v
   }
   drop();  // stream-ordered pool
   dfree(c, d_ptrs);
-  leaf_stage_free(c, &stage);
+  if (!f->binned) leaf_stage_free(c, &stage);
   return RFX_OK;
 }
 
@@ -2925,6 +2961,230 @@ static rfx_records* msp_emit(rfx_table* t, uint64_t lower, uint64_t upper, uint6
   f.upper = upper;
   f.histo = histo;
   return msp_emit_finish(&f);
+}
+
+// ---- the binned route: count -> survivors grouped by fine minimizer bin -> strike, no (pos,key) sort ------------------
+// What a trio needs of a sample's count is the histogram, the number of records and a set difference; the difference needs
+// both sides grouped the same way, and the leaf leaves them so.  See rfx_msp.hip (k_strike_bins) and rufus_hip.h.
+struct rfx_binned {
+  rfx_ctx* ctx = nullptr;
+  int k = 0;
+  rfxk::msp_stage st;
+  uint2* bin_at = nullptr;
+  uint32_t bin_lo = 0, bin_hi = 0;
+  int bits = 0;
+  uint64_t n = 0;
+};
+struct rfx_candidates {
+  rfx_ctx* ctx = nullptr;
+  int k = 0, bits = 0;
+  uint64_t* keys = nullptr;  // RFX_EMPTY: struck out by a later control
+  uint32_t* bins = nullptr;
+  uint32_t n = 0;
+};
+
+static rfxk::binned_view binned_view_of(const rfx_binned* b) {
+  rfxk::binned_view v;
+  if (!b) return v;
+  v.keys = b->st.keys;
+  v.counts = b->st.counts;
+  v.fill = b->st.fill;
+  v.bin_at = b->bin_at;
+  v.chunk = b->st.chunk;
+  v.n_chunks = b->st.n_chunks;
+  v.bin_lo = b->bin_lo;
+  v.bin_hi = b->bin_hi;
+  v.bits = b->bits;
+  return v;
+}
+
+static void msp_binned_drop(rfx_finish* f) {
+  rfx_ctx* c = f->t->ctx;
+  leaf_stage_free(c, &f->bstage);
+  dfree(c, f->bin_at);
+  f->bin_at = nullptr;
+  dfree(c, f->bsq);
+  f->bsq = nullptr;
+}
+
+rfx_binned* rfx_count_finish_binned(rfx_table* t, uint64_t lower, uint64_t upper, uint64_t* histo) {
+  if (!t) return nullptr;
+  rfx_ctx* c = t->ctx;
+  (void)hipSetDevice(c->device);
+  if (t->pend_error) {
+    snprintf(g_err, sizeof g_err, "a deferred MSP re-partition failed (%s); the table is incomplete", rfx_strerror(t->pend_error));
+    return nullptr;
+  }
+  if (!t->table_active && t->segs->empty() && t->deferred->empty() && !t->peers) {  // no read at all: nothing in no bin
+    rfx_binned* b = new rfx_binned();
+    b->ctx = c;
+    b->k = t->k;
+    if (histo) memset(histo, 0, RFX_HISTO_BINS * 8);
+    return b;
+  }
+  if (t->table_active || t->segs->empty() || t->seg_kind != RFX_COUNT_MSP || !t->deferred->empty() || t->peers ||
+      t->pos_lo != 0 || t->pos_hi != (1ull << t->lsize)) {
+    snprintf(g_err, sizeof g_err, "rfx_count_finish_binned: an MSP table with read blocks of its own, over all positions, on one device");
+    return nullptr;
+  }
+  rfx_finish f;
+  f.t = t;
+  f.lower = lower;
+  f.upper = upper;
+  f.binned = true;
+  const uint32_t P1 = (uint32_t)rfxk::p1_bins();
+  const size_t ncur = (size_t)P1 * rfxk::p1_cur_stride();
+  const rfx_ord_cfg cfg0 = ord_cfg(t, 7);
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    int to_bits = 0;
+    bool refine = false;
+    uint64_t kmers = 0;
+    std::vector<std::vector<uint64_t>> h_bs;
+    // (always the refined leaf, whatever the table's size: it is the one that cuts the bins into launches by size, and a
+    // group that is at the target already is read in place)
+    if (msp_prepare_leaf(t, &to_bits, &refine, h_bs, &kmers, true) != RFX_OK) return nullptr;
+    f.kmers = kmers;
+    // one zeroed block: histogram, number of survivors, the three flag words behind the (unused) coarse cursors
+    const size_t zero_bytes = ((size_t)RFX_HISTO_BINS + 1) * 8 + (ncur + RFX_CUR_TAIL) * 4;
+    f.bsq = (uint64_t*)dmalloc(c, zero_bytes);
+    if (!f.bsq) { snprintf(g_err, sizeof g_err, "rfx_count_finish_binned: out of device memory"); return nullptr; }
+    unsigned long long* d_histo = (unsigned long long*)f.bsq;
+    uint32_t* cur = (uint32_t*)(d_histo + RFX_HISTO_BINS + 1);
+    hipError_t e = hipMemsetAsync(f.bsq, 0, zero_bytes, c->stream);
+    if (e != hipSuccess) { hip_fail(e, "rfx_count_finish_binned"); msp_binned_drop(&f); return nullptr; }
+    const int rc = msp_leaf_refined(&f, to_bits, h_bs, cfg0.sel_bits, cur, ncur);
+    if (rc) {
+      (void)ctx_sync(c);
+      msp_binned_drop(&f);
+      if (rc == RFX_E_NOMEM) snprintf(g_err, sizeof g_err, "rfx_count_finish_binned: out of device memory");
+      return nullptr;
+    }
+    rfxk::histo_staged(c, f.bstage, d_histo, d_histo + RFX_HISTO_BINS);
+    uint32_t tail[RFX_CUR_TAIL] = {0, 0, 0};
+    uint64_t total = 0;
+    std::vector<uint64_t> h(RFX_HISTO_BINS, 0);
+    e = queue_read(c, tail, cur + ncur, sizeof tail);
+    if (e == hipSuccess) e = queue_read(c, &total, d_histo + RFX_HISTO_BINS, 8);
+    if (e == hipSuccess && histo) e = queue_read(c, h.data(), d_histo, RFX_HISTO_BINS * 8);
+    if (e == hipSuccess) e = ctx_sync(c);
+    if (e != hipSuccess) { hip_fail(e, "rfx_count_finish_binned"); (void)ctx_sync(c); msp_binned_drop(&f); return nullptr; }
+    if (tail[1]) {
+      msp_binned_drop(&f);
+      snprintf(g_err, sizeof g_err, "MSP: a bin could not be split far enough to fit LDS");
+      return nullptr;
+    }
+    if (tail[0]) {  // the pool came short: once more with the chunks the counter asks for
+      f.stage_extra += tail[2] + tail[2] / 4 + 64;
+      msp_binned_drop(&f);
+      continue;
+    }
+    rfx_binned* b = new rfx_binned();
+    b->ctx = c;
+    b->k = t->k;
+    b->st = f.bstage;
+    b->bin_at = f.bin_at;
+    b->bin_lo = f.bin_lo;
+    b->bin_hi = f.bin_hi;
+    b->bits = f.bin_bits;
+    b->n = total;
+    f.bstage = rfxk::msp_stage{};
+    f.bin_at = nullptr;
+    msp_binned_drop(&f);
+    if (histo) memcpy(histo, h.data(), RFX_HISTO_BINS * 8);
+    if (kmers) {
+      c->msp_surv_frac[lower >= 2 ? 1 : 0] = (double)total / (double)kmers;
+      if (c->msp_surv_by_size.size() > 256) c->msp_surv_by_size.clear();
+      c->msp_surv_by_size[msp_surv_key(lower, kmers)] = (double)total / (double)kmers;
+    }
+    uint64_t rec_bytes = 0;
+    for (auto& sg : *t->segs) rec_bytes += sg.n * 8;
+    if (rec_bytes > (4ull << 30)) p2l_drop_segments(t);  // a big table is consumed by its finish, as by rfx_count_finish
+    return b;
+  }
+  snprintf(g_err, sizeof g_err, "MSP: the staging pool did not converge (internal error)");
+  return nullptr;
+}
+
+uint64_t rfx_binned_size(const rfx_binned* b) { return b ? b->n : 0; }
+int rfx_binned_bits(const rfx_binned* b) { return b ? b->bits : 0; }
+void rfx_binned_free(rfx_binned* b) {
+  if (!b) return;
+  (void)hipSetDevice(b->ctx->device);
+  leaf_stage_free(b->ctx, &b->st);
+  dfree(b->ctx, b->bin_at);
+  delete b;
+}
+
+rfx_candidates* rfx_binned_strike(rfx_ctx* c, rfx_binned* subject, const rfx_binned* control, uint32_t min_count,
+                                  uint32_t max_count) {
+  if (!c || !subject || subject->ctx != c || (control && (control->ctx != c || control->k != subject->k))) {
+    snprintf(g_err, sizeof g_err, "rfx_binned_strike: bad argument");
+    return nullptr;
+  }
+  (void)hipSetDevice(c->device);
+  const rfxk::binned_view S = binned_view_of(subject), C = binned_view_of(control);
+  // what a control leaves of a shard's candidates is little; a list that comes short is made again as long as the counter says
+  uint64_t cap = std::max<uint64_t>(1u << 16, subject->n / 256);
+  if (!control) cap = std::max<uint64_t>(cap, subject->n / 4);
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), 0xFFFFFFFFull);
+    uint64_t* keys = (uint64_t*)dmalloc(c, cap * 8);
+    uint32_t* bins = (uint32_t*)dmalloc(c, cap * 4);
+    uint32_t* d_n = (uint32_t*)dmalloc(c, 4);
+    auto drop = [&] { dfree(c, keys); dfree(c, bins); dfree(c, d_n); };
+    if (!keys || !bins || !d_n) { drop(); snprintf(g_err, sizeof g_err, "rfx_binned_strike: out of device memory"); return nullptr; }
+    hipError_t e = hipMemsetAsync(d_n, 0, 4, c->stream);
+    uint32_t n = 0;
+    if (e == hipSuccess) {
+      rfxk::strike_bins(c, S, C, min_count, max_count, keys, bins, (uint32_t)cap, d_n);
+      e = queue_read(c, &n, d_n, 4);
+    }
+    if (e == hipSuccess) e = ctx_sync(c);
+    if (e != hipSuccess) { hip_fail(e, "rfx_binned_strike"); (void)ctx_sync(c); drop(); return nullptr; }
+    dfree(c, d_n);
+    if (n > cap) {
+      dfree(c, keys);
+      dfree(c, bins);
+      cap = n;
+      continue;
+    }
+    rfx_candidates* r = new rfx_candidates();
+    r->ctx = c;
+    r->k = subject->k;
+    r->bits = subject->bits;
+    r->keys = keys;
+    r->bins = bins;
+    r->n = n;
+    return r;
+  }
+  snprintf(g_err, sizeof g_err, "rfx_binned_strike: the candidate list did not converge (internal error)");
+  return nullptr;
+}
+
+int rfx_candidates_strike(rfx_candidates* a, const rfx_binned* control) {
+  if (!a || !control || a->ctx != control->ctx || a->k != control->k) return RFX_E_INVAL;
+  rfx_ctx* c = a->ctx;
+  (void)hipSetDevice(c->device);
+  rfxk::strike_cands(c, a->keys, a->bins, a->n, a->bits, binned_view_of(control));
+  HIPCHK(ctx_sync(c));  // (the caller frees the control next)
+  return RFX_OK;
+}
+
+uint64_t rfx_candidates_size(const rfx_candidates* a) { return a ? a->n : 0; }
+int rfx_candidates_get(const rfx_candidates* a, uint64_t* keys_out) {
+  if (!a || (a->n && !keys_out)) return RFX_E_INVAL;
+  if (!a->n) return RFX_OK;
+  (void)hipSetDevice(a->ctx->device);
+  HIPCHK(ctx_sync(a->ctx));
+  HIPCHK(hipMemcpy(keys_out, a->keys, (size_t)a->n * 8, hipMemcpyDeviceToHost));
+  return RFX_OK;
+}
+void rfx_candidates_free(rfx_candidates* a) {
+  if (!a) return;
+  (void)hipSetDevice(a->ctx->device);
+  dfree(a->ctx, a->keys);
+  dfree(a->ctx, a->bins);
+  delete a;
 }
 
 static void p2l_drop_segments(rfx_table* t) {

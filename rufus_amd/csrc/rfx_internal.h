@@ -440,7 +440,7 @@ void msp_replay(rfx_ctx*, const rfx_reads_view&, const void* map, int k, int can
 inline uint64_t msp_part1_slack(int grid, int slab_log2) { return (uint64_t)grid * 3u << slab_log2; }
 // The staging pool of the leaf's launches (rfx_msp.hip k_msp_leaf / k_surv_place): n_chunks chunks of `chunk` (key, count)
 // pairs, fill[n_chunks] (zeroed once: k_surv_place puts every fill back to 0), more[launches] (zeroed once: chunks handed
-// out beyond the first `grid` of launch i).
+// out beyond the first `grid` of launch i).  A pool that is kept (binned_view): more[0] hands out every chunk.
 struct msp_stage {
   uint64_t* keys = nullptr;
   uint32_t* counts = nullptr;
@@ -455,7 +455,31 @@ void msp_leaf(rfx_ctx*, const uint64_t* const* seg_inst, const uint64_t* const* 
               unsigned int* stage_short /* chunks the pool came short by (max over the launches) */,
               int geo /* 0: 1024 threads + 8192 slots, 1: 768 + 4096 (two per CU) */,
               const uint32_t* const* seg_ext, const uint32_t* ext0 /* the records' planes */, const msp_stage& st,
-              uint32_t launch /* index into st.more */, uint32_t grid /* from msp_leaf_plan */);
+              uint32_t launch /* index into st.more */, uint32_t grid /* from msp_leaf_plan */,
+              uint2* bin_at = nullptr /* binned finish: [2 b], [2 b + 1] = (chunk, offset) where bin b's survivors begin / end;
+                                         written up to bin P + grid - 1 (the marks a next launch goes on from) */);
+// ---- the binned route (rfx_binned, rfx_api.hip): the staging pool IS the result ----
+// A table's survivors where the leaf left them: the pool (fill[n_chunks .. 2 n_chunks) = the chunk a workgroup went on with
+// after chunk i) and bin_at[2 (b - bin_lo)], [.. + 1] = (chunk, offset) where the survivors of fine minimizer bin b (of 2^bits)
+// begin / end (all ones: no launch came to it); bins outside [bin_lo, bin_hi) are empty.
+struct binned_view {
+  const uint64_t* keys = nullptr;
+  uint32_t* counts = nullptr;
+  const uint32_t* fill = nullptr;
+  const uint2* bin_at = nullptr;
+  uint32_t chunk = 0, n_chunks = 0, bin_lo = 0, bin_hi = 0;
+  int bits = 0;
+};
+uint32_t msp_leaf_chunk_room(int geo, uint32_t chunk);  // entries a chunk holds at least before its workgroup moves on
+uint32_t msp_leaf_chunk_kept(uint32_t chunk);           // the chunk size of a pool that is kept, given msp_leaf_plan's
+// count-of-counts of the staged survivors (span k_histo) + their number
+void histo_staged(rfx_ctx*, const msp_stage&, unsigned long long* d_histo, unsigned long long* d_total);
+// candidates of S (lo <= count <= hi) that C (bin_at == null: nobody) does not hold -> (key, bin of S), *out_n counts on
+// beyond cap; S's counts of fallen candidates may be put to 0
+void strike_bins(rfx_ctx*, const binned_view& S, const binned_view& C, uint32_t lo, uint32_t hi, uint64_t* out_k, uint32_t* out_b,
+                 uint32_t cap, uint32_t* out_n);
+// keys[i] = RFX_EMPTY where C holds candidate i (of bin bins[i] of 2^bits)
+void strike_cands(rfx_ctx*, uint64_t* keys, const uint32_t* bins, uint32_t n, int bits, const binned_view& C);
 void msp_leaf_plan(rfx_ctx*, uint32_t P, int geo, uint64_t n_records, uint64_t est_survivors, uint32_t extra, uint32_t* grid,
                    uint32_t* chunk, uint32_t* n_chunks);
 void surv_hist(rfx_ctx*, const uint64_t* buf_a, const uint32_t* coarse_cur, uint32_t cap_a, uint32_t P2, int shift2,

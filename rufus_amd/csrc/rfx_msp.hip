@@ -973,7 +973,7 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
     const uint32_t* __restrict__ ext0, uint32_t P, int k, uint64_t lower, uint64_t upper,
     uint64_t* __restrict__ stage_k, uint32_t* __restrict__ stage_c, uint32_t CH, uint32_t* __restrict__ stage_fill,
     uint32_t* __restrict__ stage_more, uint32_t n_chunks, unsigned int* __restrict__ flag, unsigned int* __restrict__ err,
-    unsigned int* __restrict__ stage_short, int force_mixed) {
+    unsigned int* __restrict__ stage_short, int force_mixed, uint2* __restrict__ bin_at) {
   constexpr int TBL_LOG2 = GEO ? 12 : 13, TBL = 1 << TBL_LOG2, BLK = (int)MSP_LEAF_BLK(GEO), FILL = TBL * 3 / 4;
   static_assert(MSP_LEAF_PASS_MAX(GEO) >= (uint32_t)(FILL + BLK) && FILL + BLK <= TBL, "what a pass can leave behind fits the chunk and the table");
   constexpr int RC_LOG2 = TBL_LOG2 - (GEO ? RFX_RC_SHRINK : 2), RC = 1 << RC_LOG2, KMAP = TBL;
@@ -1028,8 +1028,31 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
     s_rmin[i] = ~0u;
     s_rmax[i] = 0;
   }
-  if (threadIdx.x == 0) s_chunk = blockIdx.x;  // (the launch's pool: gridDim.x chunks handed out here, the others by stage_more)
+  // (the launch's pool: gridDim.x chunks handed out here, the others by stage_more.  bin_at != null -- the survivors STAY in
+  // the pool, rfx_binned: every chunk of every launch comes from the one counter, a chunk is never used twice, and a
+  // workgroup goes on where a workgroup of the launch before stopped -- that one left the mark of its "next bin" in this
+  // launch's range, see the end of the bin loop -- so that a launch's last chunks do not stay half empty, 16 launches x
+  // 2048 of them.  No such mark (all ones): a fresh chunk.)
   if (threadIdx.x < 2) s_nd[threadIdx.x] = s_ovf[threadIdx.x] = s_nk[threadIdx.x] = s_ns[threadIdx.x] = s_mixed[threadIdx.x] = 0;
+  if (threadIdx.x == 0) {
+    uint32_t ch0 = blockIdx.x;
+    if (bin_at) {
+      const uint2 at0 = bin_at[2 * (size_t)blockIdx.x];
+      if (at0.x < n_chunks) {
+        ch0 = at0.x;
+        s_ns[0] = at0.y;  // (the chunk's fill reaches the other threads as the first pass's survivor count: `used` += s_ns)
+      } else {
+        ch0 = atomicAdd(stage_more, 1u);
+        if (ch0 >= n_chunks) {  // the pool is spent (see the chunk switch below): results void, the host runs the leaf again
+          atomicExch(flag, 1u);
+          atomicMax(stage_short, ch0 - n_chunks + 1u);
+          ch0 = 0;
+        }
+        bin_at[2 * (size_t)blockIdx.x] = make_uint2(ch0, 0u);  // where the first bin's survivors begin
+      }
+    }
+    s_chunk = ch0;
+  }
   uint32_t used = 0;  // entries of the staging chunk in use (the same in every thread)
   uint32_t X = 0;     // parity of the pass
   __syncthreads();
@@ -1233,12 +1256,13 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
         if (threadIdx.x == 0) {
           const uint32_t mine = s_chunk;
           stage_fill[mine] = used;
-          uint32_t nx = gridDim.x + atomicAdd(stage_more, 1u);
+          uint32_t nx = (bin_at ? 0u : gridDim.x) + atomicAdd(stage_more, 1u);
           if (nx >= n_chunks) {  // the pool is spent: the host runs the launch again with the pool the counters ask for;
             atomicExch(flag, 1u);  // until then this workgroup writes over its own chunk (results void)
             atomicMax(stage_short, nx - n_chunks + 1u);
             nx = mine;
           }
+          if (bin_at) stage_fill[n_chunks + mine] = nx;  // (binned: the chunk a reader goes on with)
           s_chunk = nx;
         }
         used = 0;
@@ -1265,6 +1289,11 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
       }
     }
     if (failed && threadIdx.x == 0) atomicExch(err, 1u);
+    if (bin_at && threadIdx.x == 0) {  // the bin's survivors end here (thread 0 wrote s_chunk itself), the next bin's begin
+      const uint2 at = make_uint2(s_chunk, used);  // (a next bin beyond P: the first bin of a workgroup of the next launch)
+      bin_at[2 * (size_t)bin + 1] = at;
+      bin_at[2 * ((size_t)bin + gridDim.x)] = at;
+    }
   }
   if (threadIdx.x == 0) stage_fill[s_chunk] = used;
 }
@@ -1542,6 +1571,202 @@ __global__ __launch_bounds__(SS_BLOCK) void k_surv_sort(const uint64_t* __restri
   }
 }
 
+// ---- the binned route (rfx_binned): a table's survivors stay where the leaf staged them ----------------------------------
+// Every k-mer of a minimizer bin is in that bin in EVERY sample, and k_msp_leaf leaves a bin's survivors as one run of its
+// workgroup's chunks: bin_at[2 b] = (chunk, offset) where the run begins, bin_at[2 b + 1] where it ends, fill[chunk] how far
+// a chunk in between was filled, fill[n_chunks + chunk] the chunk the workgroup went on with.  A set difference needs no
+// more than that: the control's survivors of a bin into an LDS set, the subject's probe it.
+
+// fn(first entry of the chunk, begin, end) for every stretch of bin `gbin`'s survivors (the same in every lane)
+// the marks of bin gbin: (begin chunk, offset, end chunk, offset); all ones: an empty bin
+__device__ __forceinline__ uint4 binned_marks(const rfxk::binned_view& v, uint32_t gbin) {
+  if (!v.bin_at || gbin < v.bin_lo || gbin >= v.bin_hi) return make_uint4(~0u, ~0u, ~0u, ~0u);
+  return reinterpret_cast<const uint4*>(v.bin_at)[gbin - v.bin_lo];
+}
+template <class F>
+__device__ __forceinline__ void binned_segments(const rfxk::binned_view& v, const uint4 m, F&& fn) {
+  const uint2 a = make_uint2(m.x, m.y), e = make_uint2(m.z, m.w);
+  if (e.x >= v.n_chunks) return;  // (all ones: no launch came to this bin)
+  uint32_t ch = a.x, o = a.y;
+  for (uint32_t hops = 0; hops <= v.n_chunks && ch < v.n_chunks; ++hops) {
+    const bool last = ch == e.x;
+    const uint32_t end = min(last ? e.y : v.fill[ch], v.chunk);
+    if (end > o) fn((size_t)ch * v.chunk, o, end);
+    if (last) break;
+    ch = v.fill[v.n_chunks + ch];
+    o = 0;
+  }
+}
+template <class F>
+__device__ __forceinline__ void binned_segments(const rfxk::binned_view& v, uint32_t gbin, F&& fn) {
+  binned_segments(v, binned_marks(v, gbin), fn);
+}
+// fn(bin, ...) over bins [b0, b1); `first`: the marks of b0, fetched by the caller
+template <class F>
+__device__ __forceinline__ void binned_range(const rfxk::binned_view& v, uint32_t b0, uint32_t b1, const uint4 first, F&& fn) {
+  for (uint32_t b = b0; b < b1; ++b)
+    binned_segments(v, b == b0 ? first : binned_marks(v, b), [&](size_t f0, uint32_t o, uint32_t e) { fn(b, f0, o, e); });
+}
+
+// survivors of a lane -> the candidate list, one reservation per wave that has any (few have: what a control leaves of a bin)
+__device__ __forceinline__ void cand_append(bool surv, uint64_t key, uint32_t bin, uint64_t* __restrict__ out_k,
+                                            uint32_t* __restrict__ out_b, uint32_t cap, uint32_t* __restrict__ out_n) {
+  const unsigned long long m = __ballot(surv);
+  if (!m) return;
+  const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll(m) - 1u;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(out_n, (uint32_t)__popcll(m));
+  base = __shfl(base, (int)leader, 64);
+  if (surv) {
+    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (at < cap) {  // (a list that came short: the counter goes on, the host runs the strike again with what it asks for)
+      out_k[at] = key;
+      out_b[at] = bin;
+    }
+  }
+}
+
+constexpr int SB_BLK = 128, SB_SET_LOG2 = 11, SB_SET = 1 << SB_SET_LOG2, SB_TILE = SB_SET / 2;
+__device__ __forceinline__ uint32_t sb_hash(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40); }
+
+// Subject S against control C, unit after unit (a unit: a bin of the coarser of the two sides -- bins are prefixes of one
+// hash, so it is 2^d whole bins of the other side); one workgroup per unit.  The control's survivors of the unit go into
+// the set, SB_TILE at a time; every candidate of the subject with lo <= count <= hi that the set does not hold goes to
+// the list as (key, its bin in S).  One tile (the rule: a bin averages a few hundred survivors): one pass over the
+// subject's entries and nothing written back.  Several (a bin that the leaf halved again and again): the lane that owns a
+// candidate puts its count to 0 when the candidate falls, a plain store, and a last pass lists what still has one.
+// C.bin_at == null: no control, the range alone.
+__global__ __launch_bounds__(SB_BLK) void k_strike_bins(const rfxk::binned_view S, const rfxk::binned_view C, int ubits, uint32_t u_lo,
+                                                        uint32_t u_hi, uint32_t lo, uint32_t hi, uint64_t* __restrict__ out_k,
+                                                        uint32_t* __restrict__ out_b, uint32_t cap, uint32_t* __restrict__ out_n) {
+  __shared__ unsigned long long s_set[SB_SET];
+  const int ds = S.bits - ubits, dc = C.bin_at ? C.bits - ubits : 0;
+  for (uint32_t u = u_lo + blockIdx.x; u < u_hi; u += gridDim.x) {
+    uint32_t n_s = 0, n_c = 0;
+    const uint32_t s0 = u << ds, s1 = (u + 1u) << ds, c0 = u << dc, c1 = C.bin_at ? (u + 1u) << dc : c0;
+    const uint4 ms = binned_marks(S, s0), mc = binned_marks(C, c0);  // (both sides' first marks are asked for at once)
+    binned_range(S, s0, s1, ms, [&](uint32_t, size_t, uint32_t o, uint32_t e) { n_s += e - o; });
+    if (!n_s) continue;
+    binned_range(C, c0, c1, mc, [&](uint32_t, size_t, uint32_t o, uint32_t e) { n_c += e - o; });
+    const uint32_t tiles = n_c ? (n_c + SB_TILE - 1u) / SB_TILE : 1u;
+    const bool single = tiles == 1u;
+    for (uint32_t t = 0; t < tiles; ++t) {
+      const uint32_t t0 = t * SB_TILE, t1 = min(t0 + (uint32_t)SB_TILE, n_c);
+      uint32_t lg = 8;
+      while ((1u << lg) < 2u * (t1 - t0)) ++lg;  // (<= SB_SET_LOG2: the set is at most half full)
+      const uint32_t mask = (1u << lg) - 1u;
+      for (uint32_t i = threadIdx.x; i <= mask; i += SB_BLK) s_set[i] = RFX_EMPTY;
+      __syncthreads();
+      if (t1 > t0) {
+        uint32_t idx0 = 0;  // entries of the unit before this stretch
+        binned_range(C, c0, c1, mc, [&](uint32_t, size_t first, uint32_t o, uint32_t e) {
+            const uint32_t from = max(idx0, t0), to = min(idx0 + (e - o), t1);
+            for (uint32_t i = from + threadIdx.x; i < to; i += SB_BLK) {
+              const unsigned long long key = C.keys[first + o + (i - idx0)];
+              uint32_t h = sb_hash(key) & mask;
+              for (;;) {
+                const unsigned long long old = atomicCAS(&s_set[h], (unsigned long long)RFX_EMPTY, key);
+                if (old == RFX_EMPTY || old == key) break;
+                h = (h + 1u) & mask;
+              }
+            }
+            idx0 += e - o;
+          });
+      }
+      __syncthreads();
+      binned_range(S, s0, s1, ms, [&](uint32_t b, size_t first, uint32_t o, uint32_t e) {
+          for (uint32_t i0 = o; i0 < e; i0 += SB_BLK) {  // (every lane takes every trip: the list is filled wave by wave)
+            const uint32_t i = i0 + threadIdx.x;
+            uint64_t key = 0;
+            uint32_t c = 0;
+            if (i < e) {
+              c = S.counts[first + i];
+              key = S.keys[first + i];
+              bool drop = false;
+              if (t == 0 && c && (c < lo || c > hi)) drop = true;
+              if (c && !drop && t1 > t0) {
+                uint32_t h = sb_hash(key) & mask;
+                for (;;) {
+                  const unsigned long long v = s_set[h];
+                  if (v == key) drop = true;
+                  if (v == key || v == RFX_EMPTY) break;
+                  h = (h + 1u) & mask;
+                }
+              }
+              if (drop) {
+                c = 0;
+                if (!single) S.counts[first + i] = 0;
+              }
+            }
+            if (single) cand_append(c != 0, key, b, out_k, out_b, cap, out_n);
+          }
+        });
+      __syncthreads();  // (the set is cleared for the next tile / unit)
+    }
+    if (!single)
+      binned_range(S, s0, s1, ms, [&](uint32_t b, size_t first, uint32_t o, uint32_t e) {
+          for (uint32_t i0 = o; i0 < e; i0 += SB_BLK) {
+            const uint32_t i = i0 + threadIdx.x;
+            const bool live = i < e && S.counts[first + i] != 0;
+            cand_append(live, live ? S.keys[first + i] : 0ull, b, out_k, out_b, cap, out_n);
+          }
+        });
+  }
+}
+
+// The later controls: the candidates the first one left are few, so a wave takes one, reads the control's survivors of the
+// candidate's bin (of the bins it covers, or the bin that covers it) and lane 0 strikes the key out when one of them is it.
+__global__ __launch_bounds__(256) void k_strike_cands(uint64_t* __restrict__ keys, const uint32_t* __restrict__ bins, uint32_t n,
+                                                      int bits, const rfxk::binned_view C) {
+  const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * 256u + threadIdx.x) >> 6, n_waves = gridDim.x * 4u;
+  for (uint32_t i = wave; i < n; i += n_waves) {
+    const uint64_t key = keys[i];
+    if (key == RFX_EMPTY) continue;
+    const uint32_t sb = bins[i];
+    const uint32_t b0 = C.bits >= bits ? sb << (C.bits - bits) : sb >> (bits - C.bits);
+    const uint32_t b1 = C.bits >= bits ? (sb + 1u) << (C.bits - bits) : b0 + 1u;
+    bool found = false;
+    for (uint32_t b = b0; b < b1; ++b)
+      binned_segments(C, b, [&](size_t first, uint32_t o, uint32_t e) {
+        for (uint32_t j = o + lane; j < e; j += 64u) found |= C.keys[first + j] == key;
+      });
+    if (__ballot(found) && lane == 0) keys[i] = RFX_EMPTY;
+  }
+}
+
+// count-of-counts and number of the survivors in a staging pool (rfx_binned: what k_histo_bins is to the coarse pos bins)
+__global__ __launch_bounds__(256) void k_histo_staged(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ fill,
+                                                       const uint32_t* __restrict__ more, uint32_t CH, uint32_t n_chunks,
+                                                       unsigned long long* __restrict__ g_histo,
+                                                       unsigned long long* __restrict__ g_total) {
+  __shared__ uint32_t s_h[RFX_HISTO_BINS];
+  for (int i = threadIdx.x; i < RFX_HISTO_BINS; i += 256) s_h[i] = 0;
+  __syncthreads();
+  const uint32_t n_used = min(*more, n_chunks);
+  unsigned long long total = 0;
+  for (uint32_t ch = blockIdx.x; ch < n_used; ch += gridDim.x) {
+    const uint32_t n = min(fill[ch], CH);
+    const uint32_t* const src = counts + (size_t)ch * CH;
+    total += n;
+    uint32_t i = threadIdx.x;
+    for (; i + 3u * 256u < n; i += 4u * 256u) {
+      uint32_t c[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) c[q] = src[i + q * 256];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) atomicAdd(&s_h[c[q] > 10001u ? 10001u : c[q]], 1u);
+    }
+    for (; i < n; i += 256u) {
+      const uint32_t c = src[i];
+      atomicAdd(&s_h[c > 10001u ? 10001u : c], 1u);
+    }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < RFX_HISTO_BINS; b += 256)
+    if (s_h[b]) atomicAdd(&g_histo[b], (unsigned long long)s_h[b]);
+  if (threadIdx.x == 0 && total) atomicAdd(g_total, total);
+}
+
 }  // namespace
 
 namespace rfxk {
@@ -1642,15 +1867,15 @@ void msp_leaf(rfx_ctx* c, const uint64_t* const* seg_inst, const uint64_t* const
               int ntab, int sel_bits, int shift1, uint64_t pos_lo, uint64_t pos_hi, uint64_t lower, uint64_t upper,
               uint64_t* out_w, uint32_t* out_c, uint32_t* cur, uint32_t cap, unsigned int* flag, unsigned int* err,
               unsigned int* stage_short, int geo, const uint32_t* const* seg_ext, const uint32_t* ext0, const msp_stage& st,
-              uint32_t launch, uint32_t grid) {
+              uint32_t launch, uint32_t grid, uint2* bin_at) {
   const int force_mixed = getenv("RFX_LEAF_FORCE_MIXED") != nullptr;
-  uint32_t* const more = st.more + launch;
+  uint32_t* const more = st.more + (bin_at ? 0u : launch);  // (binned: one counter hands out the chunks of all launches)
   {
     rfx_span sp(c, "k_msp_leaf");
 #define RFX_MSP_LEAF(CANON, GEO)                                                                                        \
   hipLaunchKernelGGL((k_msp_leaf<CANON, GEO>), dim3(grid), dim3(MSP_LEAF_BLK(GEO)), 0, c->stream, seg_inst, seg_bs, nseg, \
                      inst0, bs0, seg_ext, ext0, P, k, lower, upper, st.keys, st.counts, st.chunk, st.fill, more,           \
-                     st.n_chunks, flag, err, stage_short, force_mixed)
+                     st.n_chunks, flag, err, stage_short, force_mixed, bin_at)
     if (canonical) {
       if (geo) RFX_MSP_LEAF(true, 1);
       else RFX_MSP_LEAF(true, 0);
@@ -1660,12 +1885,43 @@ void msp_leaf(rfx_ctx* c, const uint64_t* const* seg_inst, const uint64_t* const
     }
 #undef RFX_MSP_LEAF
   }
-  {
+  if (!bin_at) {  // (binned: the survivors stay in the staging pool, minimizer bin after minimizer bin)
     rfx_span sp(c, "k_surv_place");
     const uint32_t pg = std::min<uint32_t>(st.n_chunks, (uint32_t)c->n_cu * (uint32_t)std::max(1, 160 * 1024 / (16 * 1024 + SP_N * 12 + 2048)));
     hipLaunchKernelGGL(k_surv_place, dim3(pg), dim3(SP_BLK), 0, c->stream, st.keys, st.counts, st.chunk, st.fill, more, grid,
                        st.n_chunks, lut, ntab, sel_bits, shift1, pos_lo, pos_hi, out_w, out_c, cur, cap, flag);
   }
+}
+
+uint32_t msp_leaf_chunk_room(int geo, uint32_t chunk) { return chunk - MSP_LEAF_PASS_MAX(geo); }
+// A pool that is kept pays for the room a chunk is left with when its workgroup moves on (up to a pass's worth of
+// entries): a quarter of the 16384-entry chunk of a big input, a sixteenth of this one.
+uint32_t msp_leaf_chunk_kept(uint32_t chunk) { return chunk >= 16384u ? 65536u : chunk; }
+
+void histo_staged(rfx_ctx* c, const msp_stage& st, unsigned long long* d_histo, unsigned long long* d_total) {
+  rfx_span sp(c, "k_histo");
+  const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(st.n_chunks, (uint32_t)c->n_cu * 4));
+  hipLaunchKernelGGL(k_histo_staged, dim3(grid), dim3(256), 0, c->stream, st.counts, st.fill, st.more, st.chunk, st.n_chunks,
+                     d_histo, d_total);
+}
+
+void strike_bins(rfx_ctx* c, const binned_view& S, const binned_view& C, uint32_t lo, uint32_t hi, uint64_t* out_k,
+                 uint32_t* out_b, uint32_t cap, uint32_t* out_n) {
+  rfx_span sp(c, "k_strike_bins");
+  const int ubits = C.bin_at ? std::min(S.bits, C.bits) : S.bits;
+  const int ds = S.bits - ubits;
+  const uint32_t u_lo = S.bin_lo >> ds, u_hi = (uint32_t)((((uint64_t)S.bin_hi + (1u << ds) - 1)) >> ds);
+  if (u_hi <= u_lo) return;
+  const uint32_t grid = std::min<uint32_t>(u_hi - u_lo, (uint32_t)c->n_cu * 10);  // 16 KB of LDS: ten workgroups of two waves per CU
+  hipLaunchKernelGGL(k_strike_bins, dim3(grid), dim3(SB_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, out_k, out_b, cap,
+                     out_n);
+}
+
+void strike_cands(rfx_ctx* c, uint64_t* keys, const uint32_t* bins, uint32_t n, int bits, const binned_view& C) {
+  if (!n) return;
+  rfx_span sp(c, "k_strike_cands");
+  const uint32_t grid = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cu * 8);
+  hipLaunchKernelGGL(k_strike_cands, dim3(grid), dim3(256), 0, c->stream, keys, bins, n, bits, C);
 }
 
 void surv_hist(rfx_ctx* c, const uint64_t* buf_a, const uint32_t* coarse_cur, uint32_t cap_a, uint32_t P2, int shift2,

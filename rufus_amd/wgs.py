@@ -91,7 +91,10 @@ def plan_passes(n_reads_total: int, read_len: int, k: int, resident_bytes: int, 
     ~3 k-mer instances; 1 / (S x world) of the sample -- two copies alive at the peak of an exchange: the
     partition and the receive buffers, which the owner counts in place), the refinement scratch (1/8 of the records), the survivor
     arrays (44 B per surviving k-mer: two partition levels + the records), and the subject's candidate records
-    of this pass (20 B each; WgsTrio.run counts the subject first and keeps only them)."""
+    of this pass (20 B each; WgsTrio.run counts the subject first and keeps only them).
+    On the binned route of run() the survivors are 12-byte staged entries (the pool is ~1.2 x that) for the subject as
+    for the sample being counted, and the second partition level and the records do not exist; the estimate below is
+    left as it is -- it is then on the safe side, and the pass count stays what it was."""
     windows = n_reads_total * max(read_len - k + 1, 0)           # per sample
     distinct = windows / max(coverage_hint * (read_len - k + 1) / read_len, 1.0)
     for s in range(1, 257 // world):
@@ -136,6 +139,7 @@ class WgsTrio:
         self.count_wall_s = 0.0     # host wall time inside count_shard() in the last run() (every count ends with a wait)
         self.masks_are_views = False  # run()'s hit masks stay views of the ctx's page-locked read-back buffer (valid until the next run())
         self.replayed_blocks = 0    # blocks added by replay in the last run()
+        self.binned_counts = 0      # (sample, pass) counts of the last run() that ended on the binned route (run())
         # bytes of super-k-mer records this rank sent to / received from OTHER ranks in the last run() (the record
         # exchange of count_shard: RCCL all-to-all over xGMI; what stays on the rank is not counted)
         self.exchange_sent = self.exchange_received = 0
@@ -147,11 +151,18 @@ class WgsTrio:
         if self.passes * self.world > 256:
             raise ValueError("passes x ranks must not exceed the 256 virtual minimizer bins")
 
-    def _count_shard_local(self, blocks, shard: int, si):
+    def _count_shard_local(self, blocks, shard: int, si, binned: bool = False):
         """One device: the table of this (sample, shard).  Shard passes hash every block once per pass; with
         `early_budget` bytes of headroom (bench.py: what the device has left beside the peak of a step) the blocks are, as
         far as that goes, hashed ONCE for this shard and the next (rfx_count_set_early): the next shard's records wait
-        in a table of their own (self._early) and that pass is given only the other blocks."""
+        in a table of their own (self._early) and that pass is given only the other blocks.
+        binned: the count ends with the survivors grouped by minimizer bin (capi.Binned) instead of sorted records."""
+        def finish(t_):
+            if binned:
+                self.binned_counts += 1
+                return t_.finish_binned(self.lower, want_histo=True)
+            return t_.finish(self.lower, want_histo=True)
+
         held = self._early.pop((si, shard), None) if si is not None else None
         if held is not None:
             t, done = held
@@ -179,7 +190,7 @@ class WgsTrio:
                 self.replayed_blocks += t.replayed()
                 if shard == 0:
                     self._inject("maps", shard)      # (tests: the headroom turns out not to be there)
-                return t.finish(self.lower, want_histo=True)
+                return finish(t)
             todo = [i for i in range(len(blocks)) if i not in done]
             ahead = set()
             if si is not None and self.passes > 1 and shard + 1 < self.passes and self._early_left > 0 and not self.map_budget:
@@ -206,7 +217,7 @@ class WgsTrio:
                 nxt.adopt_early(t)
                 self._early[(si, shard + 1)] = (nxt, frozenset(ahead))
                 nxt = None
-            return t.finish(self.lower, want_histo=True)
+            return finish(t)
         finally:
             if nxt is not None:
                 nxt.free()
@@ -229,15 +240,18 @@ class WgsTrio:
         self._drop_early()
         self._drop_store()
 
-    def count_shard(self, blocks, shard: int, si=None):
+    def _local(self) -> bool:
+        return self.world == 1 and not (self.group is not None and os.environ.get("RFX_WGS_FORCE_EXCHANGE"))
+
+    def count_shard(self, blocks, shard: int, si=None, binned: bool = False):
         """Records (in (pos,key) order) + histogram of the k-mers of minimizer shard `shard` of `passes` --
         on N ranks: of this rank's 1/N of that shard.  The cut is flat over passes x ranks virtual shards
         (q = shard * N + rank of passes * N), so a pass is a contiguous range of bins split among the ranks:
         every rank partitions ITS blocks restricted to the pass (rfx_count_set_shard(shard, passes)), the
         records of owner g's bins are one contiguous run per segment -> one all_to_all_single per segment
         (RCCL over xGMI), the owner imports the runs and counts complete bins.  No partial counts, no reduce."""
-        if self.world == 1 and not (self.group is not None and os.environ.get("RFX_WGS_FORCE_EXCHANGE")):
-            return self._count_shard_local(blocks, shard, si)
+        if self._local():
+            return self._count_shard_local(blocks, shard, si, binned)
         t = capi.CountTable(self.ctx, self.k, self.size, True, mode=capi.COUNT_MSP)
         try:
             err = None
@@ -490,12 +504,23 @@ class WgsTrio:
             lap(f"pass {sh} sample {si} kept ({len(rec)})")
             return rec
         raw = getattr(self, "_cand_raw", False)
-        raw_bytes = len(cand) * 20 if raw else 0
-        nxt = (capi.records_subtract(self.ctx, cand, [rec], max(5, self.min_cov), self.max_cov) if raw else
-               capi.records_subtract(self.ctx, cand, [rec]))
+        if isinstance(rec, capi.Binned):
+            # The binned route: the first control is struck off the subject's staged survivors bin against bin (range and
+            # strike in one pass, as below); what is left is a short list, and every further control is looked up in it.
+            raw_bytes = len(cand) * 12 if raw else 0
+            if raw:
+                nxt = capi.binned_strike(self.ctx, cand, rec, max(5, self.min_cov), self.max_cov)
+                cand.free()
+                cand = nxt
+            else:
+                cand.strike(rec)
+        else:
+            raw_bytes = len(cand) * 20 if raw else 0
+            nxt = (capi.records_subtract(self.ctx, cand, [rec], max(5, self.min_cov), self.max_cov) if raw else
+                   capi.records_subtract(self.ctx, cand, [rec]))
+            cand.free()
+            cand = nxt
         self._cand_raw = False
-        cand.free()
-        cand = nxt
         # The step's peak is the count of the FIRST control of a pass (the subject's records wait beside it); from here on
         # the pass runs that much lower, and so may hold that much more of the next pass's records cut ahead -- provided the
         # samples they belong to are counted BEFORE the first control of that pass (run() reverses the controls' order on
@@ -540,7 +565,12 @@ class WgsTrio:
             cand, cands, shard_recs = None, {}, {}
             self._drop_early()
             self._early_left = int(self.early_budget) if self.world == 1 and not keep_shard_records else 0
-            self.replayed_blocks = 0
+            self.replayed_blocks = self.binned_counts = 0
+            # A plain run needs of every count the histogram, the number of records and the set difference -- none of which
+            # needs the (pos,key) order of jellyfish's file: the survivors stay grouped by minimizer bin (capi.Binned) and
+            # the controls are struck off bin against bin.  Verified or kept records, a group of ranks: sorted records, as
+            # ever; RFX_TRIO_SORTED=1 forces them (A/B, bisecting).
+            binned = self._local() and not verify and not keep_shard_records and not os.environ.get("RFX_TRIO_SORTED")
             self.exchange_sent = self.exchange_received = 0
             use_maps = self.map_budget > 0 and self.world == 1 and self.passes > 1 and not keep_shard_records
             if not use_maps:
@@ -594,7 +624,7 @@ class WgsTrio:
                     cand = cands.pop(sh, None)
                     blocks = samples[si]
                     t_c = time.perf_counter()
-                    rec, h = self.count_shard(blocks, sh, si)   # (its failures are agreed inside)
+                    rec, h = self.count_shard(blocks, sh, si, binned)   # (its failures are agreed inside)
                     self.count_wall_s += time.perf_counter() - t_c
                     recs.append(rec)
                     histos[si] += h
@@ -616,11 +646,12 @@ class WgsTrio:
                         kept.append(recs)
                     else:
                         if getattr(self, "_cand_raw", False):      # a subject without controls: the range alone
-                            nxt = capi.records_subtract(self.ctx, cand, [], max(5, self.min_cov), self.max_cov)
+                            nxt = (capi.binned_strike(self.ctx, cand, None, max(5, self.min_cov), self.max_cov) if binned else
+                                   capi.records_subtract(self.ctx, cand, [], max(5, self.min_cov), self.max_cov))
                             cand.free()
                             cand = nxt
                             self._cand_raw = False
-                        k_ = cand.get()[0]
+                        k_ = cand.keys() if binned else cand.get()[0]
                         cand.free()
                         cand = None
                     lap(f"pass {sh} set difference ({len(k_)} k-mers)")
