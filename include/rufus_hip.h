@@ -475,7 +475,35 @@ int rfx_candidates_strike(rfx_candidates*, const rfx_binned* control);
 /* entries of the list (struck ones included); _get: all of them, a struck one as ~0 -- canonical keys, no order */
 uint64_t rfx_candidates_size(const rfx_candidates*);
 int rfx_candidates_get(const rfx_candidates*, uint64_t* keys_out);
+/* The subject's count of every entry, in the order of rfx_candidates_get (a struck entry's count is unspecified): the
+ * second column of the hash list, `kmer count` (runRufus.sh:925-926, scripts/CheckJellyHashList.sh:12).  The strike
+ * notes it when it lists the candidate, so the subject's store may be freed before this is asked. */
+int rfx_candidates_get_counts(const rfx_candidates*, uint32_t* counts_out);
+/* The exclude databases of runRufus.sh -e (:738-740; merged into the set difference at :925 by jf/jellyfish/
+ * merge_files.cc:69-155): every live candidate that the (pos,key)-ordered record set holds is struck off, on the device
+ * (pos from the records' own matrix, then rfx_query's search).  The records may come from a count or from a .Jhash
+ * (rfx_records_load / _load_fd).  RFX_E_FORMAT when k differs, RFX_E_INVAL for records of another context. */
+int rfx_candidates_strike_records(rfx_candidates*, const rfx_records* exclude);
 void rfx_candidates_free(rfx_candidates*);
+/* A binned store read where it lies; none of these changes it.
+ * _get: every survivor in bin order (within a bin: the order the leaf left) -- key, count (count_main.cc:318-324 -L/-U),
+ * fine minimizer bin and flat index in the store, chunk * chunk size + offset (entry i of rfx_binned_dev_keys /
+ * _dev_counts); any output may be NULL.  *n_out is the number of survivors; RFX_E_RANGE (with *n_out set) when cap is
+ * short.  What `jellyfish dump` (jf/include/jellyfish/binary_dumper.hpp:156-203) is to a .Jhash, in no file's order.
+ * _checksum: the two sums of rfx_records_checksum over the store -- the shards of a count add up to the sorted route's.
+ * _verify: what the strike relies on, a workgroup per bin: out[0] = survivors that do not lie in the bin their own
+ * minimizer names, out[1] = counts outside [lower, upper] (count_main.cc:318-324), out[2] = keys that are not
+ * canonical (jf/include/jellyfish/mer_dna.hpp canonical(): the smaller of a k-mer and its reverse complement),
+ * out[3] = keys a bin holds more than once (each occurrence after the first, per tile of the bin),
+ * out[4] = sum of the counts (histo_main.cc:33-89: sum of i * histo[i]).  A correct store gives 0, 0, 0, 0.
+ * _query: `jellyfish query` (binary_dumper.hpp:156-203) on the store: the count of each canonical key, 0 if absent. */
+int rfx_binned_get(const rfx_binned*, uint64_t* keys_out, uint32_t* counts_out, uint32_t* bins_out, uint64_t* at_out,
+                   uint64_t cap, uint64_t* n_out);
+int rfx_binned_checksum(const rfx_binned*, uint64_t out[2]);
+int rfx_binned_verify(const rfx_binned*, uint64_t lower, uint64_t upper, uint64_t out[5]);
+int rfx_binned_query(const rfx_binned*, const uint64_t* canonical_keys, uint64_t n, uint32_t* counts_out);
+const uint64_t* rfx_binned_dev_keys(const rfx_binned*);   /* device addresses of the store's keys / counts */
+const uint32_t* rfx_binned_dev_counts(const rfx_binned*);
 
 /* ---------------------------------------------------------------------------------------------
  * K5: read filter (src/RUFUS.Filter.cpp:196-277, src/RUFUS.Filter.ss.cpp:164-203)

@@ -20,6 +20,7 @@ HISTO_BINS = 10002
 PACK_COUNT, PACK_FILTER = 1, 2
 COUNT_AUTO, COUNT_TABLE, COUNT_P2L, COUNT_MSP = 0, 1, 2, 3
 E_FULL, E_RANGE, E_MIXEDCASE = -4, -7, -6
+E_INVAL, E_FORMAT = -2, -8
 
 u8p, u32p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 
@@ -64,6 +65,14 @@ SIGNATURES = {
     "rfx_candidates_size": (C.c_uint64, [C.c_void_p]),
     "rfx_candidates_get": (C.c_int, [C.c_void_p, u64p]),
     "rfx_candidates_free": (None, [C.c_void_p]),
+    "rfx_candidates_get_counts": (C.c_int, [C.c_void_p, u32p]),
+    "rfx_candidates_strike_records": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rfx_binned_get": (C.c_int, [C.c_void_p, u64p, u32p, u32p, u64p, C.c_uint64, u64p]),
+    "rfx_binned_checksum": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_binned_verify": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),
+    "rfx_binned_query": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u32p]),
+    "rfx_binned_dev_keys": (C.c_void_p, [C.c_void_p]),
+    "rfx_binned_dev_counts": (C.c_void_p, [C.c_void_p]),
     "rfx_reads_upload": (C.c_void_p, [C.c_void_p, u64p, u32p, u32p, u32p, u32p, C.c_uint32]),
     "rfx_reads_free": (None, [C.c_void_p]),
     "rfx_reads_count": (C.c_uint32, [C.c_void_p]),
@@ -789,6 +798,55 @@ class Binned:
     def bits(self):
         return lib().rfx_binned_bits(self._h)
 
+    def _live(self):
+        if not self._h:
+            raise RufusError("binned records: freed")
+        return self._h
+
+    def get(self):
+        """Every survivor in bin order: (keys, counts, bins, at) -- `at` is the survivor's index in the store, i.e. entry
+        `at` of the arrays dev_ptrs() names (rfx_binned_get)."""
+        h = self._live()
+        n = len(self)
+        keys, counts = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        bins, at = np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        got = C.c_uint64(0)
+        _check(lib().rfx_binned_get(h, _p(keys, u64p), _p(counts, u32p), _p(bins, u32p), _p(at, u64p), n, C.byref(got)),
+               "rfx_binned_get")
+        if got.value != n:
+            raise RufusError(f"rfx_binned_get: {got.value} survivors in the bins, {n} counted by the finish")
+        return keys, counts, bins, at
+
+    def checksum(self) -> tuple:
+        """Records.checksum() of the store: the shards of a count add up to the sorted route's (rfx_binned_checksum)."""
+        o = np.zeros(2, dtype=np.uint64)
+        _check(lib().rfx_binned_checksum(self._live(), _p(o, u64p)), "rfx_binned_checksum")
+        return int(o[0]), int(o[1])
+
+    def verify(self, lower: int = 0, upper: int = 2**64 - 1) -> dict:
+        """What the strike relies on, checked on the device (all 0 but sum_counts when correct): every survivor canonical,
+        lower <= count <= upper, in the bin its own minimizer names, and there once (rfx_binned_verify)."""
+        if not 0 <= lower <= upper < 2**64:
+            raise ValueError("verify: 0 <= lower <= upper < 2^64")
+        o = np.zeros(5, dtype=np.uint64)
+        _check(lib().rfx_binned_verify(self._live(), lower, upper, _p(o, u64p)), "rfx_binned_verify")
+        return {"bad_bin": int(o[0]), "bad_count": int(o[1]), "not_canonical": int(o[2]), "duplicate": int(o[3]),
+                "sum_counts": int(o[4])}
+
+    def query(self, keys: np.ndarray) -> np.ndarray:
+        """The store's count of each canonical key, 0 where it does not hold the key (rfx_binned_query)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        if keys.ndim != 1:
+            raise ValueError("query: a flat array of keys")
+        out = np.zeros(len(keys), dtype=np.uint32)
+        _check(lib().rfx_binned_query(self._live(), _p(keys, u64p), len(keys), _p(out, u32p)), "rfx_binned_query")
+        return out
+
+    def dev_ptrs(self):
+        """Device addresses of the store's keys (uint64) and counts (uint32); get()'s `at` indexes both."""
+        L = lib()
+        return L.rfx_binned_dev_keys(self._live()), L.rfx_binned_dev_counts(self._live())
+
     def free(self):
         if self._h:
             lib().rfx_binned_free(self._h)
@@ -810,10 +868,33 @@ class Candidates:
     def strike(self, control: Binned):
         _check(lib().rfx_candidates_strike(self._h, control._h), "rfx_candidates_strike")
 
-    def keys(self) -> np.ndarray:
+    def strike_records(self, records: "Records"):
+        """Strike off every candidate that a (pos,key)-sorted record set holds -- an exclude database, from a count or
+        loaded from a .Jhash (rfx_candidates_strike_records)."""
+        if not isinstance(records, Records) or not records._h:
+            raise TypeError("strike_records: a live capi.Records")
+        _check(lib().rfx_candidates_strike_records(self._h, records._h), "rfx_candidates_strike_records")
+
+    def _raw_keys(self) -> np.ndarray:
         k = np.zeros(len(self), np.uint64)
         _check(lib().rfx_candidates_get(self._h, _p(k, u64p)), "rfx_candidates_get")
+        return k
+
+    def keys(self) -> np.ndarray:
+        k = self._raw_keys()
         return k[k != np.uint64(0xFFFFFFFFFFFFFFFF)]
+
+    def counts(self, raw_keys=None) -> np.ndarray:
+        """The subject's counts of the candidates keys() returns, in that order (rfx_candidates_get_counts)."""
+        c = np.zeros(len(self), np.uint32)
+        _check(lib().rfx_candidates_get_counts(self._h, _p(c, u32p)), "rfx_candidates_get_counts")
+        k = self._raw_keys() if raw_keys is None else raw_keys
+        return c[k != np.uint64(0xFFFFFFFFFFFFFFFF)]
+
+    def keys_counts(self):
+        """(keys(), counts()) with one read of the keys."""
+        k = self._raw_keys()
+        return k[k != np.uint64(0xFFFFFFFFFFFFFFFF)], self.counts(k)
 
     def free(self):
         if self._h:

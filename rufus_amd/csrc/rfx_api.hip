@@ -2968,7 +2968,7 @@ static rfx_records* msp_emit(rfx_table* t, uint64_t lower, uint64_t upper, uint6
 // both sides grouped the same way, and the leaf leaves them so.  See rfx_msp.hip (k_strike_bins) and rufus_hip.h.
 struct rfx_binned {
   rfx_ctx* ctx = nullptr;
-  int k = 0;
+  int k = 0, canonical = 1;
   rfxk::msp_stage st;
   uint2* bin_at = nullptr;
   uint32_t bin_lo = 0, bin_hi = 0;
@@ -2980,6 +2980,7 @@ struct rfx_candidates {
   int k = 0, bits = 0;
   uint64_t* keys = nullptr;  // RFX_EMPTY: struck out by a later control
   uint32_t* bins = nullptr;
+  uint32_t* counts = nullptr;  // the subject's count of every listed candidate
   uint32_t n = 0;
 };
 
@@ -3019,6 +3020,7 @@ rfx_binned* rfx_count_finish_binned(rfx_table* t, uint64_t lower, uint64_t upper
     rfx_binned* b = new rfx_binned();
     b->ctx = c;
     b->k = t->k;
+    b->canonical = t->canonical;
     if (histo) memset(histo, 0, RFX_HISTO_BINS * 8);
     return b;
   }
@@ -3081,6 +3083,7 @@ rfx_binned* rfx_count_finish_binned(rfx_table* t, uint64_t lower, uint64_t upper
     rfx_binned* b = new rfx_binned();
     b->ctx = c;
     b->k = t->k;
+    b->canonical = t->canonical;
     b->st = f.bstage;
     b->bin_at = f.bin_at;
     b->bin_lo = f.bin_lo;
@@ -3130,13 +3133,14 @@ rfx_candidates* rfx_binned_strike(rfx_ctx* c, rfx_binned* subject, const rfx_bin
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), 0xFFFFFFFFull);
     uint64_t* keys = (uint64_t*)dmalloc(c, cap * 8);
     uint32_t* bins = (uint32_t*)dmalloc(c, cap * 4);
+    uint32_t* counts = (uint32_t*)dmalloc(c, cap * 4);
     uint32_t* d_n = (uint32_t*)dmalloc(c, 4);
-    auto drop = [&] { dfree(c, keys); dfree(c, bins); dfree(c, d_n); };
-    if (!keys || !bins || !d_n) { drop(); snprintf(g_err, sizeof g_err, "rfx_binned_strike: out of device memory"); return nullptr; }
+    auto drop = [&] { dfree(c, keys); dfree(c, bins); dfree(c, counts); dfree(c, d_n); };
+    if (!keys || !bins || !counts || !d_n) { drop(); snprintf(g_err, sizeof g_err, "rfx_binned_strike: out of device memory"); return nullptr; }
     hipError_t e = hipMemsetAsync(d_n, 0, 4, c->stream);
     uint32_t n = 0;
     if (e == hipSuccess) {
-      rfxk::strike_bins(c, S, C, min_count, max_count, keys, bins, (uint32_t)cap, d_n);
+      rfxk::strike_bins(c, S, C, min_count, max_count, keys, bins, counts, (uint32_t)cap, d_n);
       e = queue_read(c, &n, d_n, 4);
     }
     if (e == hipSuccess) e = ctx_sync(c);
@@ -3145,6 +3149,7 @@ rfx_candidates* rfx_binned_strike(rfx_ctx* c, rfx_binned* subject, const rfx_bin
     if (n > cap) {
       dfree(c, keys);
       dfree(c, bins);
+      dfree(c, counts);
       cap = n;
       continue;
     }
@@ -3154,6 +3159,7 @@ rfx_candidates* rfx_binned_strike(rfx_ctx* c, rfx_binned* subject, const rfx_bin
     r->bits = subject->bits;
     r->keys = keys;
     r->bins = bins;
+    r->counts = counts;
     r->n = n;
     return r;
   }
@@ -3179,11 +3185,131 @@ int rfx_candidates_get(const rfx_candidates* a, uint64_t* keys_out) {
   HIPCHK(hipMemcpy(keys_out, a->keys, (size_t)a->n * 8, hipMemcpyDeviceToHost));
   return RFX_OK;
 }
+int rfx_candidates_get_counts(const rfx_candidates* a, uint32_t* counts_out) {
+  if (!a || (a->n && !counts_out)) return RFX_E_INVAL;
+  if (!a->n) return RFX_OK;
+  (void)hipSetDevice(a->ctx->device);
+  HIPCHK(ctx_sync(a->ctx));
+  HIPCHK(hipMemcpy(counts_out, a->counts, (size_t)a->n * 4, hipMemcpyDeviceToHost));
+  return RFX_OK;
+}
+
+int rfx_candidates_strike_records(rfx_candidates* a, const rfx_records* exclude) {
+  if (!a || !exclude || a->ctx != exclude->ctx) return RFX_E_INVAL;
+  if (a->k != exclude->k) {
+    snprintf(g_err, sizeof g_err, "rfx_candidates_strike_records: the records hold %d-mers, the candidates %d-mers", exclude->k, a->k);
+    return RFX_E_FORMAT;
+  }
+  rfx_ctx* c = a->ctx;
+  (void)hipSetDevice(c->device);
+  rfxk::strike_query(c, a->keys, a->n, exclude->lut, exclude->ntab, exclude->keys, exclude->pos, exclude->n);
+  HIPCHK(ctx_sync(c));  // (the caller may free the records next)
+  return RFX_OK;
+}
+
+// ---- a binned store read where it lies ----
+int rfx_binned_get(const rfx_binned* b, uint64_t* keys_out, uint32_t* counts_out, uint32_t* bins_out, uint64_t* at_out,
+                   uint64_t cap, uint64_t* n_out) {
+  if (!b || !n_out) return RFX_E_INVAL;
+  *n_out = 0;
+  const uint32_t nb = b->bin_hi - b->bin_lo;
+  if (!b->bin_at || !nb) return RFX_OK;
+  rfx_ctx* c = b->ctx;
+  (void)hipSetDevice(c->device);
+  const rfxk::binned_view v = binned_view_of(b);
+  unsigned long long* d_offs = (unsigned long long*)dmalloc(c, ((size_t)nb + 1) * 8);
+  if (!d_offs) return RFX_E_NOMEM;
+  uint64_t n = 0;
+  rfxk::binned_offsets(c, v, d_offs);
+  hipError_t e = queue_read(c, &n, d_offs + nb, 8);
+  if (e == hipSuccess) e = ctx_sync(c);
+  if (e != hipSuccess) { (void)ctx_sync(c); dfree(c, d_offs); return hip_fail(e, "rfx_binned_get"); }
+  *n_out = n;
+  if (n > cap) { dfree(c, d_offs); return RFX_E_RANGE; }
+  if (!n || (!keys_out && !counts_out && !bins_out && !at_out)) { dfree(c, d_offs); return RFX_OK; }
+  uint64_t* dk = keys_out ? (uint64_t*)dmalloc(c, n * 8) : nullptr;
+  uint32_t* dc = counts_out ? (uint32_t*)dmalloc(c, n * 4) : nullptr;
+  uint32_t* db = bins_out ? (uint32_t*)dmalloc(c, n * 4) : nullptr;
+  uint64_t* da = at_out ? (uint64_t*)dmalloc(c, n * 8) : nullptr;
+  int rc = RFX_OK;
+  if ((keys_out && !dk) || (counts_out && !dc) || (bins_out && !db) || (at_out && !da)) rc = RFX_E_NOMEM;
+  if (rc == RFX_OK) {
+    rfxk::binned_gather(c, v, d_offs, n, dk, dc, db, da);
+    if (dk && e == hipSuccess) e = queue_read(c, keys_out, dk, n * 8);
+    if (dc && e == hipSuccess) e = queue_read(c, counts_out, dc, n * 4);
+    if (db && e == hipSuccess) e = queue_read(c, bins_out, db, n * 4);
+    if (da && e == hipSuccess) e = queue_read(c, at_out, da, n * 8);
+    if (e == hipSuccess) e = ctx_sync(c);
+    if (e != hipSuccess) { (void)ctx_sync(c); rc = hip_fail(e, "rfx_binned_get"); }
+  }
+  dfree(c, dk); dfree(c, dc); dfree(c, db); dfree(c, da); dfree(c, d_offs);
+  return rc;
+}
+
+int rfx_binned_checksum(const rfx_binned* b, uint64_t out[2]) {
+  if (!b || !out) return RFX_E_INVAL;
+  out[0] = out[1] = 0;
+  if (!b->st.n_chunks || !b->st.more) return RFX_OK;
+  rfx_ctx* c = b->ctx;
+  (void)hipSetDevice(c->device);
+  unsigned long long* d = (unsigned long long*)dmalloc(c, 2 * 8);
+  if (!d) return RFX_E_NOMEM;
+  hipError_t e = hipMemsetAsync(d, 0, 2 * 8, c->stream);
+  if (e == hipSuccess) {
+    rfxk::binned_checksum(c, b->st, d);
+    e = queue_read(c, out, d, 2 * 8);
+  }
+  if (e == hipSuccess) e = ctx_sync(c);
+  dfree(c, d);
+  return e == hipSuccess ? RFX_OK : hip_fail(e, "rfx_binned_checksum");
+}
+
+int rfx_binned_verify(const rfx_binned* b, uint64_t lower, uint64_t upper, uint64_t out[5]) {
+  if (!b || !out) return RFX_E_INVAL;
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (!b->bin_at || b->bin_hi <= b->bin_lo) return RFX_OK;
+  rfx_ctx* c = b->ctx;
+  (void)hipSetDevice(c->device);
+  unsigned long long* d = (unsigned long long*)dmalloc(c, 5 * 8);
+  if (!d) return RFX_E_NOMEM;
+  hipError_t e = hipMemsetAsync(d, 0, 5 * 8, c->stream);
+  if (e == hipSuccess) {
+    rfxk::binned_verify(c, binned_view_of(b), b->k, b->canonical, lower, upper, d);
+    e = queue_read(c, out, d, 5 * 8);
+  }
+  if (e == hipSuccess) e = ctx_sync(c);
+  dfree(c, d);
+  return e == hipSuccess ? RFX_OK : hip_fail(e, "rfx_binned_verify");
+}
+
+int rfx_binned_query(const rfx_binned* b, const uint64_t* canonical_keys, uint64_t n, uint32_t* counts_out) {
+  if (!b || (n && (!canonical_keys || !counts_out))) return RFX_E_INVAL;
+  if (n == 0) return RFX_OK;
+  if (!b->bin_at) { memset(counts_out, 0, (size_t)n * 4); return RFX_OK; }  // (no read at all: nothing in no bin)
+  rfx_ctx* c = b->ctx;
+  (void)hipSetDevice(c->device);
+  uint64_t* dq = (uint64_t*)dmalloc(c, n * 8);
+  uint32_t* dout = (uint32_t*)dmalloc(c, n * 4);
+  if (!dq || !dout) { dfree(c, dq); dfree(c, dout); return RFX_E_NOMEM; }
+  hipError_t e = upload(c, dq, canonical_keys, n * 8);
+  if (e == hipSuccess) {
+    rfxk::binned_query(c, binned_view_of(b), b->k, b->canonical, dq, n, dout);
+    e = queue_read(c, counts_out, dout, n * 4);
+  }
+  if (e == hipSuccess) e = ctx_sync(c);
+  dfree(c, dq); dfree(c, dout);
+  return e == hipSuccess ? RFX_OK : hip_fail(e, "rfx_binned_query");
+}
+
+const uint64_t* rfx_binned_dev_keys(const rfx_binned* b) { return b ? b->st.keys : nullptr; }
+const uint32_t* rfx_binned_dev_counts(const rfx_binned* b) { return b ? b->st.counts : nullptr; }
+
 void rfx_candidates_free(rfx_candidates* a) {
   if (!a) return;
   (void)hipSetDevice(a->ctx->device);
   dfree(a->ctx, a->keys);
   dfree(a->ctx, a->bins);
+  dfree(a->ctx, a->counts);
   delete a;
 }
 

@@ -77,6 +77,30 @@ __device__ __forceinline__ uint32_t msp_bin(uint32_t minh, int bin_bits) {
   return msp_binhash(minh) >> (32 - bin_bits);  // msp_record_binhash() repeats this from the record
 }
 
+// The bin hash of a k-mer from its key alone (canon: the canonical key of a canonical count): the minimum over the k-mer's
+// own msp_wl(k) m-mers of the upper 27 hash bits -- the position k_msp_part1 folds into the low 5 only breaks ties between
+// hashes whose upper bits are equal already -- spread as msp_binhash spreads it.  msp_key_bin() is the fine minimizer bin
+// the leaf leaves the k-mer in; every reader of an rfx_binned store that needs a key's bin asks here.
+__device__ __forceinline__ uint32_t msp_key_binhash(uint64_t key, int k, bool canon) {
+  const int m = msp_m(k), wl = msp_wl(k);
+  const uint32_t mmask = m >= 16 ? ~0u : (1u << (2 * m)) - 1;
+  uint32_t minh = ~0u;
+  for (int i = 0; i < wl; ++i) {
+    const uint32_t f = (uint32_t)(key >> (2 * i)) & mmask;
+    uint32_t c = f;
+    if (canon) {
+      uint32_t y = __brev(~f);
+      y = ((y & 0xAAAAAAAAu) >> 1) | ((y & 0x55555555u) << 1);
+      c = min(f, y >> (32 - 2 * m));
+    }
+    minh = min(minh, mmer_hash(c) & MSP_HMASK);
+  }
+  return msp_binhash(minh);
+}
+__device__ __forceinline__ uint32_t msp_key_bin(uint64_t key, int k, bool canon, int bin_bits) {
+  return bin_bits > 0 ? msp_key_binhash(key, k, canon) >> (32 - bin_bits) : 0u;
+}
+
 __device__ __forceinline__ uint64_t revcomp_bases(uint64_t s, int nbases) {
   uint64_t y = __brevll(~s);  // complement, then reverse: bit pairs end up swapped inside
   y = ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);

@@ -193,6 +193,13 @@ __device__ __forceinline__ const uint32_t* rv_acgt(const rfx_reads_view& rv, uin
   if (!((bits >> (r & 63u)) & 1ull)) return nullptr;
   return rv.acgt + (size_t)(rv.nrank[r >> 6] + (uint32_t)__popcll(bits & ((1ull << (r & 63u)) - 1ull))) * rv.uwpr;
 }
+// the mix of the record multiset checksums (rfx_records_checksum, rfx_binned_checksum): the splitmix64 finaliser
+__device__ __forceinline__ uint64_t checksum_mix(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
 #endif
 
 inline uint64_t rfx_next_reads_gen() {  // process-wide, never 0
@@ -335,6 +342,9 @@ void compact_scatter(rfx_ctx*, const uint8_t* flags, const uint64_t* keys, const
                      uint64_t n, const uint64_t* block_off, uint64_t* out_keys, uint32_t* out_counts, uint64_t* out_pos);
 void query(rfx_ctx*, const uint64_t* qkeys, uint64_t nq, const uint64_t* lut, int ntab, const uint64_t* keys,
            const uint64_t* pos, const uint32_t* counts, uint64_t n, uint32_t* out);
+// cand[i] = RFX_EMPTY where the (pos,key)-sorted records hold candidate i (k_query's search; struck entries are skipped)
+void strike_query(rfx_ctx*, uint64_t* cand, uint64_t nq, const uint64_t* lut, int ntab, const uint64_t* keys,
+                  const uint64_t* pos, uint64_t n);
 void set_insert(rfx_ctx*, const uint64_t* keys, uint64_t n, uint64_t* slots, int bits);
 void set_bitmap(rfx_ctx*, const uint64_t* keys, uint64_t n, uint32_t* bm, int bm_bits, int bm_shift);
 // k >= 16 and a small set: two 2^16-bit pre-filter bitmaps (last 8 bases, the 8 before) in packed order
@@ -474,12 +484,25 @@ uint32_t msp_leaf_chunk_room(int geo, uint32_t chunk);  // entries a chunk holds
 uint32_t msp_leaf_chunk_kept(uint32_t chunk);           // the chunk size of a pool that is kept, given msp_leaf_plan's
 // count-of-counts of the staged survivors (span k_histo) + their number
 void histo_staged(rfx_ctx*, const msp_stage&, unsigned long long* d_histo, unsigned long long* d_total);
-// candidates of S (lo <= count <= hi) that C (bin_at == null: nobody) does not hold -> (key, bin of S), *out_n counts on
-// beyond cap; S's counts of fallen candidates may be put to 0
+// candidates of S (lo <= count <= hi) that C (bin_at == null: nobody) does not hold -> (key, bin of S, count in S), *out_n
+// counts on beyond cap; S's counts of fallen candidates may be put to 0
 void strike_bins(rfx_ctx*, const binned_view& S, const binned_view& C, uint32_t lo, uint32_t hi, uint64_t* out_k, uint32_t* out_b,
-                 uint32_t cap, uint32_t* out_n);
+                 uint32_t* out_c, uint32_t cap, uint32_t* out_n);
 // keys[i] = RFX_EMPTY where C holds candidate i (of bin bins[i] of 2^bits)
 void strike_cands(rfx_ctx*, uint64_t* keys, const uint32_t* bins, uint32_t n, int bits, const binned_view& C);
+// ---- reading a binned store where it lies (rfx_binned_get / _checksum / _verify / _query) ----
+// sizes[b - bin_lo] = where bin b's survivors begin in bin order, sizes[bin_hi - bin_lo] = their number (nb + 1 words)
+void binned_offsets(rfx_ctx*, const binned_view&, unsigned long long* d_offs);
+// every survivor in bin order: key, count, bin, flat index in the pool (any output may be null); n = d_offs[nb]
+void binned_gather(rfx_ctx*, const binned_view&, const unsigned long long* d_offs, uint64_t n, uint64_t* keys_out,
+                   uint32_t* counts_out, uint32_t* bins_out, uint64_t* at_out);
+// records_checksum over the filled part of every used chunk of the pool
+void binned_checksum(rfx_ctx*, const msp_stage&, unsigned long long* d_out /* 2, zeroed */);
+// d_out (zeroed) += {bad_bin, bad_count, not_canonical, duplicate, sum_counts}: a workgroup per bin
+void binned_verify(rfx_ctx*, const binned_view&, int k, int canonical, uint64_t lower, uint64_t upper,
+                   unsigned long long* d_out);
+// out[i] = the store's count of qkeys[i] (0: not held): a wave per key scans the key's bin
+void binned_query(rfx_ctx*, const binned_view&, int k, int canonical, const uint64_t* qkeys, uint64_t nq, uint32_t* out);
 void msp_leaf_plan(rfx_ctx*, uint32_t P, int geo, uint64_t n_records, uint64_t est_survivors, uint32_t extra, uint32_t* grid,
                    uint32_t* chunk, uint32_t* n_chunks);
 void surv_hist(rfx_ctx*, const uint64_t* buf_a, const uint32_t* coarse_cur, uint32_t cap_a, uint32_t P2, int shift2,

@@ -494,12 +494,7 @@ __global__ __launch_bounds__(256) void k_records_verify(const uint64_t* __restri
 // A checksum of the record MULTISET, independent of how the count was cut into shard passes, devices or slices:
 // out[0] += sum of mix(key) * count, out[1] += sum of mix(key) (mod 2^64; mix = the splitmix64 finaliser).  Two runs hold
 // the same (key, count) pairs iff (with overwhelming probability) both sums agree.
-__device__ __forceinline__ uint64_t checksum_mix(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+// (checksum_mix: rfx_internal.h -- rfx_binned_checksum sums the same terms over a staging pool)
 __global__ __launch_bounds__(256) void k_records_checksum(const uint64_t* __restrict__ keys,
                                                            const uint32_t* __restrict__ counts, uint64_t n,
                                                            unsigned long long* __restrict__ out) {
@@ -793,6 +788,23 @@ __global__ __launch_bounds__(256) void k_query(const uint64_t* __restrict__ qkey
     const uint64_t p = gf2_pos(s_lut, k, ntab);
     const uint64_t lo = lower_bound(keys, pos, n, p, k);
     out[i] = (lo < n && keys[lo] == k) ? counts[lo] : 0u;
+  }
+}
+
+// k_query's search for a list of candidates: the ones the records hold are struck out (RFX_EMPTY), whatever their count
+// there -- the exclude databases of runRufus.sh -e (:738-740, :925), which the executables merge into the set difference
+__global__ __launch_bounds__(256) void k_strike_query(uint64_t* __restrict__ cand, uint64_t nq,
+                                                       const uint64_t* __restrict__ g_lut, int ntab,
+                                                       const uint64_t* __restrict__ keys, const uint64_t* __restrict__ pos,
+                                                       uint64_t n) {
+  __shared__ uint64_t s_lut[8 * 256];
+  load_lut(s_lut, g_lut, ntab);
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t k = cand[i];
+    if (k == RFX_EMPTY) continue;
+    const uint64_t lo = lower_bound(keys, pos, n, gf2_pos(s_lut, k, ntab), k);
+    if (lo < n && keys[lo] == k) cand[i] = RFX_EMPTY;
   }
 }
 
@@ -1890,6 +1902,13 @@ void query(rfx_ctx* c, const uint64_t* qkeys, uint64_t nq, const uint64_t* lut, 
   rfx_span sp(c, "k_query");
   hipLaunchKernelGGL(k_query, dim3(grid_for(c, nq, 256, 8)), dim3(256), 0, c->stream, qkeys, nq, lut, ntab, keys, pos,
                      counts, n, out);
+}
+
+void strike_query(rfx_ctx* c, uint64_t* cand, uint64_t nq, const uint64_t* lut, int ntab, const uint64_t* keys,
+                  const uint64_t* pos, uint64_t n) {
+  if (nq == 0 || n == 0) return;
+  rfx_span sp(c, "k_strike_query");
+  hipLaunchKernelGGL(k_strike_query, dim3(grid_for(c, nq, 256, 8)), dim3(256), 0, c->stream, cand, nq, lut, ntab, keys, pos, n);
 }
 
 void set_insert(rfx_ctx* c, const uint64_t* keys, uint64_t n, uint64_t* slots, int bits) {

@@ -1609,8 +1609,10 @@ __device__ __forceinline__ void binned_range(const rfxk::binned_view& v, uint32_
 }
 
 // survivors of a lane -> the candidate list, one reservation per wave that has any (few have: what a control leaves of a bin)
-__device__ __forceinline__ void cand_append(bool surv, uint64_t key, uint32_t bin, uint64_t* __restrict__ out_k,
-                                            uint32_t* __restrict__ out_b, uint32_t cap, uint32_t* __restrict__ out_n) {
+// (count: the subject's count of the candidate, what the hash list prints beside the k-mer -- runRufus.sh:925-926)
+__device__ __forceinline__ void cand_append(bool surv, uint64_t key, uint32_t bin, uint32_t count, uint64_t* __restrict__ out_k,
+                                            uint32_t* __restrict__ out_b, uint32_t* __restrict__ out_c, uint32_t cap,
+                                            uint32_t* __restrict__ out_n) {
   const unsigned long long m = __ballot(surv);
   if (!m) return;
   const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll(m) - 1u;
@@ -1622,6 +1624,7 @@ __device__ __forceinline__ void cand_append(bool surv, uint64_t key, uint32_t bi
     if (at < cap) {  // (a list that came short: the counter goes on, the host runs the strike again with what it asks for)
       out_k[at] = key;
       out_b[at] = bin;
+      out_c[at] = count;
     }
   }
 }
@@ -1632,13 +1635,14 @@ __device__ __forceinline__ uint32_t sb_hash(uint64_t key) { return (uint32_t)((k
 // Subject S against control C, unit after unit (a unit: a bin of the coarser of the two sides -- bins are prefixes of one
 // hash, so it is 2^d whole bins of the other side); one workgroup per unit.  The control's survivors of the unit go into
 // the set, SB_TILE at a time; every candidate of the subject with lo <= count <= hi that the set does not hold goes to
-// the list as (key, its bin in S).  One tile (the rule: a bin averages a few hundred survivors): one pass over the
+// the list as (key, its bin in S, its count in S).  One tile (the rule: a bin averages a few hundred survivors): one pass over the
 // subject's entries and nothing written back.  Several (a bin that the leaf halved again and again): the lane that owns a
 // candidate puts its count to 0 when the candidate falls, a plain store, and a last pass lists what still has one.
 // C.bin_at == null: no control, the range alone.
 __global__ __launch_bounds__(SB_BLK) void k_strike_bins(const rfxk::binned_view S, const rfxk::binned_view C, int ubits, uint32_t u_lo,
                                                         uint32_t u_hi, uint32_t lo, uint32_t hi, uint64_t* __restrict__ out_k,
-                                                        uint32_t* __restrict__ out_b, uint32_t cap, uint32_t* __restrict__ out_n) {
+                                                        uint32_t* __restrict__ out_b, uint32_t* __restrict__ out_c, uint32_t cap,
+                                                        uint32_t* __restrict__ out_n) {
   __shared__ unsigned long long s_set[SB_SET];
   const int ds = S.bits - ubits, dc = C.bin_at ? C.bits - ubits : 0;
   for (uint32_t u = u_lo + blockIdx.x; u < u_hi; u += gridDim.x) {
@@ -1698,7 +1702,7 @@ __global__ __launch_bounds__(SB_BLK) void k_strike_bins(const rfxk::binned_view 
                 if (!single) S.counts[first + i] = 0;
               }
             }
-            if (single) cand_append(c != 0, key, b, out_k, out_b, cap, out_n);
+            if (single) cand_append(c != 0, key, b, c, out_k, out_b, out_c, cap, out_n);
           }
         });
       __syncthreads();  // (the set is cleared for the next tile / unit)
@@ -1707,8 +1711,8 @@ __global__ __launch_bounds__(SB_BLK) void k_strike_bins(const rfxk::binned_view 
       binned_range(S, s0, s1, ms, [&](uint32_t b, size_t first, uint32_t o, uint32_t e) {
           for (uint32_t i0 = o; i0 < e; i0 += SB_BLK) {
             const uint32_t i = i0 + threadIdx.x;
-            const bool live = i < e && S.counts[first + i] != 0;
-            cand_append(live, live ? S.keys[first + i] : 0ull, b, out_k, out_b, cap, out_n);
+            const uint32_t c = i < e ? S.counts[first + i] : 0u;
+            cand_append(c != 0, c ? S.keys[first + i] : 0ull, b, c, out_k, out_b, out_c, cap, out_n);
           }
         });
   }
@@ -1765,6 +1769,189 @@ __global__ __launch_bounds__(256) void k_histo_staged(const uint32_t* __restrict
   for (int b = threadIdx.x; b < RFX_HISTO_BINS; b += 256)
     if (s_h[b]) atomicAdd(&g_histo[b], (unsigned long long)s_h[b]);
   if (threadIdx.x == 0 && total) atomicAdd(g_total, total);
+}
+
+
+// ---- reading a binned store where it lies ---------------------------------------------------------------------------
+// None of these writes the store, and every walk is binned_segments': at most n_chunks + 1 hops, offsets clamped to the
+// chunk size -- whatever the keys, counts and marks hold, no access leaves the pool and every loop ends.
+
+// survivors of every bin (rfx_binned_get, step 1)
+__global__ __launch_bounds__(256) void k_binned_sizes(const rfxk::binned_view v, unsigned long long* __restrict__ sizes) {
+  const uint32_t nb = v.bin_hi - v.bin_lo;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nb; i += (uint64_t)gridDim.x * 256u) {
+    unsigned long long n = 0;
+    binned_segments(v, v.bin_lo + (uint32_t)i, [&](size_t, uint32_t o, uint32_t e) { n += e - o; });
+    sizes[i] = n;
+  }
+}
+
+// a[0 .. nb) -> its exclusive prefix sums, a[nb] = the total; one workgroup (a read-out, not a hot path)
+constexpr int BSC_BLK = 1024;
+__global__ __launch_bounds__(BSC_BLK) void k_binned_scan(unsigned long long* __restrict__ a, uint32_t nb) {
+  __shared__ unsigned long long s_sum[BSC_BLK];
+  const uint64_t per = ((uint64_t)nb + BSC_BLK - 1) / BSC_BLK;
+  const uint64_t lo = min((uint64_t)threadIdx.x * per, (uint64_t)nb), hi = min(lo + per, (uint64_t)nb);
+  unsigned long long sum = 0;
+  for (uint64_t i = lo; i < hi; ++i) sum += a[i];
+  s_sum[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long run = 0;
+    for (int i = 0; i < BSC_BLK; ++i) {
+      const unsigned long long t = s_sum[i];
+      s_sum[i] = run;
+      run += t;
+    }
+    a[nb] = run;
+  }
+  __syncthreads();
+  unsigned long long run = s_sum[threadIdx.x];
+  for (uint64_t i = lo; i < hi; ++i) {
+    const unsigned long long t = a[i];
+    a[i] = run;
+    run += t;
+  }
+}
+
+// a workgroup per bin copies the bin's stretches to where the bin begins in bin order (rfx_binned_get, step 2)
+__global__ __launch_bounds__(256) void k_binned_gather(const rfxk::binned_view v, const unsigned long long* __restrict__ offs,
+                                                        unsigned long long n_total, uint64_t* __restrict__ keys_out,
+                                                        uint32_t* __restrict__ counts_out, uint32_t* __restrict__ bins_out,
+                                                        uint64_t* __restrict__ at_out) {
+  const uint32_t nb = v.bin_hi - v.bin_lo;
+  for (uint32_t bi = blockIdx.x; bi < nb; bi += gridDim.x) {
+    unsigned long long d0 = offs[bi];
+    binned_segments(v, v.bin_lo + bi, [&](size_t first, uint32_t o, uint32_t e) {
+      for (uint32_t j = o + threadIdx.x; j < e; j += 256u) {
+        const unsigned long long d = d0 + (j - o);
+        if (d >= n_total) continue;  // (cannot be: the offsets were made from this very walk)
+        if (keys_out) keys_out[d] = v.keys[first + j];
+        if (counts_out) counts_out[d] = v.counts[first + j];
+        if (bins_out) bins_out[d] = v.bin_lo + bi;
+        if (at_out) at_out[d] = first + j;
+      }
+      d0 += e - o;
+    });
+  }
+}
+
+// k_records_checksum over the filled part of every used chunk, as k_histo_staged streams them
+__global__ __launch_bounds__(256) void k_binned_checksum(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ counts,
+                                                          const uint32_t* __restrict__ fill, const uint32_t* __restrict__ more,
+                                                          uint32_t CH, uint32_t n_chunks, unsigned long long* __restrict__ out) {
+  const uint32_t n_used = min(*more, n_chunks);
+  unsigned long long a = 0, b = 0;
+  for (uint32_t ch = blockIdx.x; ch < n_used; ch += gridDim.x) {
+    const uint32_t n = min(fill[ch], CH);
+    const size_t first = (size_t)ch * CH;
+    for (uint32_t i = threadIdx.x; i < n; i += 256u) {
+      const uint64_t m = checksum_mix(keys[first + i]);
+      a += m * counts[first + i];
+      b += m;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    a += __shfl_xor(a, o);
+    b += __shfl_xor(b, o);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    atomicAdd(&out[0], a);
+    atomicAdd(&out[1], b);
+  }
+}
+
+// What the strike relies on, checked where the survivors lie: every key canonical, lower <= count <= upper, in the bin its
+// own minimizer names (msp_key_bin), and there once.  A workgroup per bin.  "Once": the bin's survivors go into the LDS
+// set SB_TILE at a time -- an insert that meets its own key is a duplicate -- and, when the bin has more than one tile, the
+// survivors behind the tile are streamed against it (tile against stream, as k_strike_bins takes a large control bin).
+constexpr int BV_BLK = 256;
+__global__ __launch_bounds__(BV_BLK) void k_binned_verify(const rfxk::binned_view v, int k, int canon, unsigned long long lower,
+                                                           unsigned long long upper, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_set[SB_SET];
+  constexpr uint32_t mask = SB_SET - 1u;
+  const uint32_t nb = v.bin_hi - v.bin_lo;
+  const uint64_t kmask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
+  unsigned long long acc[5] = {0, 0, 0, 0, 0};  // bad_bin, bad_count, not_canonical, duplicate, sum_counts
+  for (uint32_t bi = blockIdx.x; bi < nb; bi += gridDim.x) {
+    const uint32_t b = v.bin_lo + bi;
+    const uint4 mk = binned_marks(v, b);
+    uint64_t n_s = 0;
+    binned_segments(v, mk, [&](size_t, uint32_t o, uint32_t e) { n_s += e - o; });
+    if (!n_s) continue;
+    const uint64_t tiles = (n_s + SB_TILE - 1) / SB_TILE;
+    for (uint64_t t = 0; t < tiles; ++t) {
+      const uint64_t t0 = t * SB_TILE, t1 = min(t0 + (uint64_t)SB_TILE, n_s);
+      for (uint32_t i = threadIdx.x; i < (uint32_t)SB_SET; i += BV_BLK) s_set[i] = RFX_EMPTY;
+      __syncthreads();
+      uint64_t idx0 = 0;  // entries of the bin before this stretch
+      binned_segments(v, mk, [&](size_t first, uint32_t o, uint32_t e) {
+        const uint64_t from = max(idx0, t0), to = min(idx0 + (e - o), t1);
+        for (uint64_t i = from + threadIdx.x; i < to; i += BV_BLK) {
+          const size_t at = first + o + (size_t)(i - idx0);
+          const uint64_t key = v.keys[at];
+          const uint32_t c = v.counts[at];
+          acc[4] += c;
+          acc[1] += (c < lower || c > upper) ? 1u : 0u;
+          acc[2] += ((key & ~kmask) != 0 || (canon && revcomp_bases(key & kmask, k) < key)) ? 1u : 0u;
+          acc[0] += msp_key_bin(key, k, canon != 0, v.bits) != b ? 1u : 0u;
+          uint32_t h = sb_hash(key) & mask;
+          for (;;) {  // (<= SB_TILE keys in SB_SET slots: an empty slot is always met)
+            const unsigned long long old = atomicCAS(&s_set[h], (unsigned long long)RFX_EMPTY, (unsigned long long)key);
+            if (old == key) ++acc[3];
+            if (old == RFX_EMPTY || old == key) break;
+            h = (h + 1u) & mask;
+          }
+        }
+        idx0 += e - o;
+      });
+      __syncthreads();
+      if (t + 1 < tiles) {
+        idx0 = 0;
+        binned_segments(v, mk, [&](size_t first, uint32_t o, uint32_t e) {
+          const uint64_t from = max(idx0, t1), to = idx0 + (e - o);
+          for (uint64_t i = from + threadIdx.x; i < to; i += BV_BLK) {
+            const uint64_t key = v.keys[first + o + (size_t)(i - idx0)];
+            uint32_t h = sb_hash(key) & mask;
+            for (;;) {
+              const unsigned long long s = s_set[h];
+              if (s == key) ++acc[3];
+              if (s == key || s == RFX_EMPTY) break;
+              h = (h + 1u) & mask;
+            }
+          }
+          idx0 += e - o;
+        });
+      }
+      __syncthreads();  // (the set is cleared for the next tile / bin)
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    unsigned long long x = acc[q];
+    for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o);
+    if ((threadIdx.x & 63u) == 0 && x) atomicAdd(&out[q], x);
+  }
+}
+
+// A wave per key, as k_strike_cands: the key's bin from the key, then the bin's survivors 64 at a time.
+__global__ __launch_bounds__(256) void k_binned_query(const rfxk::binned_view v, int k, int canon,
+                                                       const uint64_t* __restrict__ qkeys, uint64_t nq,
+                                                       uint32_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4u;
+  for (uint64_t i = wave; i < nq; i += n_waves) {
+    const uint64_t key = qkeys[i];
+    const uint32_t b = msp_key_bin(key, k, canon != 0, v.bits);
+    uint32_t c = 0;
+    binned_segments(v, b, [&](size_t first, uint32_t o, uint32_t e) {
+      for (uint32_t j = o + lane; j < e; j += 64u)
+        if (v.keys[first + j] == key) c = max(c, v.counts[first + j]);
+    });
+    for (int o = 32; o; o >>= 1) c = max(c, (uint32_t)__shfl_xor((int)c, o));
+    if (lane == 0) out[i] = c;
+  }
 }
 
 }  // namespace
@@ -1906,15 +2093,15 @@ void histo_staged(rfx_ctx* c, const msp_stage& st, unsigned long long* d_histo, 
 }
 
 void strike_bins(rfx_ctx* c, const binned_view& S, const binned_view& C, uint32_t lo, uint32_t hi, uint64_t* out_k,
-                 uint32_t* out_b, uint32_t cap, uint32_t* out_n) {
+                 uint32_t* out_b, uint32_t* out_c, uint32_t cap, uint32_t* out_n) {
   rfx_span sp(c, "k_strike_bins");
   const int ubits = C.bin_at ? std::min(S.bits, C.bits) : S.bits;
   const int ds = S.bits - ubits;
   const uint32_t u_lo = S.bin_lo >> ds, u_hi = (uint32_t)((((uint64_t)S.bin_hi + (1u << ds) - 1)) >> ds);
   if (u_hi <= u_lo) return;
   const uint32_t grid = std::min<uint32_t>(u_hi - u_lo, (uint32_t)c->n_cu * 10);  // 16 KB of LDS: ten workgroups of two waves per CU
-  hipLaunchKernelGGL(k_strike_bins, dim3(grid), dim3(SB_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, out_k, out_b, cap,
-                     out_n);
+  hipLaunchKernelGGL(k_strike_bins, dim3(grid), dim3(SB_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, out_k, out_b, out_c,
+                     cap, out_n);
 }
 
 void strike_cands(rfx_ctx* c, uint64_t* keys, const uint32_t* bins, uint32_t n, int bits, const binned_view& C) {
@@ -1922,6 +2109,51 @@ void strike_cands(rfx_ctx* c, uint64_t* keys, const uint32_t* bins, uint32_t n, 
   rfx_span sp(c, "k_strike_cands");
   const uint32_t grid = std::min<uint32_t>((n + 3) / 4, (uint32_t)c->n_cu * 8);
   hipLaunchKernelGGL(k_strike_cands, dim3(grid), dim3(256), 0, c->stream, keys, bins, n, bits, C);
+}
+
+void binned_offsets(rfx_ctx* c, const binned_view& v, unsigned long long* d_offs) {
+  rfx_span sp(c, "k_binned_get");
+  const uint32_t nb = v.bin_hi - v.bin_lo;
+  if (nb) {
+    const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((nb + 255u) / 256u, (uint32_t)c->n_cu * 8));
+    hipLaunchKernelGGL(k_binned_sizes, dim3(grid), dim3(256), 0, c->stream, v, d_offs);
+  }
+  hipLaunchKernelGGL(k_binned_scan, dim3(1), dim3(BSC_BLK), 0, c->stream, d_offs, nb);
+}
+
+void binned_gather(rfx_ctx* c, const binned_view& v, const unsigned long long* d_offs, uint64_t n, uint64_t* keys_out,
+                   uint32_t* counts_out, uint32_t* bins_out, uint64_t* at_out) {
+  const uint32_t nb = v.bin_hi - v.bin_lo;
+  if (!nb || !n) return;
+  rfx_span sp(c, "k_binned_get");
+  const uint32_t grid = std::min<uint32_t>(nb, (uint32_t)c->n_cu * 8);
+  hipLaunchKernelGGL(k_binned_gather, dim3(grid), dim3(256), 0, c->stream, v, d_offs, (unsigned long long)n, keys_out, counts_out,
+                     bins_out, at_out);
+}
+
+void binned_checksum(rfx_ctx* c, const msp_stage& st, unsigned long long* d_out) {
+  if (!st.n_chunks) return;
+  rfx_span sp(c, "k_binned_checksum");
+  const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(st.n_chunks, (uint32_t)c->n_cu * 4));
+  hipLaunchKernelGGL(k_binned_checksum, dim3(grid), dim3(256), 0, c->stream, st.keys, st.counts, st.fill, st.more, st.chunk,
+                     st.n_chunks, d_out);
+}
+
+void binned_verify(rfx_ctx* c, const binned_view& v, int k, int canonical, uint64_t lower, uint64_t upper,
+                   unsigned long long* d_out) {
+  const uint32_t nb = v.bin_hi - v.bin_lo;
+  if (!nb) return;
+  rfx_span sp(c, "k_binned_verify");
+  const uint32_t grid = std::min<uint32_t>(nb, (uint32_t)c->n_cu * 8);  // 16 KB of LDS, four waves
+  hipLaunchKernelGGL(k_binned_verify, dim3(grid), dim3(BV_BLK), 0, c->stream, v, k, canonical, (unsigned long long)lower,
+                     (unsigned long long)upper, d_out);
+}
+
+void binned_query(rfx_ctx* c, const binned_view& v, int k, int canonical, const uint64_t* qkeys, uint64_t nq, uint32_t* out) {
+  if (!nq) return;
+  rfx_span sp(c, "k_binned_query");
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((nq + 3) / 4, (uint64_t)c->n_cu * 8);
+  hipLaunchKernelGGL(k_binned_query, dim3(grid), dim3(256), 0, c->stream, v, k, canonical, qkeys, nq, out);
 }
 
 void surv_hist(rfx_ctx* c, const uint64_t* buf_a, const uint32_t* coarse_cur, uint32_t cap_a, uint32_t P2, int shift2,

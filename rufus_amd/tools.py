@@ -235,6 +235,16 @@ def hash_list(ctx: capi.Context, subject: JhashFile, others, min_cov: int, max_c
     return "".join(f"{t} {int(c)}\n" for t, c in zip(keys_to_text(keys, subject.k), counts))
 
 
+def hash_list_of_run(res: dict, k: int) -> str:
+    """The ``kmer count`` text (runRufus.sh:925-926, the .HashList file) of a wgs.WgsTrio.run() result: its mutant_keys
+    and mutant_counts, line for line as hash_list() writes them."""
+    keys = np.asarray(res["mutant_keys"], dtype=np.uint64)
+    counts = np.asarray(res["mutant_counts"])
+    if keys.ndim != 1 or keys.shape != counts.shape:
+        raise ValueError("hash_list_of_run: mutant_keys and mutant_counts of one length")
+    return "".join(f"{t} {int(c)}\n" for t, c in zip(keys_to_text(keys, k), counts))
+
+
 # ---------------------------------------------------------------------------------------------------
 # RUFUS.Filter
 # ---------------------------------------------------------------------------------------------------

@@ -482,8 +482,10 @@ class WgsTrio:
         """What run() does with one sample's records of one pass (verify, candidates / strike-out); returns cand."""
         if verify:
             v = rec.verify(self.lower)
-            for k_ in ("bad_order", "bad_pos", "bad_count"):
-                ver[k_] += v[k_]
+            # (a Binned store reports bad_bin / duplicate / not_canonical where sorted records report bad_order / bad_pos)
+            for k_ in v:
+                if k_ != "sum_counts":
+                    ver[k_] += v[k_]
             ver["sum_counts"][si] += v["sum_counts"]
             ver["checksum"][si] = [(a + b) % (1 << 64) for a, b in zip(ver["checksum"][si], rec.checksum())]
             if probe_keys is not None and len(probe_keys):
@@ -541,12 +543,22 @@ class WgsTrio:
             pos ^= np.where((keys >> np.uint64(b)) & np.uint64(1), self.cols[c - 1 - b], np.uint64(0))
         return pos & np.uint64((1 << self.lsize) - 1) if self.lsize < 64 else pos
 
-    def run(self, samples, keep_shard_records: bool = False, verify: bool = False, probe_keys=None):
+    def run(self, samples, keep_shard_records: bool = False, verify=False, probe_keys=None, exclude=()):
         """samples: [subject blocks, control blocks, ...] (lists of capi.ReadBlock).
+
+        out["mutant_keys"] / out["mutant_counts"]: the hash list in (pos, key) order, `kmer` and the subject's `count`
+        (runRufus.sh:925-926).  exclude: capi.Records (a count's, or a .Jhash loaded with Records.load / load_fd) whose
+        k-mers are struck off after the controls -- runRufus.sh -e.
 
         verify: every shard's records are checked where they lie before they are freed (rfx_records_verify: strict
         (pos,key) order, pos == M * key, lower <= count) -> out["verify"]; probe_keys (canonical keys, e.g. the hash
-        list of an earlier run): out["verify"]["probe_found"][sample] = how many of them each sample holds."""
+        list of an earlier run): out["verify"]["probe_found"][sample] = how many of them each sample holds.
+        verify=True sorts every shard's records for that; verify="binned" stays on the binned route and checks every store
+        where it lies (capi.Binned.verify / checksum / query): the same dictionary, bad_order and bad_pos 0, and bad_bin,
+        duplicate, not_canonical beside them."""
+        if verify == "binned" and (not self._local() or keep_shard_records):
+            raise ValueError('verify="binned": one device, no kept shard records')
+        exclude = list(exclude)
         trace = os.environ.get("RFX_WGS_TRACE")
         t_last = time.perf_counter()
 
@@ -561,7 +573,7 @@ class WgsTrio:
         while True:
             histos = [np.zeros(capi.HISTO_BINS, dtype=np.uint64) for _ in samples]
             n_rec = [0] * len(samples)
-            keys, kept, recs = [], [], []
+            keys, kcounts, kept, recs = [], [], [], []
             cand, cands, shard_recs = None, {}, {}
             self._drop_early()
             self._early_left = int(self.early_budget) if self.world == 1 and not keep_shard_records else 0
@@ -570,7 +582,8 @@ class WgsTrio:
             # needs the (pos,key) order of jellyfish's file: the survivors stay grouped by minimizer bin (capi.Binned) and
             # the controls are struck off bin against bin.  Verified or kept records, a group of ranks: sorted records, as
             # ever; RFX_TRIO_SORTED=1 forces them (A/B, bisecting).
-            binned = self._local() and not verify and not keep_shard_records and not os.environ.get("RFX_TRIO_SORTED")
+            binned = verify == "binned" or (self._local() and not verify and not keep_shard_records and
+                                            not os.environ.get("RFX_TRIO_SORTED"))
             self.exchange_sent = self.exchange_received = 0
             use_maps = self.map_budget > 0 and self.world == 1 and self.passes > 1 and not keep_shard_records
             if not use_maps:
@@ -583,6 +596,8 @@ class WgsTrio:
             ver = {"bad_order": 0, "bad_pos": 0, "bad_count": 0, "sum_counts": [0] * len(samples),
                    "probe_found": [0] * len(samples), "probe_count_out_of_range": 0,
                    "checksum": [[0, 0] for _ in samples]}   # rfx_records_checksum, summed over the shards
+            if verify == "binned":
+                ver.update(bad_bin=0, duplicate=0, not_canonical=0)
             try:
                 # The subject (sample 0) is counted first and only its CANDIDATES stay: the records with MinCov <=
                 # count <= MaxDepth; every control then strikes out what it holds and is freed at once
@@ -642,7 +657,7 @@ class WgsTrio:
                         cand = None
                         continue
                     if keep_shard_records:
-                        k_, _ = capi.unique_to_subject(self.ctx, recs[0], recs[1:], self.min_cov, self.max_cov)
+                        k_, c_ = capi.unique_to_subject(self.ctx, recs[0], recs[1:] + exclude, self.min_cov, self.max_cov)
                         kept.append(recs)
                     else:
                         if getattr(self, "_cand_raw", False):      # a subject without controls: the range alone
@@ -651,11 +666,21 @@ class WgsTrio:
                             cand.free()
                             cand = nxt
                             self._cand_raw = False
-                        k_ = cand.keys() if binned else cand.get()[0]
+                        if binned:
+                            for ex in exclude:
+                                cand.strike_records(ex)
+                            k_, c_ = cand.keys_counts()
+                        else:
+                            if exclude:
+                                nxt = capi.records_subtract(self.ctx, cand, exclude)
+                                cand.free()
+                                cand = nxt
+                            k_, c_ = cand.get()[:2]
                         cand.free()
                         cand = None
                     lap(f"pass {sh} set difference ({len(k_)} k-mers)")
                     keys.append(k_)
+                    kcounts.append(c_)
                     shard_recs[sh] = []
                     recs = []
                 break
@@ -688,11 +713,13 @@ class WgsTrio:
                 if trace:
                     print(f"[wgs] out of device memory: retrying with {self.passes} passes", flush=True)
         keys = np.concatenate(keys) if keys else np.zeros(0, np.uint64)
+        kcounts = np.concatenate(kcounts).astype(np.uint32) if kcounts else np.zeros(0, np.uint32)
         if self.world > 1:     # every rank needs the whole hash list; histograms and record counts add up
             import torch
             import torch.distributed as dist
             from .dist import all_gather_keys, _wire
             dev = torch.device("cuda", torch.cuda.current_device())
+            kcounts = all_gather_keys(kcounts.astype(np.uint64), dev, self.group).astype(np.uint32)   # (rank by rank, as the keys)
             keys = all_gather_keys(keys, dev, self.group)
             h = _wire(torch.from_numpy(np.stack(histos).astype(np.int64)).to(dev), self.group)
             dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
@@ -701,7 +728,8 @@ class WgsTrio:
             dist.all_reduce(nr, op=dist.ReduceOp.SUM, group=self.group)
             n_rec = nr.tolist()
         if len(keys):
-            keys = keys[np.lexsort((keys, self.pos_of(keys)))]
+            order = np.lexsort((keys, self.pos_of(keys)))
+            keys, kcounts = keys[order], kcounts[order]
         lap("hash list order")
         n_pulled = 0
         masks = []
@@ -722,7 +750,7 @@ class WgsTrio:
             t_ = _wire(torch.tensor([n_pulled], dtype=torch.int64, device=dev), self.group)
             dist.all_reduce(t_, op=dist.ReduceOp.SUM, group=self.group)
             n_pulled = int(t_.item())
-        out = {"n_mutant": len(keys), "n_pulled_local": n_pulled_local, "mutant_keys": keys, "n_pulled": n_pulled, "n_records": n_rec, "histos": histos,
+        out = {"n_mutant": len(keys), "n_pulled_local": n_pulled_local, "mutant_keys": keys, "mutant_counts": kcounts, "n_pulled": n_pulled, "n_records": n_rec, "histos": histos,
                "hit_masks": masks}
         if keep_shard_records:
             out["shard_records"] = kept
@@ -846,6 +874,68 @@ def self_check(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, 
         out["sampled_block_windows"] = want
     return out
 
+
+
+def self_check_binned(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, more_passes: bool = True) -> dict:
+    """Steps 1-3 of self_check() on the route a plain run() takes: every shard's store is checked where the count left it
+    (verify="binned": capi.Binned.verify / checksum / query) instead of being sorted first.  Raises AssertionError; returns
+    a summary.
+
+    1. a second run with every store verified on the device: every survivor canonical, count >= lower, in the bin its own
+       minimizer names and there once; the sum of the counts equals sum(i * histo[i]); the same record counts, histograms,
+       hash list (k-mers and counts) and pulled pairs as `res`;
+    2. the mutant k-mers: each is held by the subject with MinCov <= count <= MaxDepth and by NO control, and they are the
+       alt-allele k-mers of the planted SNVs (a handful of recurrent sequencing errors aside);
+    3. one more shard pass (S + 1) gives the same -- and the same multiset of (key, count) records."""
+    k = trio.k
+    out = {}
+    keys0 = np.asarray(res["mutant_keys"], dtype=np.uint64)
+    rv = trio.run(samples, verify="binned", probe_keys=keys0)
+    assert trio.binned_counts == trio.passes * len(samples), "the binned route was left"
+    v = rv["verify"]
+    assert all(v[x] == 0 for x in ("bad_order", "bad_pos", "bad_count", "bad_bin", "duplicate", "not_canonical")), \
+        f"stores fail their invariants: {v}"
+    assert rv["n_records"] == res["n_records"] and rv["n_pulled"] == res["n_pulled"]
+    assert np.array_equal(rv["mutant_keys"], keys0)
+    if "mutant_counts" in res:
+        assert np.array_equal(rv["mutant_counts"], res["mutant_counts"])
+    for si, h in enumerate(rv["histos"]):
+        assert np.array_equal(h, res["histos"][si])
+        assert int(h[-1]) != 0 or int(sum(int(x) * i for i, x in enumerate(h))) == v["sum_counts"][si], "histogram != records"
+        assert int(h.sum()) == rv["n_records"][si]
+    assert v["probe_found"][0] == len(keys0) and v["probe_count_out_of_range"] == 0, "a mutant k-mer is not the subject's"
+    assert all(x == 0 for x in v["probe_found"][1:]), "a mutant k-mer occurs in a control"
+    out.update(records_verified=int(sum(rv["n_records"])), bin_count_canonical_duplicate_violations=0,
+               mutant_in_subject=int(v["probe_found"][0]), mutant_in_controls=int(sum(v["probe_found"][1:])))
+    from .tools import keys_to_text
+    if sys_[0].n_snv and len(samples) > 1:
+        expect = expected_snv_kmers(sys_[0], k)
+        got = set(x.encode() for x in keys_to_text(keys0, k))
+        assert len(got) == len(keys0)
+        extra = got - expect
+        out.update(snv_kmers_expected=len(expect), snv_kmers_found=len(got & expect), not_snv_kmers=len(extra))
+        import math     # (the allowance of self_check: recurrent errors at G * 3 * C(c, 5) * (e / 3)^5 sites)
+        cov = max(5, int(round(n_pairs * 2 * sys_[0].read_len / sys_[0].genome_len)))
+        e3 = sys_[0].err_1024 / 1024.0 / 3.0
+        sites = sys_[0].genome_len * 3.0 * math.comb(cov, 5) * e3 ** 5
+        out["not_snv_kmers_allowed"] = int(k * (3 * sites + 30))
+        assert len(extra) <= out["not_snv_kmers_allowed"], f"{len(extra)} mutant k-mers are no SNV k-mers"
+        if n_pairs * 300 >= 20 * sys_[0].genome_len:
+            assert len(got & expect) >= 0.9 * len(expect), f"only {len(got & expect)} of {len(expect)} SNV k-mers found"
+    if more_passes:
+        t2 = WgsTrio(ctx, k, trio.size, trio.lower, trio.min_cov, trio.max_cov, trio.thresh, passes=trio.passes + 1)
+        try:
+            r2 = t2.run(samples, verify="binned")
+            assert t2.binned_counts == t2.passes * len(samples), "the binned route was left"
+        finally:
+            t2.close()
+        assert r2["n_records"] == res["n_records"] and r2["n_pulled"] == res["n_pulled"]
+        assert np.array_equal(r2["mutant_keys"], keys0)
+        assert all(np.array_equal(a, b) for a, b in zip(r2["histos"], res["histos"]))
+        assert r2["verify"]["checksum"] == v["checksum"], "S and S + 1 shard passes do not hold the same records"
+        out["passes_compared"] = [trio.passes, t2.passes]
+        out["multiset_checksums"] = ["%016x" % c[0] for c in v["checksum"]]
+    return out
 
 
 def make_sample(ctx: capi.Context, sy: capi.Synth, n_pairs: int, block_pairs: int = 1 << 24, min_q: int = 15,
