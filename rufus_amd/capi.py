@@ -326,10 +326,10 @@ class Context:
 
     def close(self):
         if self._h:
-            if getattr(self, "_pin_ptr", None):
-                self._pin_arr = None
-                lib().rfx_host_free(self._pin_ptr)
-                self._pin_ptr = None
+            self._pin_arr = None
+            for p in getattr(self, "_pin_ptrs", ()):     # (every buffer pinned_u64() ever handed out)
+                lib().rfx_host_free(p)
+            self._pin_ptrs = []
             lib().rfx_close(self._h)
             self._h = None
 
@@ -378,17 +378,16 @@ class Context:
         return ReadBlock.from_handle(self, h)
 
     def pinned_u64(self, n_words: int) -> np.ndarray:
-        """A page-locked uint64 array of at least n_words (rfx_host_alloc), kept by the ctx and reused by the next call."""
+        """A page-locked uint64 array of at least n_words (rfx_host_alloc), kept by the ctx and reused by the next call.
+        When it has to grow, the buffer before stays allocated until close(): callers hold views of it (WgsTrio.run()'s
+        hit masks with masks_are_views)."""
         have = getattr(self, "_pin_arr", None)
         if have is None or len(have) < n_words:
-            old_p = getattr(self, "_pin_ptr", None)
             p = lib().rfx_host_alloc(max(n_words, 1) * 8)
             if not p:
                 raise RufusError("rfx_host_alloc failed")
-            self._pin_ptr = p
+            self._pin_ptrs = getattr(self, "_pin_ptrs", []) + [p]
             self._pin_arr = np.ctypeslib.as_array((C.c_uint64 * max(n_words, 1)).from_address(p))
-            if old_p:
-                lib().rfx_host_free(old_p)
         return self._pin_arr[:max(n_words, 1)]
 
     def __enter__(self):

@@ -8,8 +8,14 @@ is refined chunk by chunk at finish), takes the set difference on the shard (the
 same in every sample), adds up the histograms and frees the shard's records.  The mutant k-mers of all
 shards, put back into (pos,key) order, are the hash list; the subject's blocks are then filtered.
 
+Two routes.  A plain run needs of every count the histogram, the number of records and the set difference -- none of
+which needs the (pos,key) order of jellyfish's file: the survivors stay grouped by minimizer bin (capi.Binned) and the
+controls are struck off bin against bin.  Verified or kept records, a group of ranks: sorted records (capi.Records), as
+ever; RFX_TRIO_SORTED=1 forces them (A/B, bisecting).  The run loop sees neither: the subject's store of a pass becomes a
+_BinnedCandidates or a _SortedCandidates, which have one interface (strike, finish, raw_bytes, free).
+
 Everything that computes is a C-ABI call into the HIP library; this module only sequences them (the same
-sequence the drop-in executables run per sample).
+sequence the drop-in executables run per sample; tests/test_wgs_driver_host.py pins it).
 """
 from __future__ import annotations
 
@@ -112,6 +118,125 @@ def plan_passes(n_reads_total: int, read_len: int, k: int, resident_bytes: int, 
     return max(1, 256 // world)
 
 
+def plan_steps(passes: int, n_samples: int, use_maps: bool, keep_shard_records: bool) -> list:
+    """Order of the (pass, sample) steps of a run.  The subject (sample 0) is counted first and only its CANDIDATES stay;
+    every control then strikes out what it holds and is freed at once: one sample's records alive at a time.
+    Plain: pass by pass (odd passes take the controls in reverse: the control counted last in one pass -- whose records of
+    the next pass may have been cut ahead in the room the subject's records left, see WgsTrio._attempt -- is the first
+    control of the next; kept shard records stay in the samples' order).  With run maps: subject and first control pass by
+    pass, then every further control through all its passes at once -- the candidates a shard has left after the first control
+    are few, so they can wait, and never more than two samples' maps are alive (the pool is sized for that: bench.py)."""
+    P, ns = passes, n_samples
+    if use_maps and ns > 2:
+        return [(sh, si) for sh in range(P) for si in (0, 1)] + [(sh, si) for si in range(2, ns) for sh in range(P)]
+    return [(sh, si) for sh in range(P)
+            for si in (list(range(ns)) if sh % 2 == 0 or keep_shard_records else [0] + list(range(ns - 1, 0, -1)))]
+
+
+def plan_maps_ahead(steps) -> dict:
+    """Maps made ahead, {step: sample}: the step before a sample's FIRST step queues that sample's maps -- if the store has
+    room for them then (two samples' maps fit: the step must come after the last step of the sample before the previous
+    one, whose maps go with its last pass).
+    (opt-in, RFX_MAP_AHEAD=1: measured at W it buys nothing -- 1943 against 1941 ms per step --: the hashing launch holds
+    414 of a SIMD's 512 registers, the replay and partition workgroups of the first stream do not fit beside it, and the
+    two streams take turns instead of sharing the CUs)"""
+    first, last_of = {}, {}
+    for i, (_, si) in enumerate(steps):
+        first.setdefault(si, i)
+        last_of[si] = i
+    order = sorted(first, key=first.get)
+    ahead = {}
+    for n, si in enumerate(order[1:], 1):
+        at = first[si] - 1                          # the step that queues them
+        if n >= 2 and at <= last_of[order[n - 2]]:
+            continue                                # (three samples' maps would be alive)
+        ahead[steps[at]] = si
+    return ahead
+
+
+class _BinnedCandidates:
+    """The subject's candidates of one pass.  They start raw: the subject's store as its count left it (now this object's),
+    the count range min_count .. max_count yet to be applied.  strike(control's store; it stays the caller's): the first
+    one applies the range and strikes bin against bin in ONE pass over the subject's staged survivors (capi.binned_strike);
+    what is left is a short list (capi.Candidates), and every further control is looked up in it, in place.
+    finish(exclude) -> (keys, counts): the range alone if no control came, the exclude sets, the read-out; frees itself.
+    raw_bytes: what the first strike gives back, 0 after it."""
+    entry_bytes = 12        # a staged survivor
+
+    def __init__(self, ctx, store, min_count: int, max_count: int):
+        self.ctx, self._h, self._range = ctx, store, (min_count, max_count)
+
+    def __len__(self):
+        return len(self._h)
+
+    @property
+    def raw_bytes(self) -> int:
+        return len(self._h) * self.entry_bytes if self._range else 0
+
+    def _becomes(self, struck):
+        self._h.free()
+        self._h, self._range = struck, None
+
+    def strike(self, control):
+        if self._range:
+            self._becomes(capi.binned_strike(self.ctx, self._h, control, *self._range))
+        else:
+            self._h.strike(control)
+
+    def finish(self, exclude):
+        if self._range:
+            self.strike(None)
+        for ex in exclude:
+            self._h.strike_records(ex)
+        out = self._h.keys_counts()
+        self.free()
+        return out
+
+    def free(self):
+        if self._h is not None:
+            self._h.free()
+            self._h = None
+
+
+class _SortedCandidates(_BinnedCandidates):
+    """The same of (pos,key)-sorted capi.Records: every strike is a records_subtract, which returns a new set."""
+    entry_bytes = 20        # a record: key, count, pos
+
+    def strike(self, *controls):
+        self._becomes(capi.records_subtract(self.ctx, self._h, list(controls), *(self._range or ())))
+
+    def finish(self, exclude):
+        if self._range:
+            self.strike()
+        if exclude:
+            self.strike(*exclude)
+        out = self._h.get()[:2]
+        self.free()
+        return out
+
+
+class _Attempt:
+    """What one attempt of WgsTrio.run() has computed, and what it still holds on the device."""
+
+    def __init__(self, n_samples: int, passes: int, verify):
+        self.histos, self.n_rec = [np.zeros(capi.HISTO_BINS, dtype=np.uint64) for _ in range(n_samples)], [0] * n_samples
+        self.keys, self.kcounts = [], []            # the hash list, pass by pass
+        self.recs = {sh: [] for sh in range(passes)}    # pass -> its records that are neither struck off nor kept yet
+        self.cands, self.kept = {}, []      # pass -> the subject's candidates; keep_shard_records: the finished passes' records
+        self.ver = {"bad_order": 0, "bad_pos": 0, "bad_count": 0, "sum_counts": [0] * n_samples,
+                    "probe_found": [0] * n_samples, "probe_count_out_of_range": 0,
+                    "checksum": [[0, 0] for _ in range(n_samples)]}   # rfx_records_checksum, summed over the shards
+        if verify == "binned":
+            self.ver.update(bad_bin=0, duplicate=0, not_canonical=0)
+
+    def release(self):
+        """A failed attempt: free what it holds (everything is held in one place, so each thing once)."""
+        held = [r for recs in list(self.recs.values()) + self.kept for r in recs] + list(self.cands.values())
+        self.recs, self.kept, self.cands = {}, [], {}
+        for r in held:
+            r.free()
+
+
 class WgsTrio:
     """count x (subject + controls) -> histograms -> hash list -> filter, in minimizer-shard passes."""
 
@@ -127,6 +252,7 @@ class WgsTrio:
         self.group = group
         self.early_budget = 0       # bytes of device memory that may hold records cut ahead for the next shard pass
         self._early, self._early_left, self._early_cost = {}, 0, 0
+        self._injected = False      # RFX_WGS_INJECT_OOM has fired (_inject: once per driver)
         # bytes of device memory that may hold RUN MAPS (32 B per read; rfx_runmaps_*): the first shard pass over a block
         # leaves one, the later passes rebuild their records from reads + map instead of hashing the block again
         # (one store for the trio, ONE piece of device memory of that size, kept from run to run: at 90 % of the HBM maps
@@ -152,17 +278,8 @@ class WgsTrio:
             raise ValueError("passes x ranks must not exceed the 256 virtual minimizer bins")
 
     def _count_shard_local(self, blocks, shard: int, si, binned: bool = False):
-        """One device: the table of this (sample, shard).  Shard passes hash every block once per pass; with
-        `early_budget` bytes of headroom (bench.py: what the device has left beside the peak of a step) the blocks are, as
-        far as that goes, hashed ONCE for this shard and the next (rfx_count_set_early): the next shard's records wait
-        in a table of their own (self._early) and that pass is given only the other blocks.
+        """One device: the table of this (sample, shard), from run maps (_add_replayed) or from the blocks (_add_cut_ahead).
         binned: the count ends with the survivors grouped by minimizer bin (capi.Binned) instead of sorted records."""
-        def finish(t_):
-            if binned:
-                self.binned_counts += 1
-                return t_.finish_binned(self.lower, want_histo=True)
-            return t_.finish(self.lower, want_histo=True)
-
         held = self._early.pop((si, shard), None) if si is not None else None
         if held is not None:
             t, done = held
@@ -170,58 +287,68 @@ class WgsTrio:
             t, done = capi.CountTable(self.ctx, self.k, self.size, True, mode=capi.COUNT_MSP), frozenset()
             if self.passes > 1:
                 t.set_shard(shard, self.passes)
-        nxt = None
         store = self._store if si is not None and self.passes > 1 else None
         try:
             if store is not None:       # (run maps instead of blocks cut ahead: 32 instead of 132 bytes per read)
-                t.set_runmaps(store)
-                t.prepare_maps(blocks)       # (all of them behind ONE wait: 0.75 ms of idle device per block otherwise)
-                # Round 6: the maps of the sample that is counted NEXT are hashed on the ctx's second stream while this
-                # sample's records are partitioned, refined and sorted on the first (run(): self._ahead): the hashing launch
-                # is bound by the instructions it issues, the partition levels by the memory, and they share a CU.
-                nxt_blocks = self._ahead.pop((shard, si), None) if self._ahead else None
-                if nxt_blocks:
-                    self.maps_ahead += t.prefetch_maps(nxt_blocks)
-                last = shard == self.passes - 1
-                for b in blocks:
-                    t.add(b)
-                    if last:
-                        store.drop(b)
-                self.replayed_blocks += t.replayed()
-                if shard == 0:
-                    self._inject("maps", shard)      # (tests: the headroom turns out not to be there)
-                return finish(t)
-            todo = [i for i in range(len(blocks)) if i not in done]
-            ahead = set()
-            if si is not None and self.passes > 1 and shard + 1 < self.passes and self._early_left > 0 and not self.map_budget:
-                t.set_early(True)
-                cost = self._early_cost
-                while todo and self._early_left > cost:     # (cost: what the block before took)
-                    used0, n0 = self.ctx.mem_stats()["used"], t.early_segments()
-                    i = todo.pop(0)
-                    t.add(blocks[i])
-                    if t.early_segments() == n0:            # not a block for the early cut (small, or the shards meet
-                        break                               # inside a coarse bin): neither will the others be
-                    ahead.add(i)
-                    # (the block's own segment came with it: the early half is the next shard's share of the growth)
-                    cost = self._early_cost = (self.ctx.mem_stats()["used"] - used0) // 2
-                    self._early_left -= cost
-                t.set_early(False)
-                if ahead:
-                    self._inject("early", shard)     # (tests: the headroom turns out not to be there)
-            for i in todo:
-                t.add(blocks[i])
-            if ahead:
-                nxt = capi.CountTable(self.ctx, self.k, self.size, True, mode=capi.COUNT_MSP)
-                nxt.set_shard(shard + 1, self.passes)
-                nxt.adopt_early(t)
-                self._early[(si, shard + 1)] = (nxt, frozenset(ahead))
-                nxt = None
-            return finish(t)
+                self._add_replayed(t, store, blocks, shard, si)
+            else:
+                self._add_cut_ahead(t, done, blocks, shard, si)
+            if binned:
+                self.binned_counts += 1
+                return t.finish_binned(self.lower, want_histo=True)
+            return t.finish(self.lower, want_histo=True)
         finally:
-            if nxt is not None:
-                nxt.free()
             t.free()
+
+    def _add_replayed(self, t, store, blocks, shard: int, si):
+        """The adds of a count with run maps (the last pass drops them)."""
+        t.set_runmaps(store)
+        t.prepare_maps(blocks)       # (all of them behind ONE wait: 0.75 ms of idle device per block otherwise)
+        # Round 6: the maps of the sample that is counted NEXT are hashed on the ctx's second stream while this
+        # sample's records are partitioned, refined and sorted on the first (plan_maps_ahead: self._ahead): the hashing
+        # launch is bound by the instructions it issues, the partition levels by the memory, and they share a CU.
+        nxt_blocks = self._ahead.pop((shard, si), None) if self._ahead else None
+        if nxt_blocks:
+            self.maps_ahead += t.prefetch_maps(nxt_blocks)
+        last = shard == self.passes - 1
+        for b in blocks:
+            t.add(b)
+            if last:
+                store.drop(b)
+        self.replayed_blocks += t.replayed()
+        if shard == 0:
+            self._inject("maps", shard)      # (tests: the headroom turns out not to be there)
+
+    def _add_cut_ahead(self, t, done, blocks, shard: int, si):
+        """The adds of a count without run maps.  Shard passes hash every block once per pass; with `early_budget` bytes of
+        headroom (bench.py: what the device has left beside the peak of a step) the blocks are, as far as that goes, hashed
+        ONCE for this shard and the next (rfx_count_set_early): the next shard's records wait in a table of their own
+        (self._early) and that pass is given only the other blocks (`done`: those this table holds already)."""
+        todo = [i for i in range(len(blocks)) if i not in done]
+        ahead = set()
+        if si is not None and self.passes > 1 and shard + 1 < self.passes and self._early_left > 0 and not self.map_budget:
+            t.set_early(True)
+            cost = self._early_cost
+            while todo and self._early_left > cost:     # (cost: what the block before took)
+                used0, n0 = self.ctx.mem_stats()["used"], t.early_segments()
+                i = todo.pop(0)
+                t.add(blocks[i])
+                if t.early_segments() == n0:            # not a block for the early cut (small, or the shards meet
+                    break                               # inside a coarse bin): neither will the others be
+                ahead.add(i)
+                # (the block's own segment came with it: the early half is the next shard's share of the growth)
+                cost = self._early_cost = (self.ctx.mem_stats()["used"] - used0) // 2
+                self._early_left -= cost
+            t.set_early(False)
+            if ahead:
+                self._inject("early", shard)     # (tests: the headroom turns out not to be there)
+        for i in todo:
+            t.add(blocks[i])
+        if ahead:       # (the next pass's table is self._early's from birth: whatever fails here, _drop_early() frees it)
+            nxt = capi.CountTable(self.ctx, self.k, self.size, True, mode=capi.COUNT_MSP)
+            self._early[(si, shard + 1)] = (nxt, frozenset(ahead))
+            nxt.set_shard(shard + 1, self.passes)
+            nxt.adopt_early(t)
 
     def _drop_early(self):
         for t, _ in self._early.values():
@@ -478,61 +605,20 @@ class WgsTrio:
                 helper.join()
             own.free()
 
-    def _after_count(self, rec, recs, si, sh, cand, ver, verify, probe_keys, keep_shard_records, lap):
-        """What run() does with one sample's records of one pass (verify, candidates / strike-out); returns cand."""
-        if verify:
-            v = rec.verify(self.lower)
-            # (a Binned store reports bad_bin / duplicate / not_canonical where sorted records report bad_order / bad_pos)
-            for k_ in v:
-                if k_ != "sum_counts":
-                    ver[k_] += v[k_]
-            ver["sum_counts"][si] += v["sum_counts"]
-            ver["checksum"][si] = [(a + b) % (1 << 64) for a, b in zip(ver["checksum"][si], rec.checksum())]
-            if probe_keys is not None and len(probe_keys):
-                got = rec.query(np.asarray(probe_keys, dtype=np.uint64))
-                ver["probe_found"][si] += int((got > 0).sum())
-                if si == 0:
-                    ver["probe_count_out_of_range"] += int(((got > 0) & ((got < max(5, self.min_cov)) |
-                                                                         (got > self.max_cov))).sum())
-            lap(f"pass {sh} sample {si} verify")
-        if keep_shard_records:
-            return cand
-        if si == 0:
-            # The subject's records stay as they are until the first control is there: "MinCov <= count <= MaxDepth" and
-            # "not in control 1" are then ONE pass over them (round 4; before, the range alone made a 31 GB copy of a W
-            # shard that the next step read again: 20 ms per pass).  Without any control the range is applied at the end.
-            self._cand_raw = True
-            recs.pop()
-            lap(f"pass {sh} sample {si} kept ({len(rec)})")
-            return rec
-        raw = getattr(self, "_cand_raw", False)
-        if isinstance(rec, capi.Binned):
-            # The binned route: the first control is struck off the subject's staged survivors bin against bin (range and
-            # strike in one pass, as below); what is left is a short list, and every further control is looked up in it.
-            raw_bytes = len(cand) * 12 if raw else 0
-            if raw:
-                nxt = capi.binned_strike(self.ctx, cand, rec, max(5, self.min_cov), self.max_cov)
-                cand.free()
-                cand = nxt
-            else:
-                cand.strike(rec)
-        else:
-            raw_bytes = len(cand) * 20 if raw else 0
-            nxt = (capi.records_subtract(self.ctx, cand, [rec], max(5, self.min_cov), self.max_cov) if raw else
-                   capi.records_subtract(self.ctx, cand, [rec]))
-            cand.free()
-            cand = nxt
-        self._cand_raw = False
-        # The step's peak is the count of the FIRST control of a pass (the subject's records wait beside it); from here on
-        # the pass runs that much lower, and so may hold that much more of the next pass's records cut ahead -- provided the
-        # samples they belong to are counted BEFORE the first control of that pass (run() reverses the controls' order on
-        # odd passes).  Two passes only: with more, what is held overlaps from pass to pass.
-        if raw and self.passes == 2 and sh == 0 and self.early_budget > 0:
-            self._early_left += raw_bytes
-        rec.free()
-        recs.pop()
-        lap(f"pass {sh} sample {si} candidates ({len(cand)})")
-        return cand
+    def _verify_store(self, ver, rec, si: int, probe_keys):
+        """verify: one shard's records (or store) checked where they lie, added up in `ver`."""
+        v = rec.verify(self.lower)
+        for k_ in v:
+            if k_ != "sum_counts":
+                ver[k_] += v[k_]
+        ver["sum_counts"][si] += v["sum_counts"]
+        ver["checksum"][si] = [(a + b) % (1 << 64) for a, b in zip(ver["checksum"][si], rec.checksum())]
+        if probe_keys is not None and len(probe_keys):
+            got = rec.query(np.asarray(probe_keys, dtype=np.uint64))
+            ver["probe_found"][si] += int((got > 0).sum())
+            if si == 0:
+                ver["probe_count_out_of_range"] += int(((got > 0) & ((got < max(5, self.min_cov)) |
+                                                                     (got > self.max_cov))).sum())
 
     def pos_of(self, keys: np.ndarray) -> np.ndarray:
         """pos = (M * key) & (2^lsize - 1): bit b of the key selects column 2k-1-b."""
@@ -542,6 +628,115 @@ class WgsTrio:
         for b in range(c):
             pos ^= np.where((keys >> np.uint64(b)) & np.uint64(1), self.cols[c - 1 - b], np.uint64(0))
         return pos & np.uint64((1 << self.lsize) - 1) if self.lsize < 64 else pos
+
+    def _attempt(self, st, samples, keep_shard_records, verify, probe_keys, exclude, lap):
+        """One attempt of run() with the present `passes` and budgets: every (pass, sample) step, into `st`."""
+        self._drop_early()
+        self._early_left = int(self.early_budget) if self.world == 1 and not keep_shard_records else 0
+        self.replayed_blocks = self.binned_counts = self.maps_ahead = self.exchange_sent = self.exchange_received = 0
+        self.count_wall_s = 0.0
+        binned = verify == "binned" or (self._local() and not verify and not keep_shard_records and
+                                        not os.environ.get("RFX_TRIO_SORTED"))
+        candidates = _BinnedCandidates if binned else _SortedCandidates     # (the two routes: the module's docstring)
+        use_maps = self.map_budget > 0 and self.world == 1 and self.passes > 1 and not keep_shard_records
+        if not use_maps:
+            self._drop_store()
+        elif self._store is None:
+            try:
+                self._store = capi.RunMaps(self.ctx, int(self.map_budget), pooled=True)
+            except capi.RufusError:         # no room for the pool: the passes hash as before
+                self.map_budget, use_maps = 0, False
+        steps = plan_steps(self.passes, len(samples), use_maps, keep_shard_records)
+        last_step = {sh: i for i, (sh, _) in enumerate(steps)}
+        self._ahead = ({step: samples[si] for step, si in plan_maps_ahead(steps).items()}
+                       if use_maps and os.environ.get("RFX_MAP_AHEAD") else {})
+        for i_step, (sh, si) in enumerate(steps):
+            t_c = time.perf_counter()
+            rec, h = self.count_shard(samples[si], sh, si, binned)   # (its failures are agreed inside)
+            self.count_wall_s += time.perf_counter() - t_c
+            st.recs[sh].append(rec)
+            st.histos[si] += h
+            st.n_rec[si] += len(rec)
+            lap(f"pass {sh} sample {si} count ({len(rec)} records)")
+            err = None              # the rest of the iteration is local: on a group its failure is
+            try:                    # agreed at its end, so that no rank goes on into a collective alone
+                if verify:
+                    self._verify_store(st.ver, rec, si, probe_keys)
+                    lap(f"pass {sh} sample {si} verify")
+                if si == 0 and not keep_shard_records:
+                    # The subject's records stay as they are until the first control is there: "MinCov <= count <= MaxDepth"
+                    # and "not in control 1" are then ONE pass over them (round 4; before, the range alone made a 31 GB copy
+                    # of a W shard that the next step read again: 20 ms per pass).  Without any control: at the end.
+                    st.cands[sh] = candidates(self.ctx, st.recs[sh].pop(), max(5, self.min_cov), self.max_cov)
+                    lap(f"pass {sh} sample {si} kept ({len(rec)})")
+                elif not keep_shard_records:
+                    # The step's peak is the count of the FIRST control of a pass (the subject's records wait beside it); from
+                    # here on the pass runs that much lower, and so may hold that much more of the next pass's records cut ahead
+                    # -- provided the samples they belong to are counted BEFORE the first control of that pass (plan_steps
+                    # reverses the controls' order on odd passes).  Two passes only: with more, what is held overlaps.
+                    cand = st.cands[sh]
+                    room = cand.raw_bytes if self.passes == 2 and sh == 0 and self.early_budget > 0 else 0
+                    cand.strike(rec)
+                    self._early_left += room
+                    st.recs[sh].pop().free()
+                    lap(f"pass {sh} sample {si} candidates ({len(cand)})")
+            except Exception as e:
+                err = e
+            self.checkpoint(err)    # (one rank: raises err)
+            if i_step != last_step[sh]:
+                continue
+            if keep_shard_records:
+                recs = st.recs[sh]
+                k_, c_ = capi.unique_to_subject(self.ctx, recs[0], recs[1:] + exclude, self.min_cov, self.max_cov)
+                st.kept.append(st.recs.pop(sh))
+            else:
+                k_, c_ = st.cands[sh].finish(exclude)
+                del st.cands[sh]
+            lap(f"pass {sh} set difference ({len(k_)} k-mers)")
+            st.keys.append(k_)
+            st.kcounts.append(c_)
+
+    def _gather(self, st):
+        """(keys, counts, histograms, record counts) of an attempt; on a group: the whole hash list, the sums of the rest."""
+        keys = np.concatenate(st.keys) if st.keys else np.zeros(0, np.uint64)
+        kcounts = np.concatenate(st.kcounts).astype(np.uint32) if st.kcounts else np.zeros(0, np.uint32)
+        if self.world == 1:
+            return keys, kcounts, st.histos, st.n_rec
+        import torch
+        from .dist import all_gather_keys
+        dev = torch.device("cuda", torch.cuda.current_device())
+        kcounts = all_gather_keys(kcounts.astype(np.uint64), dev, self.group).astype(np.uint32)   # (rank by rank, as the keys)
+        keys = all_gather_keys(keys, dev, self.group)
+        histos = [x.astype(np.uint64) for x in self._group_sum(np.stack(st.histos))]
+        return keys, kcounts, histos, self._group_sum(st.n_rec).tolist()
+
+    def _group_sum(self, values) -> np.ndarray:
+        """The ranks' sums of an array of integers."""
+        values = np.asarray(values, dtype=np.int64)
+        if self.world == 1:
+            return values
+        import torch
+        import torch.distributed as dist
+        from .dist import _wire
+        t = _wire(torch.from_numpy(values).to(torch.device("cuda", torch.cuda.current_device())), self.group)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t.cpu().numpy()
+
+    def _filter(self, blocks, keys):
+        """The subject's blocks against the hash list: (pairs pulled, the blocks' hit masks)."""
+        n_pulled, masks = 0, []
+        if len(keys):
+            mset = capi.MutantSet(self.ctx, np.concatenate([keys, revcomp_keys(keys, self.k)]), self.k)
+            try:
+                # (all the subject's blocks behind one wait: a call per block left the device idle between two blocks)
+                for b, (mask, _) in zip(blocks, mset.filter_many(blocks, self.thresh, last_base_skipped=True)):
+                    n_pulled += pulled_pairs(mask, b.n)
+                    # (views of the ctx's page-locked buffer, overwritten by the next run(): copied unless the caller says
+                    # it is done with them by then -- bench.py's timed steps)
+                    masks.append(mask if self.masks_are_views else mask.copy())
+            finally:
+                mset.free()
+        return n_pulled, masks
 
     def run(self, samples, keep_shard_records: bool = False, verify=False, probe_keys=None, exclude=()):
         """samples: [subject blocks, control blocks, ...] (lists of capi.ReadBlock).
@@ -558,7 +753,6 @@ class WgsTrio:
         duplicate, not_canonical beside them."""
         if verify == "binned" and (not self._local() or keep_shard_records):
             raise ValueError('verify="binned": one device, no kept shard records')
-        exclude = list(exclude)
         trace = os.environ.get("RFX_WGS_TRACE")
         t_last = time.perf_counter()
 
@@ -566,123 +760,13 @@ class WgsTrio:
             nonlocal t_last
             if trace:
                 self.ctx.sync()
-                now = time.perf_counter()
-                print(f"[wgs] {what}: {(now - t_last) * 1e3:.1f} ms", flush=True)
-                t_last = now
+                print(f"[wgs] {what}: {(time.perf_counter() - t_last) * 1e3:.1f} ms", flush=True)
+                t_last = time.perf_counter()
 
         while True:
-            histos = [np.zeros(capi.HISTO_BINS, dtype=np.uint64) for _ in samples]
-            n_rec = [0] * len(samples)
-            keys, kcounts, kept, recs = [], [], [], []
-            cand, cands, shard_recs = None, {}, {}
-            self._drop_early()
-            self._early_left = int(self.early_budget) if self.world == 1 and not keep_shard_records else 0
-            self.replayed_blocks = self.binned_counts = 0
-            # A plain run needs of every count the histogram, the number of records and the set difference -- none of which
-            # needs the (pos,key) order of jellyfish's file: the survivors stay grouped by minimizer bin (capi.Binned) and
-            # the controls are struck off bin against bin.  Verified or kept records, a group of ranks: sorted records, as
-            # ever; RFX_TRIO_SORTED=1 forces them (A/B, bisecting).
-            binned = verify == "binned" or (self._local() and not verify and not keep_shard_records and
-                                            not os.environ.get("RFX_TRIO_SORTED"))
-            self.exchange_sent = self.exchange_received = 0
-            use_maps = self.map_budget > 0 and self.world == 1 and self.passes > 1 and not keep_shard_records
-            if not use_maps:
-                self._drop_store()
-            elif self._store is None:
-                try:
-                    self._store = capi.RunMaps(self.ctx, int(self.map_budget), pooled=True)
-                except capi.RufusError:         # no room for the pool: the passes hash as before
-                    self.map_budget, use_maps = 0, False
-            ver = {"bad_order": 0, "bad_pos": 0, "bad_count": 0, "sum_counts": [0] * len(samples),
-                   "probe_found": [0] * len(samples), "probe_count_out_of_range": 0,
-                   "checksum": [[0, 0] for _ in samples]}   # rfx_records_checksum, summed over the shards
-            if verify == "binned":
-                ver.update(bad_bin=0, duplicate=0, not_canonical=0)
+            st = _Attempt(len(samples), self.passes, verify)
             try:
-                # The subject (sample 0) is counted first and only its CANDIDATES stay: the records with MinCov <=
-                # count <= MaxDepth; every control then strikes out what it holds and is freed at once
-                # (rfx_records_subtract) -- one sample's records alive at a time instead of all of them.
-                # Order of the (pass, sample) steps.  Plain: pass by pass (odd passes take the controls in reverse: the
-                # control counted last in one pass -- whose records of the next pass may have been cut ahead in the room
-                # the subject's records left, see _after_count -- is the first control of the next).  With run maps:
-                # subject and first control pass by pass, then every further control through all its passes at once --
-                # the candidates a shard has left after the first control are few, so they can wait, and never more
-                # than two samples' maps are alive (the pool is sized for that: bench.py).
-                P, ns = self.passes, len(samples)
-                if use_maps and ns > 2:
-                    steps = [(sh, si) for sh in range(P) for si in (0, 1)] + [(sh, si) for si in range(2, ns) for sh in range(P)]
-                else:
-                    steps = [(sh, si) for sh in range(P)
-                             for si in (list(range(ns)) if sh % 2 == 0 or keep_shard_records else [0] + list(range(ns - 1, 0, -1)))]
-                last_step = {sh: max(i for i, (sh_, _) in enumerate(steps) if sh_ == sh) for sh in range(P)}
-                shard_recs.update({sh: [] for sh in range(P)})
-                # maps made ahead: the step before a sample's FIRST step queues that sample's maps -- if the store has room
-                # for them then (two samples' maps fit: the step must come after the last step of the sample before the
-                # previous one, whose maps go with its last pass)
-                self._ahead, self.maps_ahead, self.count_wall_s = {}, 0, 0.0
-                # (opt-in, RFX_MAP_AHEAD=1: measured at W it buys nothing -- 1943 against 1941 ms per step --: the hashing
-                # launch holds 414 of a SIMD's 512 registers, the replay and partition workgroups of the first stream do
-                # not fit beside it, and the two streams take turns instead of sharing the CUs)
-                if use_maps and os.environ.get("RFX_MAP_AHEAD"):
-                    first = {}
-                    for i, (_, si_) in enumerate(steps):
-                        first.setdefault(si_, i)
-                    last_of = {si_: max(i for i, (_, s_) in enumerate(steps) if s_ == si_) for si_ in first}
-                    order = sorted(first, key=first.get)
-                    for n_, si_ in enumerate(order[1:], 1):
-                        at = first[si_] - 1                      # the step that queues them
-                        if n_ >= 2 and at <= last_of[order[n_ - 2]]:
-                            continue                             # (three samples' maps would be alive)
-                        self._ahead[steps[at]] = samples[si_]
-                for i_step, (sh, si) in enumerate(steps):
-                    recs = shard_recs[sh]
-                    cand = cands.pop(sh, None)
-                    blocks = samples[si]
-                    t_c = time.perf_counter()
-                    rec, h = self.count_shard(blocks, sh, si, binned)   # (its failures are agreed inside)
-                    self.count_wall_s += time.perf_counter() - t_c
-                    recs.append(rec)
-                    histos[si] += h
-                    n_rec[si] += len(rec)
-                    lap(f"pass {sh} sample {si} count ({len(rec)} records)")
-                    err = None              # the rest of the iteration is local: on a group its failure is
-                    try:                    # agreed at its end, so that no rank goes on into a collective alone
-                        cand = self._after_count(rec, recs, si, sh, cand, ver, verify, probe_keys, keep_shard_records, lap)
-                    except Exception as e:
-                        err = e
-                    self.checkpoint(err)    # (one rank: raises err)
-                    if i_step != last_step[sh]:
-                        if cand is not None:
-                            cands[sh] = cand
-                        cand = None
-                        continue
-                    if keep_shard_records:
-                        k_, c_ = capi.unique_to_subject(self.ctx, recs[0], recs[1:] + exclude, self.min_cov, self.max_cov)
-                        kept.append(recs)
-                    else:
-                        if getattr(self, "_cand_raw", False):      # a subject without controls: the range alone
-                            nxt = (capi.binned_strike(self.ctx, cand, None, max(5, self.min_cov), self.max_cov) if binned else
-                                   capi.records_subtract(self.ctx, cand, [], max(5, self.min_cov), self.max_cov))
-                            cand.free()
-                            cand = nxt
-                            self._cand_raw = False
-                        if binned:
-                            for ex in exclude:
-                                cand.strike_records(ex)
-                            k_, c_ = cand.keys_counts()
-                        else:
-                            if exclude:
-                                nxt = capi.records_subtract(self.ctx, cand, exclude)
-                                cand.free()
-                                cand = nxt
-                            k_, c_ = cand.get()[:2]
-                        cand.free()
-                        cand = None
-                    lap(f"pass {sh} set difference ({len(k_)} k-mers)")
-                    keys.append(k_)
-                    kcounts.append(c_)
-                    shard_recs[sh] = []
-                    recs = []
+                self._attempt(st, samples, keep_shard_records, verify, probe_keys, list(exclude), lap)
                 break
             except capi.RufusError as e:
                 # the pass plan is an estimate: if a pass does not fit after all, take one more pass and start over.
@@ -690,15 +774,10 @@ class WgsTrio:
                 # checkpoint of count_shard) can be retried -- all ranks are here then, with the same `passes`.
                 agreed = isinstance(e, GroupFailure) and e.retry
                 self._drop_early()              # (run maps / early tables of the failed attempt, whatever follows)
+                st.release()
                 if (self.world > 1 and not agreed) or self.passes >= 64 or (self.passes + 1) * self.world > 256 or \
                         not _is_out_of_memory(e):
                     raise
-                held = [r_ for rr in shard_recs.values() for r_ in rr]
-                held += [r_ for r_ in recs if r_ not in held]
-                held += [r_ for shard in kept for r_ in shard if r_ not in held]
-                held += [c_ for c_ in [cand] + list(cands.values()) if c_ is not None and c_ not in held]
-                for r in held:
-                    r.free()
                 self._drop_early()
                 if self.world > 1:
                     import torch
@@ -712,57 +791,22 @@ class WgsTrio:
                 self.passes += 1
                 if trace:
                     print(f"[wgs] out of device memory: retrying with {self.passes} passes", flush=True)
-        keys = np.concatenate(keys) if keys else np.zeros(0, np.uint64)
-        kcounts = np.concatenate(kcounts).astype(np.uint32) if kcounts else np.zeros(0, np.uint32)
-        if self.world > 1:     # every rank needs the whole hash list; histograms and record counts add up
-            import torch
-            import torch.distributed as dist
-            from .dist import all_gather_keys, _wire
-            dev = torch.device("cuda", torch.cuda.current_device())
-            kcounts = all_gather_keys(kcounts.astype(np.uint64), dev, self.group).astype(np.uint32)   # (rank by rank, as the keys)
-            keys = all_gather_keys(keys, dev, self.group)
-            h = _wire(torch.from_numpy(np.stack(histos).astype(np.int64)).to(dev), self.group)
-            dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
-            histos = [x.astype(np.uint64) for x in h.cpu().numpy()]
-            nr = _wire(torch.tensor(n_rec, dtype=torch.int64, device=dev), self.group)
-            dist.all_reduce(nr, op=dist.ReduceOp.SUM, group=self.group)
-            n_rec = nr.tolist()
-        if len(keys):
-            order = np.lexsort((keys, self.pos_of(keys)))
-            keys, kcounts = keys[order], kcounts[order]
+        keys, kcounts, histos, n_rec = self._gather(st)
+        order = np.lexsort((keys, self.pos_of(keys)))
+        keys, kcounts = keys[order], kcounts[order]
         lap("hash list order")
-        n_pulled = 0
-        masks = []
-        if len(keys):
-            mset = capi.MutantSet(self.ctx, np.concatenate([keys, revcomp_keys(keys, self.k)]), self.k)
-            try:
-                # (all the subject's blocks behind one wait: a call per block left the device idle between two blocks)
-                for b, (mask, _) in zip(samples[0], mset.filter_many(samples[0], self.thresh, last_base_skipped=True)):
-                    n_pulled += pulled_pairs(mask, b.n)
-                    # (views of the ctx's page-locked buffer, overwritten by the next run(): copied unless the caller says
-                    # it is done with them by then -- bench.py's timed steps)
-                    masks.append(mask if self.masks_are_views else mask.copy())
-            finally:
-                mset.free()
+        n_pulled_local, masks = self._filter(samples[0], keys)
         lap("filter")
-        n_pulled_local = n_pulled
-        if self.world > 1:
-            t_ = _wire(torch.tensor([n_pulled], dtype=torch.int64, device=dev), self.group)
-            dist.all_reduce(t_, op=dist.ReduceOp.SUM, group=self.group)
-            n_pulled = int(t_.item())
-        out = {"n_mutant": len(keys), "n_pulled_local": n_pulled_local, "mutant_keys": keys, "mutant_counts": kcounts, "n_pulled": n_pulled, "n_records": n_rec, "histos": histos,
-               "hit_masks": masks}
+        out = {"n_mutant": len(keys), "n_pulled_local": n_pulled_local, "mutant_keys": keys, "mutant_counts": kcounts,
+               "n_pulled": int(self._group_sum([n_pulled_local])[0]), "n_records": n_rec, "histos": histos, "hit_masks": masks}
         if keep_shard_records:
-            out["shard_records"] = kept
+            out["shard_records"] = st.kept
         if verify:
-            if self.world > 1:
-                v_ = _wire(torch.tensor([ver["bad_order"], ver["bad_pos"], ver["bad_count"], ver["probe_count_out_of_range"]]
-                                        + ver["sum_counts"] + ver["probe_found"], dtype=torch.int64, device=dev), self.group)
-                dist.all_reduce(v_, op=dist.ReduceOp.SUM, group=self.group)
-                v_ = v_.tolist()
-                n_ = len(samples)
-                ver.update(bad_order=v_[0], bad_pos=v_[1], bad_count=v_[2], probe_count_out_of_range=v_[3],
-                           sum_counts=v_[4:4 + n_], probe_found=v_[4 + n_:4 + 2 * n_])
+            ver, n_ = st.ver, len(samples)
+            v_ = self._group_sum([ver["bad_order"], ver["bad_pos"], ver["bad_count"], ver["probe_count_out_of_range"]]
+                                 + ver["sum_counts"] + ver["probe_found"]).tolist()
+            ver.update(bad_order=v_[0], bad_pos=v_[1], bad_count=v_[2], probe_count_out_of_range=v_[3],
+                       sum_counts=v_[4:4 + n_], probe_found=v_[4 + n_:4 + 2 * n_])
             out["verify"] = ver
         return out
 
@@ -795,8 +839,18 @@ def valid_windows_of_text(seq: np.ndarray, k: int) -> int:
     return tot
 
 
+def snv_allowance(sy: capi.Synth, n_pairs: int, k: int) -> int:
+    """How many k-mers may be the subject's alone without being an SNV's: sites where >= 5 of the c reads that cover a base
+    carry the SAME substitution -- G * 3 * C(c, 5) * (e / 3)^5 of them (17 at 30x, 660 at 60x for 3.1 Gb and e = 0.5 %),
+    up to k k-mers each; three times that plus 30 sites."""
+    import math
+    cov = max(5, int(round(n_pairs * 2 * sy.read_len / sy.genome_len)))
+    sites = sy.genome_len * 3.0 * math.comb(cov, 5) * (sy.err_1024 / 1024.0 / 3.0) ** 5
+    return int(k * (3 * sites + 30))
+
+
 def self_check(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, min_q: int = 15,
-               more_passes: bool = True, sample_pairs: int = 1 << 17) -> dict:
+               more_passes: bool = True, sample_pairs: int = 1 << 17, verify=True) -> dict:
     """What must hold at ANY size, checked on the data of a finished run `res` of `trio` on `samples` (bench.py runs
     this after its timed region; tests/test_scale_gpu.py at the full size of BASELINE configs[2]).  Raises
     AssertionError; returns a summary for the bench line.
@@ -807,26 +861,32 @@ def self_check(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, 
     2. the mutant k-mers: each is held by the subject with MinCov <= count <= MaxDepth and by NO control (looked up
        in every shard of every sample: merge_files.cc:69-155 + CheckJellyHashList.sh:12 semantics), and they are the
        alt-allele k-mers of the planted SNVs (a handful of recurrent sequencing errors aside);
-    3. one more shard pass (S + 1) gives the same record counts, histograms, hash list and pulled pairs -- and the same
-       multiset of (key, count) records (rfx_records_checksum summed over the shards);
+    3. on one rank: one more shard pass (S + 1) gives the same record counts, histograms, hash list and pulled pairs -- and
+       the same multiset of (key, count) records (rfx_records_checksum summed over the shards);
     4. a sampled block of the subject counted alone with lower = 1: sum(i * histo[i]) == the number of ACGT-only
-       windows, computed on the host from the generator's host twin (text), not from the packed block."""
-    k = trio.k
-    out = {}
+       windows, computed on the host from the generator's host twin (text), not from the packed block.
+    verify="binned" (self_check_binned): the route a plain run() takes -- in 1. and 3. every store is verified where the count
+    left it (every survivor canonical, count >= lower, in its minimizer's bin, there once) and 1. compares the counts too."""
+    binned, k = verify == "binned", trio.k
     keys0 = np.asarray(res["mutant_keys"], dtype=np.uint64)
-    rv = trio.run(samples, verify=True, probe_keys=keys0)
+    rv = trio.run(samples, verify=verify, probe_keys=keys0)
+    assert not binned or trio.binned_counts == trio.passes * len(samples), "the binned route was left"
     v = rv["verify"]
-    assert v["bad_order"] == 0 and v["bad_pos"] == 0 and v["bad_count"] == 0, f"records fail their invariants: {v}"
+    assert all(v[x] == 0 for x in ("bad_order", "bad_pos", "bad_count") + (("bad_bin", "duplicate", "not_canonical") if binned else ())), \
+        f"{'stores' if binned else 'records'} fail their invariants: {v}"
     assert rv["n_records"] == res["n_records"] and rv["n_pulled"] == res["n_pulled"]
     assert np.array_equal(rv["mutant_keys"], keys0)
+    if binned and "mutant_counts" in res:
+        assert np.array_equal(rv["mutant_counts"], res["mutant_counts"])
     for si, h in enumerate(rv["histos"]):
         assert np.array_equal(h, res["histos"][si])
         assert int(h[-1]) != 0 or int(sum(int(x) * i for i, x in enumerate(h))) == v["sum_counts"][si], "histogram != records"
         assert int(h.sum()) == rv["n_records"][si]
     assert v["probe_found"][0] == len(keys0) and v["probe_count_out_of_range"] == 0, "a mutant k-mer is not the subject's"
     assert all(x == 0 for x in v["probe_found"][1:]), "a mutant k-mer occurs in a control"
-    out.update(records_verified=int(sum(rv["n_records"])), order_pos_count_violations=0,
-               mutant_in_subject=int(v["probe_found"][0]), mutant_in_controls=int(sum(v["probe_found"][1:])))
+    out = {"records_verified": int(sum(rv["n_records"])),
+           "bin_count_canonical_duplicate_violations" if binned else "order_pos_count_violations": 0,
+           "mutant_in_subject": int(v["probe_found"][0]), "mutant_in_controls": int(sum(v["probe_found"][1:]))}
     from .tools import keys_to_text
     if sys_[0].n_snv and len(samples) > 1:
         expect = expected_snv_kmers(sys_[0], k)
@@ -834,20 +894,17 @@ def self_check(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, 
         assert len(got) == len(keys0)
         extra = got - expect
         out.update(snv_kmers_expected=len(expect), snv_kmers_found=len(got & expect), not_snv_kmers=len(extra))
-        # k-mers that are the subject's alone without being an SNV's: sites where >= 5 of the c reads that cover a base
-        # carry the SAME substitution -- G * 3 * C(c, 5) * (e / 3)^5 of them (17 at 30x, 660 at 60x for 3.1 Gb and
-        # e = 0.5 %), up to k k-mers each; allow three times that plus 30 sites
-        import math
-        cov = max(5, int(round(n_pairs * 2 * sys_[0].read_len / sys_[0].genome_len)))
-        e3 = sys_[0].err_1024 / 1024.0 / 3.0
-        sites = sys_[0].genome_len * 3.0 * math.comb(cov, 5) * e3 ** 5
-        out["not_snv_kmers_allowed"] = int(k * (3 * sites + 30))
+        out["not_snv_kmers_allowed"] = snv_allowance(sys_[0], n_pairs, k)
         assert len(extra) <= out["not_snv_kmers_allowed"], f"{len(extra)} mutant k-mers are no SNV k-mers"
         if n_pairs * 300 >= 20 * sys_[0].genome_len:      # at >= 20x nearly every SNV k-mer reaches MinCov
             assert len(got & expect) >= 0.9 * len(expect), f"only {len(got & expect)} of {len(expect)} SNV k-mers found"
     if more_passes and trio.world == 1:
         t2 = WgsTrio(ctx, k, trio.size, trio.lower, trio.min_cov, trio.max_cov, trio.thresh, passes=trio.passes + 1)
-        r2 = t2.run(samples, verify=True)
+        try:
+            r2 = t2.run(samples, verify=verify)
+            assert not binned or t2.binned_counts == t2.passes * len(samples), "the binned route was left"
+        finally:
+            t2.close()
         assert r2["n_records"] == res["n_records"] and r2["n_pulled"] == res["n_pulled"]
         assert np.array_equal(r2["mutant_keys"], keys0)
         assert all(np.array_equal(a, b) for a, b in zip(r2["histos"], res["histos"]))
@@ -875,67 +932,9 @@ def self_check(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, 
     return out
 
 
-
 def self_check_binned(ctx: capi.Context, trio: "WgsTrio", samples, sys_, res, n_pairs, more_passes: bool = True) -> dict:
-    """Steps 1-3 of self_check() on the route a plain run() takes: every shard's store is checked where the count left it
-    (verify="binned": capi.Binned.verify / checksum / query) instead of being sorted first.  Raises AssertionError; returns
-    a summary.
-
-    1. a second run with every store verified on the device: every survivor canonical, count >= lower, in the bin its own
-       minimizer names and there once; the sum of the counts equals sum(i * histo[i]); the same record counts, histograms,
-       hash list (k-mers and counts) and pulled pairs as `res`;
-    2. the mutant k-mers: each is held by the subject with MinCov <= count <= MaxDepth and by NO control, and they are the
-       alt-allele k-mers of the planted SNVs (a handful of recurrent sequencing errors aside);
-    3. one more shard pass (S + 1) gives the same -- and the same multiset of (key, count) records."""
-    k = trio.k
-    out = {}
-    keys0 = np.asarray(res["mutant_keys"], dtype=np.uint64)
-    rv = trio.run(samples, verify="binned", probe_keys=keys0)
-    assert trio.binned_counts == trio.passes * len(samples), "the binned route was left"
-    v = rv["verify"]
-    assert all(v[x] == 0 for x in ("bad_order", "bad_pos", "bad_count", "bad_bin", "duplicate", "not_canonical")), \
-        f"stores fail their invariants: {v}"
-    assert rv["n_records"] == res["n_records"] and rv["n_pulled"] == res["n_pulled"]
-    assert np.array_equal(rv["mutant_keys"], keys0)
-    if "mutant_counts" in res:
-        assert np.array_equal(rv["mutant_counts"], res["mutant_counts"])
-    for si, h in enumerate(rv["histos"]):
-        assert np.array_equal(h, res["histos"][si])
-        assert int(h[-1]) != 0 or int(sum(int(x) * i for i, x in enumerate(h))) == v["sum_counts"][si], "histogram != records"
-        assert int(h.sum()) == rv["n_records"][si]
-    assert v["probe_found"][0] == len(keys0) and v["probe_count_out_of_range"] == 0, "a mutant k-mer is not the subject's"
-    assert all(x == 0 for x in v["probe_found"][1:]), "a mutant k-mer occurs in a control"
-    out.update(records_verified=int(sum(rv["n_records"])), bin_count_canonical_duplicate_violations=0,
-               mutant_in_subject=int(v["probe_found"][0]), mutant_in_controls=int(sum(v["probe_found"][1:])))
-    from .tools import keys_to_text
-    if sys_[0].n_snv and len(samples) > 1:
-        expect = expected_snv_kmers(sys_[0], k)
-        got = set(x.encode() for x in keys_to_text(keys0, k))
-        assert len(got) == len(keys0)
-        extra = got - expect
-        out.update(snv_kmers_expected=len(expect), snv_kmers_found=len(got & expect), not_snv_kmers=len(extra))
-        import math     # (the allowance of self_check: recurrent errors at G * 3 * C(c, 5) * (e / 3)^5 sites)
-        cov = max(5, int(round(n_pairs * 2 * sys_[0].read_len / sys_[0].genome_len)))
-        e3 = sys_[0].err_1024 / 1024.0 / 3.0
-        sites = sys_[0].genome_len * 3.0 * math.comb(cov, 5) * e3 ** 5
-        out["not_snv_kmers_allowed"] = int(k * (3 * sites + 30))
-        assert len(extra) <= out["not_snv_kmers_allowed"], f"{len(extra)} mutant k-mers are no SNV k-mers"
-        if n_pairs * 300 >= 20 * sys_[0].genome_len:
-            assert len(got & expect) >= 0.9 * len(expect), f"only {len(got & expect)} of {len(expect)} SNV k-mers found"
-    if more_passes:
-        t2 = WgsTrio(ctx, k, trio.size, trio.lower, trio.min_cov, trio.max_cov, trio.thresh, passes=trio.passes + 1)
-        try:
-            r2 = t2.run(samples, verify="binned")
-            assert t2.binned_counts == t2.passes * len(samples), "the binned route was left"
-        finally:
-            t2.close()
-        assert r2["n_records"] == res["n_records"] and r2["n_pulled"] == res["n_pulled"]
-        assert np.array_equal(r2["mutant_keys"], keys0)
-        assert all(np.array_equal(a, b) for a, b in zip(r2["histos"], res["histos"]))
-        assert r2["verify"]["checksum"] == v["checksum"], "S and S + 1 shard passes do not hold the same records"
-        out["passes_compared"] = [trio.passes, t2.passes]
-        out["multiset_checksums"] = ["%016x" % c[0] for c in v["checksum"]]
-    return out
+    """Steps 1-3 of self_check() on the route a plain run() takes (verify="binned")."""
+    return self_check(ctx, trio, samples, sys_, res, n_pairs, more_passes=more_passes, sample_pairs=0, verify="binned")
 
 
 def make_sample(ctx: capi.Context, sy: capi.Synth, n_pairs: int, block_pairs: int = 1 << 24, min_q: int = 15,

@@ -273,6 +273,25 @@ def test_auto_mode_falls_back_to_the_table_when_the_budget_is_small(small_trio):
         small.close()
 
 
+def test_pinned_buffer_outlives_its_growth():
+    """Context.pinned_u64: when the page-locked buffer has to grow, views of the one before stay valid until close()
+    (WgsTrio.run() hands such views out as hit masks when masks_are_views is set)."""
+    c = capi.Context(0, hbm_budget=20 << 20)
+    first = second = None
+    try:
+        first = c.pinned_u64(8)
+        first[:] = np.arange(8, dtype=np.uint64) * np.uint64(0x0101010101010101)
+        second = c.pinned_u64(1 << 16)
+        second[:] = np.uint64(0xFFFFFFFFFFFFFFFF)
+        assert len(second) == 1 << 16 and second.ctypes.data != first.ctypes.data
+        assert np.array_equal(first, np.arange(8, dtype=np.uint64) * np.uint64(0x0101010101010101))
+        assert c.pinned_u64(8).ctypes.data == second.ctypes.data       # (the grown buffer is the one reused)
+    finally:
+        del first, second
+        c.close()
+    assert c._h is None
+
+
 def test_finish_begin_end_pipelines_several_tables(ctx, small_trio):
     """Three tables queued before the first is waited for (MSP: nothing blocks in _begin; the k = 31
     table finishes inside _begin) give the same records and histograms as finish()."""
