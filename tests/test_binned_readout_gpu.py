@@ -8,45 +8,13 @@ import pytest
 
 import oracle
 from rufus_amd import capi, tools, wgs
+from tests.binned_ref import by_key, np_bin, np_revcomp
 
 pytestmark = pytest.mark.gpu
 
 SIZE, MIN_COV, MAX_DEPTH, MIN_Q, THRESH = 8 << 30, 5, 1200, 15, 1
 UPPER = 1000
 G, N_PAIRS = 250_000, 25_000
-
-
-# ---- host restatements ---------------------------------------------------------------------------------------------
-def np_revcomp(keys: np.ndarray, n: int) -> np.ndarray:
-    x, r = keys.astype(np.uint64), np.zeros(len(keys), np.uint64)
-    for _ in range(n):
-        r = (r << np.uint64(2)) | (np.uint64(3) - (x & np.uint64(3)))
-        x = x >> np.uint64(2)
-    return r
-
-
-def np_bin(keys: np.ndarray, k: int, bits: int) -> np.ndarray:
-    """rfx_devutil.h msp_key_bin restated: window k - 15 from k = 26 on, else 11; m = k - (window - 1); the minimum over the
-    k-mer's own canonical m-mers of the upper 27 bits of mmer_hash, spread by msp_binhash, its top `bits` bits."""
-    M32 = np.uint64(0xFFFFFFFF)
-    wl = k - 15 if k >= 26 else 11
-    m = k - (wl - 1)
-    mmask = np.uint64((1 << (2 * m)) - 1)
-    keys = keys.astype(np.uint64)
-    minh = np.full(len(keys), 0xFFFFFFFF, np.uint64)
-    for i in range(wl):
-        f = (keys >> np.uint64(2 * i)) & mmask
-        c = np.minimum(f, np_revcomp(f, m))
-        h = ((c ^ np.uint64(0x5BD1E995)) * np.uint64(0x9E3779B1)) & M32
-        h = h ^ (h >> np.uint64(15))
-        minh = np.minimum(minh, h & np.uint64(0xFFFFFFE0))
-    bh = ((((minh & np.uint64(0xFFFFFFE0)) * np.uint64(0xC2B2AE3D)) & M32) >> np.uint64(1)) | ((minh & np.uint64(32)) << np.uint64(26))
-    return (bh >> np.uint64(32 - bits)).astype(np.uint32)
-
-
-def by_key(keys, counts):
-    o = np.argsort(keys, kind="stable")
-    return np.asarray(keys, np.uint64)[o], np.asarray(counts, np.uint64)[o]
 
 
 def sum_of_histo(h) -> int:
