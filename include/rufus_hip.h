@@ -153,6 +153,34 @@ uint64_t rfx_reads_words(const rfx_reads*);
 /* D2H copy of a block's arrays (sized by rfx_reads_words / rfx_reads_count; any pointer may be NULL). */
 int rfx_reads_get(const rfx_reads*, uint64_t* codes, uint32_t* acgt, uint32_t* good, uint32_t* word_off, uint32_t* len);
 
+/* Long sequences as reads.  The reference counts a FASTA of chromosomes or contigs with the loop it counts reads with:
+ * the parser hands every sequence out in buffers that overlap by k - 1 bases
+ * (jf/include/jellyfish/mer_overlap_sequence_parser.hpp:124-251) and the k-mer iterator slides over each
+ * (jf/include/jellyfish/mer_iterator.hpp:59-88).  Here every count kernel gives one lane to one read, so a block of long
+ * sequences is cut -- on the device -- into TILES of at most tile_len bases that start every step = tile_len - k + 1
+ * bases: the k-mer window that starts at base p of a sequence lies in tile p / step and in no other, so the tiled block
+ * has exactly the source's windows, invalid bases included (the ACGT mask is carried along).
+ *
+ * rfx_tile_plan: the plan for one sequence (pure host code).  A sequence of len <= tile_len bases is one tile, unchanged
+ * (len < k and len == 0 included); otherwise *n_tiles = ceil((len - k + 1) / step), tile t starts at base t * step and is
+ * min(tile_len, len - t * step) bases long (at least k).  RFX_E_INVAL for tile_len < k, k < 1 or k > 32.
+ *
+ * rfx_reads_tile: a new block (owned by the caller, rfx_reads_free) that holds the tiles of every read of `src`, a dense
+ * or a compact count block, in read order: codes, ACGT mask, offsets and lengths as rfx_pack_reads would make them of the
+ * tile substrings.  The `good` mask is not carried: a tiled block is for counting.  NULL on failure (rfx_last_error); a
+ * source whose tiled form would reach 2^32 tiles or words is refused, the text then starts with "rfx_reads_tile:
+ * RFX_E_RANGE".
+ *
+ * rfx_count_add does this by itself: a block whose longest read exceeds 1024 bases is counted through its tiled twin
+ * (tile_len 150), which belongs to the source block -- made at the first add for a given k, kept for the later shard
+ * passes and their run maps, replaced by another k's, freed (pending adds settled first) by rfx_reads_free of the source.
+ * The run-map calls that name the source (rfx_count_prepare_maps, rfx_count_prefetch_maps, rfx_runmaps_drop) act on the
+ * twin.  A twin that cannot be made (no memory, 2^32 tiles) leaves the untiled add: the same counts, slowly.
+ * RFX_NO_TILE=1 keeps the untiled route; RFX_TILE_LEN (<= 160) and RFX_TILE_SWITCH move the two lengths.  No knob changes
+ * a result. */
+int rfx_tile_plan(uint64_t len, int k, uint32_t tile_len, uint64_t* n_tiles, uint32_t* step);
+rfx_reads* rfx_reads_tile(rfx_ctx*, const rfx_reads* src, int k, uint32_t tile_len);
+
 /* -------------------------------------------------------------------------------------------
  * Text in, packed reads out -- on the device (kernel K1)
  * Replaces, for strict 4-line FASTQ, the reference's text parser and base packer

@@ -79,6 +79,8 @@ SIGNATURES = {
     "rfx_reads_bases": (C.c_uint64, [C.c_void_p]),
     "rfx_reads_words": (C.c_uint64, [C.c_void_p]),
     "rfx_reads_get": (C.c_int, [C.c_void_p, u64p, u32p, u32p, u32p, u32p]),
+    "rfx_tile_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_uint32, u64p, u32p]),
+    "rfx_reads_tile": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]),
     "rfx_synth_reads": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int]),
     "rfx_text_open": (C.c_void_p, [C.c_void_p, C.c_uint64]),
     "rfx_text_close": (None, [C.c_void_p]),
@@ -285,6 +287,16 @@ class Synth(C.Structure):
         return buf[:n].tobytes()
 
 
+def tile_plan(length: int, k: int, tile_len: int = 150):
+    """(n_tiles, step) of ``rfx_tile_plan``: how a sequence of `length` bases is cut into tiles of <= tile_len bases that
+    hold every k-mer window exactly once (tile t starts at t * step and is min(tile_len, length - t * step) long)."""
+    if length < 0 or not 0 <= tile_len < 2**32:
+        raise RufusError(f"rfx_tile_plan: {lib().rfx_strerror(E_INVAL).decode()} (code {E_INVAL})")
+    nt, step = C.c_uint64(0), C.c_uint32(0)
+    _check(lib().rfx_tile_plan(length, k, tile_len, C.byref(nt), C.byref(step)), "rfx_tile_plan")
+    return int(nt.value), int(step.value)
+
+
 class PackedReads:
     """Host-side packed block: 32 bases per 64-bit code word, one mask bit per base."""
 
@@ -475,6 +487,14 @@ class ReadBlock:
                 out[k_] = out[k_][:nw]
         out["len"] = out["len"][:self.n]
         return out
+
+    def tile(self, k: int, tile_len: int = 150) -> "ReadBlock":
+        """A new block holding this block's reads cut into tiles of <= tile_len bases with the same k-mer windows
+        (``rfx_reads_tile``; for counting: no good mask).  CountTable.add() does this by itself for long sequences."""
+        h = lib().rfx_reads_tile(self.ctx._h, self._h, k, tile_len)
+        if not h:
+            raise RufusError("rfx_reads_tile failed: " + lib().rfx_last_error().decode())
+        return ReadBlock.from_handle(self.ctx, h)
 
     def free(self):
         if self._h:

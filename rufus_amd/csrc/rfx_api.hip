@@ -919,6 +919,10 @@ static void rfx_reads_release_pending(const rfx_reads* r);
 
 void rfx_reads_free(rfx_reads* r) {
   if (!r) return;
+  if (r->twin) {  // (its pending adds are settled by its own free, while the twin's reads are still there)
+    rfx_reads_free(r->twin);
+    r->twin = nullptr;
+  }
   rfx_reads_release_pending(r);  // a count table may still need these reads to redo its partition
   if (r->ctx->aux) (void)hipStreamSynchronize(r->ctx->aux);  // (a map made ahead may still be hashing them)
   dfree(r->ctx, r->codes); dfree(r->ctx, r->acgt); dfree(r->ctx, r->good);
@@ -972,6 +976,48 @@ int rfx_reads_get(const rfx_reads* r, uint64_t* codes, uint32_t* acgt, uint32_t*
   if (len && r->n) HIPCHK(hipMemcpyAsync(len, r->len, (size_t)r->n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(ctx_sync(c));
   return RFX_OK;
+}
+
+// ---- the tiled twin of a block of long sequences (rfx_tile.hip) ------------------------------------------------------
+// A block whose longest read exceeds the switch length is counted through a block of reads of <= RFX_TILE_LEN bases with
+// the same k-mer windows: every count kernel gives a lane to a read.  The switch length is a tuning number (both routes are
+// exact at any value); RFX_NO_TILE=1 keeps the untiled route, RFX_TILE_SWITCH / RFX_TILE_LEN move the two lengths.
+static uint32_t tile_switch_len() {
+  if (const char* ev = getenv("RFX_TILE_SWITCH")) return (uint32_t)std::max(0ll, std::min(atoll(ev), 0xFFFFFFFFll));
+  return 1024u;
+}
+static uint32_t tile_len_for(int k) {  // 0: no tile length for this k
+  long long L = 150;
+  if (const char* ev = getenv("RFX_TILE_LEN")) L = atoll(ev);
+  L = std::min(L, 160ll);  // (the whole-read kernels and the run maps take reads of up to 160 bases)
+  return L >= k && L >= 1 ? (uint32_t)L : 0u;
+}
+// The block rfx_count_add, the run maps and the shard passes work on in r's place: r's twin for this k (made here when
+// `make`), or r itself -- short reads, RFX_NO_TILE, or a twin that cannot be made (no memory, 2^32 tiles or words): the
+// untiled add is exact, only slow.
+static const rfx_reads* count_block(const rfx_reads* r, int k, bool make) {
+  if (!r || r->max_len <= 160u || r->n == 0) return r;  // (no tile length exceeds 160: reads of the usual kind leave here)
+  if (r->max_len <= tile_switch_len() || getenv("RFX_NO_TILE")) return r;
+  const uint32_t L = tile_len_for(k);
+  if (!L || r->max_len <= L) return r;
+  if (r->twin && r->twin_k == k && r->twin_len == L) return r->twin;
+  if (!make) return r;
+  if (r->twin) {  // another k: its twin goes (settling the adds that still need it)
+    rfx_reads_free(r->twin);
+    r->twin = nullptr;
+  }
+  int rc = RFX_OK;
+  rfx_reads* tw = rfxi::reads_tile(r->ctx, r, k, L, &rc);
+  if (!tw) return r;
+  r->twin = tw;
+  r->twin_k = k;
+  r->twin_len = L;
+  if (getenv("RFX_CLI_TRACE")) {
+    static std::atomic<unsigned long long> n_tiled{0};
+    fprintf(stderr, "[rfx] tile: block %llu through the tiler: %u reads (longest %u) -> %u tiles of <= %u bases, k = %d\n",
+            n_tiled.fetch_add(1) + 1, r->n, r->max_len, tw->n, L, k);
+  }
+  return tw;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2461,7 +2507,7 @@ static int msp_passes_leaf(rfx_finish* f) {
     t->n_shards = outer_n * S;
     for (const rfx_reads* r : *t->deferred) {
       if (r->n == 0) continue;
-      const int rc = msp_add(t, r);
+      const int rc = msp_add(t, count_block(r, t->k, true));
       if (rc) return rc;
     }
     // sharded peers: this table's partitions of the pass (other tables read them; the own run is counted where it lies)
@@ -3346,9 +3392,13 @@ int rfx_count_add(rfx_table* t, const rfx_reads* r) {
   pin_guard guard(c);
   (void)hipSetDevice(c->device);
   if (r->n == 0) return RFX_OK;
+  // long sequences: from here on the block is its tiled twin (the deferred list keeps the SOURCE: its twin may be replaced
+  // by another k's before the finish, which then makes it again)
+  const rfx_reads* src = r;
+  r = count_block(src, t->k, true);
   if (t->passes >= 0) {  // rfx_count_set_passes: counted at finish, shard pass by shard pass
     if (r->windows_of(t->k) >= (1ull << 32)) return RFX_E_RANGE;
-    t->deferred->push_back(r);
+    t->deferred->push_back(src);
     // The block is HASHED now -- its run map (rfx_msp.hip) --, while the caller is still parsing input and the device has
     // nothing to do: if the sample then takes more than one shard pass, the passes only cut records from reads + map
     // (`jellyfish count` of a 30x sample: 0.3 s less between "input parsed" and "finished on the device").  Maps of up to
@@ -3528,6 +3578,10 @@ int rfx_runmaps_blocks(const rfx_runmaps* s) {
 int rfx_runmaps_drop(rfx_runmaps* s, const rfx_reads* r) {
   if (!s || !r) return RFX_E_INVAL;
   (void)hipSetDevice(s->ctx->device);
+  if (r->twin) {  // (a block of long sequences: the map is its tiled twin's)
+    const int rc = rfx_runmaps_drop(s, r->twin);
+    if (rc) return rc;
+  }
   if (s->ahead)  // (only if the block is among the maps on their way: the others may keep flying)
     for (const runmap_pending& p : s->ahead->pend)
       if (p.r == r) {
@@ -3573,6 +3627,10 @@ int rfx_count_prefetch_maps(rfx_table* t, rfx_reads* const* blocks, int n) {
   a->k = t->k;
   a->canonical = t->canonical;
   a->pend.reserve((size_t)n);
+  // (blocks of long sequences: their tiled twins are made on the FIRST stream, before the two are swapped)
+  std::vector<const rfx_reads*> blk((size_t)n, nullptr);
+  for (int i = 0; i < n; ++i)
+    if (blocks[i] && blocks[i]->ctx == c) blk[(size_t)i] = count_block(blocks[i], t->k, true);
   // the second stream starts behind what the first has queued so far: a region of the pool that a dropped map gave back
   // may still be read by a replay launch of the first stream
   hipEvent_t after = nullptr;
@@ -3581,7 +3639,7 @@ int rfx_count_prefetch_maps(rfx_table* t, rfx_reads* const* blocks, int n) {
   if (after) (void)hipEventDestroy(after);
   std::swap(c->stream, c->aux);  // (the launchers take the ctx's stream)
   for (int i = 0; i < n && ok; ++i) {
-    const rfx_reads* r = blocks[i];
+    const rfx_reads* r = blk[(size_t)i];
     if (!r || r->ctx != c || r->max_len > 160 || r->n == 0 || st->m.count(r)) continue;
     bool twice = false;
     for (const runmap_pending& q : a->pend) twice = twice || q.r == r;
@@ -3626,7 +3684,7 @@ int rfx_count_prepare_maps(rfx_table* t, rfx_reads* const* blocks, int n) {
   std::vector<runmap_pending> pend;
   pend.reserve((size_t)n);  // (the read-backs point into it)
   for (int i = 0; i < n && rc == RFX_OK; ++i) {
-    const rfx_reads* r = blocks[i];
+    const rfx_reads* r = blocks[i] && blocks[i]->ctx == c ? count_block(blocks[i], t->k, true) : nullptr;
     if (!r || r->ctx != c || r->max_len > 160 || r->n == 0) continue;
     if (runmap_get(t, r, false, &rc) || t->runmaps->m.count(r)) continue;  // there already (or known to be no block for one)
     bool twice = false;  // (a block named twice: ONE launch, one entry)

@@ -223,6 +223,12 @@ struct rfx_reads {
   uint64_t n_exc;
   rfx_reads_view view() const { return rfx_reads_view{codes, acgt, good, word_off, len, n, ulen, uwpr, nbits, nrank}; }
   uint32_t short_cnt[32];  // reads of length 0..31: they have no window for k > length, see windows_of()
+  // The tiled twin (rfx_tile.hip): a block of long sequences is counted through a block of reads of <= twin_len bases
+  // with the same k-mer windows, made at the first rfx_count_add for a given k and kept for the later shard passes.  It
+  // belongs to this block: rfx_reads_free frees it (after settling its pending adds), another k replaces it.
+  mutable rfx_reads* twin;
+  mutable int twin_k;
+  mutable uint32_t twin_len;
   // exact number of length-k windows of the block: sum over reads of max(0, len - k + 1)
   uint64_t windows_of(int k) const {
     uint64_t bases = n_bases, reads = n;
@@ -534,6 +540,8 @@ hipError_t sync(rfx_ctx*);                                               // stre
 hipError_t queue_read(rfx_ctx*, void* dst, const void* d_src, size_t n);  // lands at the next sync
 // once per ctx and kernel (`bit` names the kernel): allow `bytes` of dynamic LDS; false (and the ctx poisoned) if refused
 bool lds_opt_in(rfx_ctx*, const void* fn, size_t bytes, int bit, const char* name);
+// rfx_reads_tile with the RFX_E_* code of a refusal in *rc (rfx_tile.hip)
+rfx_reads* reads_tile(rfx_ctx*, const rfx_reads* src, int k, uint32_t tile_len, int* rc);
 }  // namespace rfxi
 
 // Launch bracket: records a HIP-event span on the ctx stream when profiling is on.
