@@ -550,6 +550,36 @@ int rfx_filter(rfx_set*, const rfx_reads*, int thresh, int last_base_skipped, ui
 int rfx_filter_many(rfx_set*, const rfx_reads* const* blocks, int n, int thresh, int last_base_skipped,
                     uint64_t* const* hitmask_out, uint64_t* n_hit_reads);
 
+/* The pull of the hit reads (the write loop of src/RUFUS.Filter.cpp after :196-277: "a pair is written when either mate
+ * reached the threshold"), for reads that live in device blocks: the selected reads become a block of their own.
+ *
+ * rfx_reads_select: a new block (owned by the caller, rfx_reads_free) with the selected reads of `src` in source order.  It
+ * is a DENSE block whether `src` is dense or compact: codes, word_off and len always, `good` if the source has it, the ACGT
+ * mask if the source has one (a compact read without a mask entry gets all ones up to its length) -- every array
+ * byte-identical to what rfx_pack_reads makes of the selected reads' text, read / word / base counts exact, so the block
+ * counts and filters like any other.  Mask bits at or above the read count are ignored.  No read selected or an empty
+ * source: a valid block of 0 reads.  The result owns nothing of the source and outlives it.  NULL on refusal, the error text
+ * then starts with the function's name and the code: "rfx_reads_select: RFX_E_RANGE" for a selection of 2^32 reads or words
+ * or more, RFX_E_INVAL for a bad mode, a NULL mask or a block of another context.
+ *
+ * rfx_reads_origin: where the reads of a block made by rfx_reads_select / rfx_filter_pull came from: block_out[i] = index
+ * of the source block in the call's array (0 for rfx_reads_select), read_out[i] = read index in that block; either may be
+ * NULL.  RFX_E_INVAL for a block that was not made by these two.
+ *
+ * rfx_filter_pull: rfx_filter_many, plus the pulled reads of all n blocks as ONE block (block 0's first); the masks never
+ * leave the device unless hitmask_out asks for them.  hitmask_out / n_hit_reads exactly as rfx_filter_many gives them (the
+ * per-read bits BEFORE the pair rule).  The ACGT mask is present only if every block has one.  n = 0: a valid empty block.
+ * NULL on refusal as above under its own name; a block without `good` is RFX_E_INVAL.  Two waits for the device per call,
+ * however many blocks. */
+#define RFX_SELECT_READS 0   /* read r is selected when bit r of the mask is set */
+#define RFX_SELECT_PAIRS 1   /* reads 2p and 2p+1 are mates (the driver's and rfx_synth_reads' layout): read r is selected
+                                when bit r or bit r^1 is set; the last read of a block with an odd read count has no
+                                mate and goes by its own bit */
+rfx_reads* rfx_reads_select(rfx_ctx*, const rfx_reads* src, const uint64_t* hitmask /* host, ceil(n/64) words */, int mode);
+int rfx_reads_origin(const rfx_reads*, uint32_t* block_out, uint32_t* read_out);
+rfx_reads* rfx_filter_pull(rfx_set*, const rfx_reads* const* blocks, int n, int thresh, int last_base_skipped, int mode,
+                           uint64_t* const* hitmask_out, uint64_t* n_hit_reads);
+
 /* ---------------------------------------------------------------------------------------------
  * N4: coverage model fit (src/ModelDist.cpp; runRufus.sh:849 runs it on every sample's histogram,
  * :862-868 read MutantMinCov and MutantSC from lines 2 and 4 of HISTO.7.7.model)

@@ -21,6 +21,7 @@ PACK_COUNT, PACK_FILTER = 1, 2
 COUNT_AUTO, COUNT_TABLE, COUNT_P2L, COUNT_MSP = 0, 1, 2, 3
 E_FULL, E_RANGE, E_MIXEDCASE = -4, -7, -6
 E_INVAL, E_FORMAT = -2, -8
+SELECT_READS, SELECT_PAIRS = 0, 1
 
 u8p, u32p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 
@@ -81,6 +82,9 @@ SIGNATURES = {
     "rfx_reads_get": (C.c_int, [C.c_void_p, u64p, u32p, u32p, u32p, u32p]),
     "rfx_tile_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_uint32, u64p, u32p]),
     "rfx_reads_tile": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]),
+    "rfx_reads_select": (C.c_void_p, [C.c_void_p, C.c_void_p, u64p, C.c_int]),
+    "rfx_reads_origin": (C.c_int, [C.c_void_p, u32p, u32p]),
+    "rfx_filter_pull": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64p), u64p]),
     "rfx_synth_reads": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int]),
     "rfx_text_open": (C.c_void_p, [C.c_void_p, C.c_uint64]),
     "rfx_text_close": (None, [C.c_void_p]),
@@ -495,6 +499,23 @@ class ReadBlock:
         if not h:
             raise RufusError("rfx_reads_tile failed: " + lib().rfx_last_error().decode())
         return ReadBlock.from_handle(self.ctx, h)
+
+    def select(self, mask: np.ndarray, pairs: bool = False) -> "ReadBlock":
+        """A new dense block with the reads whose bit is set in `mask` (uint64 words, bit r % 64 of word r // 64), in
+        source order (``rfx_reads_select``).  pairs: reads 2p and 2p + 1 are mates and go together."""
+        mask = np.ascontiguousarray(mask, dtype=np.uint64)
+        if len(mask) < (self.n + 63) // 64:
+            raise ValueError("select: the mask has fewer than ceil(n / 64) words")
+        h = lib().rfx_reads_select(self.ctx._h, self._h, _p(mask, u64p), SELECT_PAIRS if pairs else SELECT_READS)
+        if not h:
+            raise RufusError("rfx_reads_select failed: " + lib().rfx_last_error().decode())
+        return ReadBlock.from_handle(self.ctx, h)
+
+    def origin(self):
+        """(block_idx, read_idx) of every read of a block made by select() / MutantSet.pull_many(), as uint32 arrays."""
+        blk, rd = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint32)
+        _check(lib().rfx_reads_origin(self._h, _p(blk, u32p), _p(rd, u32p)), "rfx_reads_origin")
+        return blk[:self.n], rd[:self.n]
 
     def free(self):
         if self._h:
@@ -1000,6 +1021,27 @@ class MutantSet:
         nh = np.zeros(max(1, len(blocks)), np.uint64)
         _check(lib().rfx_filter_many(self._h, arr, len(blocks), thresh, int(last_base_skipped), mp, _p(nh, u64p)), "rfx_filter_many")
         return [(m, int(n)) for m, n in zip(masks, nh)]
+
+    def pull_many(self, blocks, thresh: int = 1, last_base_skipped: bool = True, pairs: bool = True, want_masks: bool = True):
+        """filter_many, and the reads (pairs: the read pairs) that hit as ONE new block (rfx_filter_pull; the caller frees
+        it): (ReadBlock, [(mask, n_hit_reads)]).  The masks are the per-read bits before the pair rule, views of the
+        ctx's page-locked buffer as filter_many's are; want_masks=False leaves them on the device (mask = None)."""
+        masks = [None] * len(blocks)
+        if want_masks:
+            words = [(b.n + 63) // 64 or 1 for b in blocks]
+            buf = self.ctx.pinned_u64(sum(words))
+            masks, at = [], 0
+            for w in words:
+                masks.append(buf[at:at + w])
+                at += w
+        arr = (C.c_void_p * max(1, len(blocks)))(*[b._h for b in blocks])
+        mp = (u64p * max(1, len(blocks)))(*[m.ctypes.data_as(u64p) for m in masks]) if want_masks else None
+        nh = np.zeros(max(1, len(blocks)), np.uint64)
+        h = lib().rfx_filter_pull(self._h, arr, len(blocks), thresh, int(last_base_skipped),
+                                  SELECT_PAIRS if pairs else SELECT_READS, mp, _p(nh, u64p))
+        if not h:
+            raise RufusError("rfx_filter_pull failed: " + lib().rfx_last_error().decode())
+        return ReadBlock.from_handle(self.ctx, h), [(m, int(n)) for m, n in zip(masks, nh)]
 
     def annotate(self, reads: ReadBlock) -> np.ndarray:
         cov = np.zeros(max(reads.bases, 1), dtype=np.uint32)

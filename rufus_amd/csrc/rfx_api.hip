@@ -928,6 +928,7 @@ void rfx_reads_free(rfx_reads* r) {
   dfree(r->ctx, r->codes); dfree(r->ctx, r->acgt); dfree(r->ctx, r->good);
   dfree(r->ctx, r->word_off); dfree(r->ctx, r->len);
   dfree(r->ctx, r->nbits); dfree(r->ctx, r->nrank);
+  dfree(r->ctx, r->org_block); dfree(r->ctx, r->org_read);
   delete r;
 }
 uint32_t rfx_reads_count(const rfx_reads* r) { return r ? r->n : 0; }
@@ -4547,6 +4548,66 @@ int rfx_filter_many(rfx_set* s, const rfx_reads* const* blocks, int n, int thres
     for (int i = 0; i < n; ++i) n_hit_reads[i] = nh[(size_t)i];
   for (void* p : held) dfree(c, p);
   return rc;
+}
+
+// The reads a mask selects as a block of their own (rfx_select.hip): the host mask goes up, the rest is reads_select_dev.
+rfx_reads* rfx_reads_select(rfx_ctx* c, const rfx_reads* src, const uint64_t* hitmask, int mode) {
+  if (!c || !src || src->ctx != c || !hitmask || (mode != RFX_SELECT_READS && mode != RFX_SELECT_PAIRS)) {
+    snprintf(g_err, sizeof g_err, "rfx_reads_select: RFX_E_INVAL: needs a block of this context, a mask and a mode RFX_SELECT_*");
+    return nullptr;
+  }
+  pin_guard guard(c);
+  (void)hipSetDevice(c->device);
+  const uint64_t nmask = ((uint64_t)src->n + 63) / 64;
+  uint64_t* d_mask = nmask ? (uint64_t*)dmalloc(c, nmask * 8) : nullptr;
+  if (nmask && !d_mask) {
+    snprintf(g_err, sizeof g_err, "rfx_reads_select: RFX_E_NOMEM: out of device memory");
+    return nullptr;
+  }
+  const hipError_t e = upload(c, d_mask, hitmask, nmask * 8);
+  if (e != hipSuccess) {
+    dfree(c, d_mask);
+    hip_fail(e, "rfx_reads_select");
+    return nullptr;
+  }
+  rfx_reads* out = rfxi::reads_select_dev(c, &src, &d_mask, 1, mode, "rfx_reads_select");
+  dfree(c, d_mask);
+  return out;
+}
+
+// rfx_filter_many whose masks stay on the device for the selection that follows: the pulled reads of a sample as ONE block.
+// The wait for the selection's totals is the filter's wait; one more at the end.
+rfx_reads* rfx_filter_pull(rfx_set* s, const rfx_reads* const* blocks, int n, int thresh, int last_base_skipped, int mode,
+                           uint64_t* const* hitmask_out, uint64_t* n_hit_reads) {
+  bool ok = s && n >= 0 && (!n || blocks) && (mode == RFX_SELECT_READS || mode == RFX_SELECT_PAIRS);
+  for (int i = 0; ok && i < n; ++i) ok = blocks[i] && blocks[i]->ctx == s->ctx && blocks[i]->good;
+  if (!ok) {
+    snprintf(g_err, sizeof g_err, "rfx_filter_pull: RFX_E_INVAL: needs a set, filter blocks (good mask) of its context and a mode RFX_SELECT_*");
+    return nullptr;
+  }
+  rfx_ctx* c = s->ctx;
+  pin_guard guard(c);
+  (void)hipSetDevice(c->device);
+  std::vector<void*> held;
+  std::vector<unsigned long long> nh((size_t)n, 0);
+  std::vector<const uint64_t*> d_masks((size_t)n, nullptr);
+  int rc = RFX_OK;
+  for (int i = 0; i < n && rc == RFX_OK; ++i) {
+    if (blocks[i]->n == 0) continue;
+    rc = filter_queue(s, blocks[i], thresh, last_base_skipped, nullptr, hitmask_out ? hitmask_out[i] : nullptr, &nh[(size_t)i], held);
+    d_masks[(size_t)i] = (const uint64_t*)held[held.size() - 2];  // (filter_queue holds d_hits, d_mask, d_n in this order)
+  }
+  rfx_reads* out = nullptr;
+  if (rc == RFX_OK) {
+    out = rfxi::reads_select_dev(c, blocks, d_masks.data(), n, mode, "rfx_filter_pull");
+  } else {
+    (void)ctx_sync(c);  // (read-backs may be queued)
+    if (rc == RFX_E_NOMEM) snprintf(g_err, sizeof g_err, "rfx_filter_pull: RFX_E_NOMEM: out of device memory");
+  }
+  if (out && n_hit_reads)
+    for (int i = 0; i < n; ++i) n_hit_reads[i] = nh[(size_t)i];
+  for (void* p : held) dfree(c, p);
+  return out;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -229,6 +229,10 @@ struct rfx_reads {
   mutable rfx_reads* twin;
   mutable int twin_k;
   mutable uint32_t twin_len;
+  // A block made by rfx_reads_select / rfx_filter_pull (rfx_select.hip) remembers where its reads came from: source block
+  // (index in the call's array) and read index in it, n entries each on the device; owned by this block.
+  uint32_t *org_block, *org_read;
+  int has_origin;
   // exact number of length-k windows of the block: sum over reads of max(0, len - k + 1)
   uint64_t windows_of(int k) const {
     uint64_t bases = n_bases, reads = n;
@@ -542,6 +546,11 @@ hipError_t queue_read(rfx_ctx*, void* dst, const void* d_src, size_t n);  // lan
 bool lds_opt_in(rfx_ctx*, const void* fn, size_t bytes, int bit, const char* name);
 // rfx_reads_tile with the RFX_E_* code of a refusal in *rc (rfx_tile.hip)
 rfx_reads* reads_tile(rfx_ctx*, const rfx_reads* src, int k, uint32_t tile_len, int* rc);
+// The selected reads of n_blocks blocks of this ctx as ONE dense block (rfx_select.hip): d_masks[i] = device mask of block i
+// (ceil(n / 64) words; not read for an empty block), mode = RFX_SELECT_*.  Two waits, the first of which also delivers what
+// the caller queued.  nullptr with "<who>: RFX_E_...: ..." as the error text.
+rfx_reads* reads_select_dev(rfx_ctx*, const rfx_reads* const* blocks, const uint64_t* const* d_masks, int n_blocks, int mode,
+                            const char* who);
 }  // namespace rfxi
 
 // Launch bracket: records a HIP-event span on the ctx stream when profiling is on.

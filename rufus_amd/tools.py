@@ -302,3 +302,19 @@ def rufus_filter_single(ctx: capi.Context, hashlist: str, fastq: str, stub: str,
         for i in np.flatnonzero(pulled):
             f.write(h[i] + b":MH%d\n" % int(hits[i]) + s[i] + b"\n" + p[i] + b"\n" + q[i] + b"\n")
     return int(pulled.sum())
+
+
+# ---------------------------------------------------------------------------------------------------
+# packed blocks back to text
+# ---------------------------------------------------------------------------------------------------
+def decode_reads(arrays: dict) -> list:
+    """The sequences of a packed block, from the dict ``capi.ReadBlock.get()`` returns (codes, word_off, len and, if
+    there, acgt): ``A C G T`` by the 2-bit codes, ``N`` where the ACGT bit is clear (which base it was is not kept)."""
+    codes, word_off, lens, acgt = arrays["codes"], arrays["word_off"], arrays["len"], arrays.get("acgt")
+    pos = (2 * np.arange(32)).astype(np.uint64)
+    letters = _LETTERS[((codes[:, None] >> pos[None, :]) & np.uint64(3)).astype(np.intp)]      # words x 32
+    if acgt is not None:
+        valid = np.unpackbits(np.ascontiguousarray(acgt, dtype="<u4").view(np.uint8), bitorder="little").reshape(-1, 32)
+        letters = np.where(valid.astype(bool), letters, np.uint8(ord("N")))
+    flat = np.ascontiguousarray(letters, dtype=np.uint8).reshape(-1).tobytes()
+    return [flat[32 * int(w):32 * int(w) + int(n)] for w, n in zip(word_off[:len(lens)], lens)]

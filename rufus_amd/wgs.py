@@ -722,28 +722,40 @@ class WgsTrio:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return t.cpu().numpy()
 
-    def _filter(self, blocks, keys):
-        """The subject's blocks against the hash list: (pairs pulled, the blocks' hit masks)."""
-        n_pulled, masks = 0, []
-        if len(keys):
+    def _filter(self, blocks, keys, pull: bool = False):
+        """The subject's blocks against the hash list: (pairs pulled, the blocks' hit masks, the pulled pairs as a block
+        of their own when `pull`, else None)."""
+        n_pulled, masks, pulled = 0, [], None
+        if len(keys) or pull:
             mset = capi.MutantSet(self.ctx, np.concatenate([keys, revcomp_keys(keys, self.k)]), self.k)
             try:
                 # (all the subject's blocks behind one wait: a call per block left the device idle between two blocks)
-                for b, (mask, _) in zip(blocks, mset.filter_many(blocks, self.thresh, last_base_skipped=True)):
+                if not len(keys):
+                    pulled, res = mset.pull_many([], self.thresh, last_base_skipped=True, pairs=True)[0], []
+                elif pull:
+                    pulled, res = mset.pull_many(blocks, self.thresh, last_base_skipped=True, pairs=True)
+                else:
+                    res = mset.filter_many(blocks, self.thresh, last_base_skipped=True)
+                for b, (mask, _) in zip(blocks, res):
                     n_pulled += pulled_pairs(mask, b.n)
                     # (views of the ctx's page-locked buffer, overwritten by the next run(): copied unless the caller says
                     # it is done with them by then -- bench.py's timed steps)
                     masks.append(mask if self.masks_are_views else mask.copy())
             finally:
                 mset.free()
-        return n_pulled, masks
+        return n_pulled, masks, pulled
 
-    def run(self, samples, keep_shard_records: bool = False, verify=False, probe_keys=None, exclude=()):
+    def run(self, samples, keep_shard_records: bool = False, verify=False, probe_keys=None, exclude=(), pull: bool = False):
         """samples: [subject blocks, control blocks, ...] (lists of capi.ReadBlock).
 
         out["mutant_keys"] / out["mutant_counts"]: the hash list in (pos, key) order, `kmer` and the subject's `count`
         (runRufus.sh:925-926).  exclude: capi.Records (a count's, or a .Jhash loaded with Records.load / load_fd) whose
         k-mers are struck off after the controls -- runRufus.sh -e.
+
+        pull: the subject's pulled read pairs as a block of their own, selected on the device (rfx_filter_pull) --
+        out["pulled"] = {"block": capi.ReadBlock (the caller frees it), "origin_block", "origin_read": index of the
+        subject's block and of the read in it, per pulled read}.  On a process group it is the rank's own: the filter is
+        local.  Everything else is as without.
 
         verify: every shard's records are checked where they lie before they are freed (rfx_records_verify: strict
         (pos,key) order, pos == M * key, lower <= count) -> out["verify"]; probe_keys (canonical keys, e.g. the hash
@@ -795,10 +807,13 @@ class WgsTrio:
         order = np.lexsort((keys, self.pos_of(keys)))
         keys, kcounts = keys[order], kcounts[order]
         lap("hash list order")
-        n_pulled_local, masks = self._filter(samples[0], keys)
+        n_pulled_local, masks, pulled = self._filter(samples[0], keys, pull)
         lap("filter")
         out = {"n_mutant": len(keys), "n_pulled_local": n_pulled_local, "mutant_keys": keys, "mutant_counts": kcounts,
                "n_pulled": int(self._group_sum([n_pulled_local])[0]), "n_records": n_rec, "histos": histos, "hit_masks": masks}
+        if pull:
+            ob, orr = pulled.origin()
+            out["pulled"] = {"block": pulled, "origin_block": ob, "origin_read": orr}
         if keep_shard_records:
             out["shard_records"] = st.kept
         if verify:
