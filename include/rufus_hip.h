@@ -218,6 +218,40 @@ rfx_reads* rfx_text_parse(rfx_text*, int flags, int min_q, int* strict);
 int rfx_text_fetch(rfx_text*, void* host);
 void rfx_text_reset(rfx_text*);
 
+/* -------------------------------------------------------------------------------------------
+ * bgzip'd text in: BGZF inflated on the device, straight into the text arena
+ * Replaces the host inflater in front of the counter, `zcat F.fastq.gz | ...` (runRufus.sh:157-160, :229-232, :974-977):
+ * one host thread there, one wavefront per BGZF block here (k_bgzf_inflate, rufus_amd/csrc/rfx_bgzf.hip; the decoder
+ * itself, RFC 1951 / RFC 1952 / the BGZF section of the SAM specification: rufus_amd/csrc/rfx_bgzf_core.h).
+ *
+ * rfx_bgzf_scan (replaces runRufus.sh:157-160's zcat as the reader of the container; pure host code): walks whole BGZF
+ * blocks from buf[0] -- magic 1f 8b 08, FLG = FEXTRA, the `BC` subfield of length 2 wherever it lies among the extra
+ * subfields, BSIZE, ISIZE <= 65536 from the footer -- and stops at the first block that is not complete in buf (no
+ * error: *consumed says where) or after max_blocks.  *n_blocks, *consumed (bytes), *inflated (sum of ISIZE); any may be
+ * NULL.  RFX_E_FORMAT for a header that is not BGZF (plain gzip without `BC` included).  This is the one function that
+ * cuts a file into appends.
+ *
+ * rfx_text_append_bgzf (replaces runRufus.sh:157-160): host[0, n) must be whole BGZF blocks (rfx_bgzf_scan consumes
+ * exactly n; else RFX_E_FORMAT) whose inflated total fits rfx_text_room (else RFX_E_RANGE, nothing queued).  The
+ * compressed bytes and one descriptor per block go to a staging area the arena owns, on the arena's copy stream; the
+ * kernel runs behind them on a second stream of the arena's, so the inflate of one append overlaps the copy of the next.
+ * The ticket means what rfx_text_append's means (the host buffer is free when rfx_text_copied / rfx_text_wait say so);
+ * rfx_text_bytes counts INFLATED bytes.  Empty blocks (the 28-byte EOF marker) are legal anywhere and add nothing; plain
+ * and BGZF appends may be mixed in one arena.  A block that does not inflate (a refusal of rfx_bgzf_core.h, a CRC
+ * mismatch) writes nothing outside its own ISIZE bytes and makes rfx_text_settle, rfx_text_parse (NULL, *strict == 1)
+ * and rfx_text_fetch fail with RFX_E_FORMAT until the next rfx_text_reset; rfx_last_error() then reads
+ * "rfx_bgzf: block <index in this arena>: <reason>".
+ *
+ * rfx_text_settle (replaces runRufus.sh:157-160: a pipe hands the parser whole lines, BGZF blocks end anywhere): waits
+ * for t's appends, finds the end of the last whole group of four lines, shortens t to it and copies the tail, device to
+ * device, to the front of `next` (which must be empty: RFX_E_INVAL; too small: RFX_E_RANGE); *carried = the tail's bytes.
+ * next == NULL with a tail is RFX_E_FORMAT (a file that ends inside a record).  An arena with fewer than four newlines
+ * carries everything.  Called like parse: from one thread, while nobody appends to t or next.
+ * ------------------------------------------------------------------------------------------- */
+int rfx_bgzf_scan(const void* buf, uint64_t n, uint32_t max_blocks, uint32_t* n_blocks, uint64_t* consumed, uint64_t* inflated);
+long rfx_text_append_bgzf(rfx_text*, const void* host, uint64_t n);
+int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried);
+
 /* Synthetic trio workload (BASELINE.json configs[1]-[4]) -- benchmark and scale-test input,
  * not a replacement of any reference code.  Every base is a pure function of (parameters, pair, mate, base
  * index) -- see rufus_amd/csrc/rfx_synth.h -- so a 30x WGS sample (6.2e8 reads) is generated straight into

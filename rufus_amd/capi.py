@@ -96,6 +96,9 @@ SIGNATURES = {
     "rfx_text_parse": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rfx_text_fetch": (C.c_int, [C.c_void_p, C.c_char_p]),
     "rfx_text_reset": (None, [C.c_void_p]),
+    "rfx_bgzf_scan": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, u32p, u64p, u64p]),
+    "rfx_text_append_bgzf": (C.c_long, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "rfx_text_settle": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
     "rfx_synth_text": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rfx_synth_snv": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_char_p, C.c_char_p]),
     "rfx_synth_genome": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
@@ -301,6 +304,14 @@ def tile_plan(length: int, k: int, tile_len: int = 150):
     return int(nt.value), int(step.value)
 
 
+def bgzf_scan(data: bytes, max_blocks: int = 0xFFFFFFFF):
+    """(n_blocks, consumed, inflated) of ``rfx_bgzf_scan``: the whole BGZF blocks at the front of `data`, the bytes they
+    take and the bytes they inflate to.  An incomplete last block is not an error; a header that is not BGZF is."""
+    nb, used, inf = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().rfx_bgzf_scan(data, len(data), max_blocks, C.byref(nb), C.byref(used), C.byref(inf)), "rfx_bgzf_scan")
+    return int(nb.value), int(used.value), int(inf.value)
+
+
 class PackedReads:
     """Host-side packed block: 32 bases per 64-bit code word, one mask bit per base."""
 
@@ -428,6 +439,25 @@ class TextArena:
             _check(int(t), "rfx_text_append")
         _check(lib().rfx_text_wait(self._h, t), "rfx_text_wait")     # (a bytes object is not pinned and may go away)
         return int(t)
+
+    def append_bgzf(self, data: bytes) -> int:
+        """Whole BGZF blocks, inflated on the device behind the text that is there (rfx_text_append_bgzf)."""
+        t = lib().rfx_text_append_bgzf(self._h, data, len(data))
+        if t < 0:
+            _check(int(t), "rfx_text_append_bgzf")
+        _check(lib().rfx_text_wait(self._h, t), "rfx_text_wait")
+        return int(t)
+
+    def settle(self, next: "TextArena | None" = None) -> int:
+        """Shortens the text to its last whole group of four lines and moves the tail to the front of `next`; the tail's
+        length in bytes (rfx_text_settle)."""
+        carried = C.c_uint64(0)
+        _check(lib().rfx_text_settle(self._h, next._h if next is not None else None, C.byref(carried)), "rfx_text_settle")
+        return int(carried.value)
+
+    @property
+    def bytes(self) -> int:
+        return int(lib().rfx_text_bytes(self._h))
 
     def parse(self, flags: int = PACK_COUNT, min_q: int = 0):
         """The block, or None when the text is not strict 4-line FASTQ."""

@@ -274,9 +274,47 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   const bool text_ok = n_gpu == 1 && nthreads > 1 && !sam_chr && !spool_path && !keep_path;
   const bool device_text = text_ok && getenv("RFX_DEVICE_PARSE") && !getenv("RFX_HOST_PARSE");
   std::unique_ptr<TextIngest> text_ingest;
+  // A bgzip'd FASTQ (a regular file whose first block rfx_bgzf_scan accepts) is inflated, parsed and packed on the device
+  // (rfx_ingest.hpp BgzfIngest; csrc/rfx_bgzf.hip) whether or not RFX_DEVICE_PARSE is set: compressed, the text is ~80
+  // bytes per read over PCIe and the host only reads the file.  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160).
+  // Plain gzip (no `BC` subfield) is not BGZF and goes where it went before.
+  std::unique_ptr<BgzfIngest> bgzf_ingest;
+  auto is_bgzf = [](const Input& in) {
+    if (!in.regular || in.size < 28) return false;
+    std::vector<char> head((size_t)std::min<uint64_t>(in.size, 1u << 16));
+    size_t got = 0;
+    while (got < head.size()) {
+      const ssize_t n = ::pread(in.fd, head.data() + got, head.size() - got, (off_t)got);
+      if (n < 0 && errno == EINTR) continue;
+      if (n <= 0) break;
+      got += (size_t)n;
+    }
+    uint32_t nb = 0;
+    return rfx_bgzf_scan(head.data(), got, 1, &nb, nullptr, nullptr) == RFX_OK && nb == 1;
+  };
   {
     for (Input& in : inputs) {
       bool done = false;
+      if (is_bgzf(in)) {
+        if (n_gpu != 1 || sam_chr || spool_path || keep_path)
+          die("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
+              "--spool, --keep-packed: inflate it and pipe it in");
+        if (!bgzf_ingest) {
+          device_ready();
+          bgzf_ingest.reset(new BgzfIngest(
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, (size_t)1 << 30,
+              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20));
+          trace("count: bgzf route, text arenas open");
+        }
+        void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
+        if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
+        (void)madvise(m, in.size, MADV_SEQUENTIAL);
+        bgzf_ingest->feed_mapped((const char*)m, in.size);
+        munmap(m, in.size);
+        trace(("count: " + bgzf_ingest->counts()).c_str());
+        if (in.fd > 0) ::close(in.fd);
+        continue;
+      }
       if (device_text && in.regular && in.size > 0) {
         if (!text_ingest) {
           device_ready();
@@ -403,6 +441,7 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // beside the device's finish, instead of in front of the first write)
   std::vector<std::pair<char*, size_t>> out_ring;
   std::thread out_ring_pinner;
+  bgzf_ingest.reset();
   if (!ingest && text_ingest) {
     trace(("count: text route, " + text_ingest->timing()).c_str());
     text_ingest.reset();  // (its page-locked text buffers go first)

@@ -1086,4 +1086,159 @@ class TextIngest {
   }
 };
 
+// ---- bgzip'd FASTQ: inflated on the device (rfx_text_append_bgzf; rufus_amd/csrc/rfx_bgzf.hip) -------------------------
+// Replaces `zcat F.fastq.gz | jellyfish count ... /dev/stdin` (runRufus.sh:157-160): the host only reads the file.  One
+// cheap pass over the block headers (rfx_bgzf_scan) cuts the mapped file into runs of whole blocks of at most `piece`
+// compressed bytes; the runs go, IN FILE ORDER (records straddle blocks, so the text must arrive in order), through a
+// ring of page-locked buffers into the arena that is being filled.  BGZF blocks end anywhere: a full arena is cut at its
+// last whole record (rfx_text_settle), the tail moves to the front of the next arena, which is then filled -- its copies
+// and inflate kernels queued, nothing waited for -- BEFORE the settled arena is parsed and counted, so the device
+// inflates the next arena's text beside the count of this one.  Two arenas: one thread feeds, settles, parses and sinks,
+// so a third would never be filled while two are busy.
+// Strict 4-line FASTQ only: the carry rule counts four lines per record, and text the device parser refuses cannot be
+// handed to the host parser arena by arena (an arena's cut would be wrong to begin with).
+// (weak: the host test harness links the executable's source against a stand-in library that has the text arena but no
+// device; there the two are null and BGZF input is refused by the constructor)
+#pragma weak rfx_text_append_bgzf
+#pragma weak rfx_text_settle
+class BgzfIngest {
+  rfx_ctx* ctx_;
+  std::function<void(rfx_reads*)> sink_;
+  size_t piece_;
+  rfx_text* arena_[2] = {nullptr, nullptr};
+  uint64_t arena_bytes_;
+  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
+  std::vector<Buf> ring_;
+  size_t next_buf_ = 0, buf_cap_ = 0;
+  uint64_t blocks_ = 0, arenas_ = 0, reads_ = 0, appends_ = 0;
+
+  [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
+
+  void settle_buf(Buf& b) {
+    if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
+    b.ticket = -1;
+  }
+  void settle_ring_of(rfx_text* t) {  // before an arena is reset: its tickets die with the reset
+    for (Buf& b : ring_)
+      if (b.t == t) settle_buf(b);
+  }
+  void parse_and_sink(rfx_text* t) {
+    if (rfx_text_bytes(t)) {
+      int strict = 1;
+      rfx_reads* r = rfx_text_parse(t, RFX_PACK_COUNT, 0, &strict);
+      if (!r && !strict) not_strict();
+      if (!r) die(std::string("rufus_amd: rfx_text_parse: ") + rfx_last_error());
+      reads_ += rfx_reads_count(r);
+      ++arenas_;
+      sink_(r);
+    }
+    settle_ring_of(t);
+    rfx_text_reset(t);
+  }
+  uint64_t settle(rfx_text* t, rfx_text* next) {
+    uint64_t carried = 0;
+    const int rc = rfx_text_settle(t, next, &carried);
+    if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
+    if (rc == RFX_E_FORMAT || rc == RFX_E_RANGE) not_strict();  // (ends inside a record / a "record" longer than an arena)
+    if (rc != RFX_OK) die(std::string("rufus_amd: rfx_text_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
+    return carried;
+  }
+
+ public:
+  BgzfIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20)
+      : ctx_(ctx), sink_(std::move(sink)), piece_(piece), arena_bytes_(arena_bytes) {
+    if (!rfx_text_append_bgzf || !rfx_text_settle) die("rufus_amd jellyfish count: this library cannot inflate BGZF input");
+    for (rfx_text*& a : arena_) {
+      a = rfx_text_open(ctx_, arena_bytes);
+      if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
+    }
+    buf_cap_ = std::max<size_t>(piece_, 1u << 16);  // (a block is at most 64 KiB)
+    ring_.resize(4);
+    for (Buf& b : ring_) {
+      b.p = (char*)rfx_host_alloc(buf_cap_);
+      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
+    }
+  }
+  ~BgzfIngest() {
+    for (Buf& b : ring_) {
+      settle_buf(b);
+      rfx_host_free(b.p);
+    }
+    for (rfx_text* a : arena_) rfx_text_close(a);
+  }
+  uint64_t reads() const { return reads_; }
+  std::string counts() const {
+    char b[160];
+    snprintf(b, sizeof b, "bgzf route: %llu blocks in %llu appends, %llu arenas, %llu reads", (unsigned long long)blocks_,
+             (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)reads_);
+    return b;
+  }
+
+  // A whole mapped BGZF file.  Dies on a block that is not BGZF or not whole, on text that is not strict 4-line FASTQ
+  // and on a block that does not inflate.
+  void feed_mapped(const char* m, size_t size) {
+    // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of text
+    struct Run { size_t at, n; uint64_t inflated; };
+    std::vector<Run> runs;
+    const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
+    for (size_t at = 0; at < size;) {
+      uint32_t nb = 0;
+      uint64_t used = 0, inf = 0;
+      int rc = rfx_bgzf_scan(m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
+      if (nb == 0) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "rufus_amd jellyfish count: %s BGZF block at byte %llu of the compressed input",
+                 rc == RFX_OK ? "truncated" : "no", (unsigned long long)at);
+        die(msg);
+      }
+      runs.push_back({at, (size_t)used, inf});
+      blocks_ += nb;
+      at += (size_t)used;
+    }
+    int cur = 0;
+    size_t i = 0;
+    // queues runs into arena `a` until the next does not fit (false: the file is at its end)
+    auto fill = [&](rfx_text* a) {
+      for (; i < runs.size(); ++i) {
+        const Run& r = runs[i];
+        if (r.inflated > arena_bytes_) not_strict();  // (cannot happen: a run inflates to <= a quarter of an arena)
+        if (r.inflated > rfx_text_room(a)) return true;
+        Buf& b = ring_[next_buf_];
+        next_buf_ = (next_buf_ + 1) % ring_.size();
+        settle_buf(b);
+        memcpy(b.p, m + r.at, r.n);
+        const long tk = rfx_text_append_bgzf(a, b.p, r.n);
+        if (tk < 0) die(std::string("rufus_amd: rfx_text_append_bgzf: ") + rfx_strerror((int)tk) + " " + rfx_last_error());
+        b.t = a;
+        b.ticket = tk;
+        ++appends_;
+      }
+      return false;
+    };
+    bool more = fill(arena_[cur]);
+    while (more) {
+      rfx_text* t = arena_[cur];
+      rfx_text* nx = arena_[cur ^ 1];
+      const uint64_t before = rfx_text_bytes(t);
+      const uint64_t carried = settle(t, nx);
+      if (carried == before) not_strict();  // a full arena without one whole record
+      more = fill(nx);       // queued, not waited for: the device inflates it beside this arena's count
+      parse_and_sink(t);
+      cur ^= 1;
+    }
+    // the last arena; a file without a final newline gets one
+    rfx_text* t = arena_[cur];
+    rfx_text* nx = arena_[cur ^ 1];
+    if (settle(t, nx)) {
+      const long tk = rfx_text_append(nx, "\n", 1);
+      if (tk < 0 || rfx_text_wait(nx, tk) != RFX_OK) die(std::string("rufus_amd: rfx_text_append: ") + rfx_last_error());
+      parse_and_sink(t);
+      (void)settle(nx, nullptr);
+      parse_and_sink(nx);
+    } else {
+      parse_and_sink(t);
+    }
+  }
+};
+
 }  // namespace rfxcli

@@ -18,6 +18,7 @@
 
 #include "../../include/rufus_hip.h"
 #include "rfx_synth.h"
+#include "rfx_bgzf_core.h"
 
 namespace {
 
@@ -172,6 +173,28 @@ const char* rfx_strerror(int code) {
     case RFX_E_FORMAT: return "malformed input";
     default: return "unknown error";
   }
+}
+
+// The one place a BGZF file is cut: the library's append, the executables and the tests all call this.
+int rfx_bgzf_scan(const void* buf, uint64_t n, uint32_t max_blocks, uint32_t* n_blocks, uint64_t* consumed, uint64_t* inflated) {
+  if (!buf && n) return RFX_E_INVAL;
+  const uint8_t* b = (const uint8_t*)buf;
+  uint64_t at = 0, inf = 0;
+  uint32_t nb = 0;
+  int rc = RFX_OK;
+  while (nb < max_blocks && at < n) {
+    uint32_t bsize, pay_off, pay_len, isize, crc;
+    const int h = bgzf_block_header(b + at, n - at, &bsize, &pay_off, &pay_len, &isize, &crc);
+    if (h < 0) rc = RFX_E_FORMAT;
+    if (h != 0) break;  // (1: the block is not whole -- no error, `consumed` says where)
+    at += bsize;
+    inf += isize;
+    ++nb;
+  }
+  if (n_blocks) *n_blocks = nb;
+  if (consumed) *consumed = at;
+  if (inflated) *inflated = inf;
+  return rc;
 }
 
 int rfx_jf_matrix(int lsize, int k, uint64_t* cols) {

@@ -530,6 +530,10 @@ void leaf(rfx_ctx*, const uint64_t* const* seg_inst, const uint64_t* const* seg_
           const uint64_t* tmp_start, uint64_t* tmp_w, uint32_t* tmp_counts, uint64_t* n_surv, unsigned int* err);
 void split_bins(rfx_ctx*, uint64_t* bs, uint32_t P, uint64_t n_own, uint64_t* bs2);
 void scan_tail(rfx_ctx*, uint64_t* v, uint64_t n);  // exclusive scan in place, v[n] = total
+// k_bgzf_inflate (rfx_bgzf.hip) on `stream`: block i of desc[0 .. n_blocks) from stage + in_off to arena + out_off,
+// status[i] = its bgzf_status, *first_bad = min(*first_bad, first_index + i) for a block that failed
+void bgzf_inflate(rfx_ctx*, hipStream_t stream, const uint8_t* stage, const struct bgzf_desc* desc, uint32_t n_blocks,
+                  uint32_t first_index, uint8_t* arena, uint32_t* status, uint32_t* first_bad);
 void leaf_compact(rfx_ctx*, const uint64_t* tmp_w, const uint32_t* tmp_counts, const uint64_t* tmp_start,
                   const uint64_t* out_off, uint32_t P, const uint64_t* lut_inv, int ntab, int sel_bits,
                   uint64_t* out_keys, uint32_t* out_counts, uint64_t* out_pos);
@@ -553,13 +557,15 @@ rfx_reads* reads_select_dev(rfx_ctx*, const rfx_reads* const* blocks, const uint
                             const char* who);
 }  // namespace rfxi
 
-// Launch bracket: records a HIP-event span on the ctx stream when profiling is on.
+// Launch bracket: records a HIP-event span on the ctx stream (or `stream`: an arena's own, rfx_text.hip) when profiling
+// is on.
 struct rfx_span {
   rfx_ctx* c;
+  hipStream_t st;
   rfx_prof_span s;
   bool on;
-  rfx_span(rfx_ctx* ctx, const char* name)
-      : c(ctx),
+  rfx_span(rfx_ctx* ctx, const char* name, hipStream_t stream = nullptr)
+      : c(ctx), st(stream ? stream : ctx->stream),
         on(ctx->prof && (ctx->prof_filter.empty() ||
                          ctx->prof_filter.find(std::string(",") + name + ",") != std::string::npos)) {
     if (on) {
@@ -573,12 +579,12 @@ struct rfx_span {
       };
       get(s.e0);
       get(s.e1);
-      (void)hipEventRecord(s.e0, c->stream);
+      (void)hipEventRecord(s.e0, st);
     }
   }
   ~rfx_span() {
     if (on) {
-      (void)hipEventRecord(s.e1, c->stream);
+      (void)hipEventRecord(s.e1, st);
       c->spans.push_back(s);
     }
   }

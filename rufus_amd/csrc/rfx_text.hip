@@ -20,12 +20,19 @@
 // rfx_text_parse report "not strict" and the caller parses that text on the host, as before (rfx_text_fetch hands it
 // back): the device path never guesses.  Two waits per block (line count, then word count): ~50 us against the 20 ms a
 // gigabyte of text takes over PCIe.
+//
+// bgzip'd text (rfx_text_append_bgzf, replaces runRufus.sh:157-160's `zcat`): the compressed blocks are copied to a staging
+// area of the arena and k_bgzf_inflate (rfx_bgzf.hip) writes their text into the arena; BGZF blocks end anywhere, so
+// rfx_text_settle cuts the arena at its last whole group of four lines (k_txt_count again, then k_txt_nth finds the byte
+// behind newline number 4 * floor(N / 4)) and carries the tail into the next arena.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
+#include "rfx_bgzf_core.h"
 #include "rfx_internal.h"
 
 using rfxi::dfree;
@@ -111,6 +118,46 @@ __global__ __launch_bounds__(TX_BLOCK) void k_txt_lines(const uint4* __restrict_
   }
 }
 
+// *cut = the byte offset behind newline number `want` (1-based, want <= the text's newlines): ONE workgroup; tile_off is
+// the exclusive scan of k_txt_count's counts (tile_off[n_tiles] = all newlines).
+__global__ __launch_bounds__(TX_BLOCK) void k_txt_nth(const uint4* __restrict__ text, uint64_t n_tiles,
+                                                       const uint64_t* __restrict__ tile_off, uint64_t want,
+                                                       uint64_t* __restrict__ cut) {
+  __shared__ uint32_t s_wave[TX_BLOCK / 64];
+  uint64_t lo = 0, hi = n_tiles;  // the tile with tile_off[tile] < want <= tile_off[tile + 1]
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) / 2;
+    if (tile_off[mid] < want) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t tile = lo;
+  const uint4 v = text[tile * (TX_TILE / 16) + threadIdx.x];
+  const uint32_t b[4] = {nl_bits(v.x), nl_bits(v.y), nl_bits(v.z), nl_bits(v.w)};
+  const uint32_t c = __popc(b[0]) + __popc(b[1]) + __popc(b[2]) + __popc(b[3]);
+  uint32_t incl = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, 64);
+    if ((int)(threadIdx.x & 63u) >= d) incl += up;
+  }
+  if ((threadIdx.x & 63u) == 63u) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t before = incl - c;
+  for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += s_wave[w];
+  uint64_t rank = tile_off[tile] + before;  // newlines in front of this thread's 16 bytes
+  if (rank < want && want <= rank + c) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t m = b[q];
+      while (m) {
+        const int bit = __ffs((int)m) - 1;  // 7, 15, 23, 31
+        m &= m - 1u;
+        if (++rank == want) *cut = tile * TX_TILE + threadIdx.x * 16u + (uint32_t)q * 4u + (uint32_t)(bit >> 3) + 1u;
+      }
+    }
+  }
+}
+
 // rfx_pack_reads' tables (rfx_host.cpp PackLut): jellyfish code of either case / RUFUS code of upper case only
 __device__ __forceinline__ bool is_acgt_upper(uint32_t ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
 __device__ __forceinline__ uint32_t base_code(uint32_t ch) {  // of an A/C/G/T in either case: A0 C1 G2 T3
@@ -193,7 +240,68 @@ struct rfx_text {
   // reset -- whose copy is long done: the reset follows the parse -- must find an event, not freed memory.
   std::vector<hipEvent_t> ev;
   size_t n_ev = 0;
+  // ---- BGZF appends (rfx_text_append_bgzf) ----
+  // The kernel runs on a second stream behind the append's copies (an event between them), so the inflate of one append
+  // overlaps the copy of the next; whoever reads the arena synchronises with both streams first (bgzf_check).
+  hipStream_t kern = nullptr;
+  hipEvent_t staged = nullptr;
+  // Staging: compressed bytes + 8 bytes of padding, descriptors and status words of every append since the reset, bump-
+  // allocated from chunks that are kept across resets (one chunk once the first arena's worth has been seen).
+  struct stage_chunk { uint8_t* p; size_t cap, used; };
+  std::vector<stage_chunk> stage;
+  struct bgzf_append { uint32_t first, n; uint32_t* status; };
+  std::vector<bgzf_append> bgzf;               // this generation's BGZF appends: block indices [first, first + n)
+  std::vector<std::vector<bgzf_desc>> descs;   // (their descriptors: the host side of an asynchronous copy)
+  uint32_t n_bgzf_blocks = 0;
+  uint32_t* first_bad = nullptr;  // device: the lowest index of a block that failed, or ~0
+  bool bgzf_failed = false;
+  std::string bgzf_msg;
 };
+
+namespace {
+
+uint8_t* stage_alloc(rfx_text* t, size_t bytes) {  // (t->mu held) 16-byte aligned
+  bytes = (bytes + 15) & ~(size_t)15;
+  for (auto& ch : t->stage)
+    if (ch.cap - ch.used >= bytes) {
+      uint8_t* p = ch.p + ch.used;
+      ch.used += bytes;
+      return p;
+    }
+  // a chunk holds what a quarter of the arena deflates to at 4 : 1 several times over; a bigger append gets its own
+  const size_t cap = std::max<size_t>(bytes, std::min<size_t>((size_t)t->cap / 4 + (1u << 20), (size_t)256 << 20));
+  uint8_t* p = nullptr;
+  if (hipMalloc((void**)&p, cap) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  t->stage.push_back({p, cap, bytes});
+  return p;
+}
+
+// RFX_OK, or RFX_E_FORMAT with "rfx_bgzf: block <index in this arena>: <reason>" as the error text: a block appended
+// since the last reset did not inflate.  Waits for the arena's copies and kernels.
+int bgzf_check(rfx_text* t) {
+  if (!t->n_bgzf_blocks) return RFX_OK;
+  if (!t->bgzf_failed) {
+    HIPCHK(hipStreamSynchronize(t->copy));
+    HIPCHK(hipStreamSynchronize(t->kern));
+    uint32_t bad = ~0u;
+    HIPCHK(hipMemcpy(&bad, t->first_bad, 4, hipMemcpyDeviceToHost));
+    if (bad == ~0u) return RFX_OK;
+    uint32_t st = 0;
+    for (const auto& a : t->bgzf)
+      if (bad >= a.first && bad - a.first < a.n) HIPCHK(hipMemcpy(&st, a.status + (bad - a.first), 4, hipMemcpyDeviceToHost));
+    char msg[160];
+    snprintf(msg, sizeof msg, "rfx_bgzf: block %u: %s", bad, bgzf_status_text(st));
+    t->bgzf_msg = msg;
+    t->bgzf_failed = true;
+  }
+  rfxi::set_error(t->bgzf_msg.c_str());
+  return RFX_E_FORMAT;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -224,6 +332,13 @@ void rfx_text_close(rfx_text* t) {
   if (!t) return;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->copy);
+  if (t->kern) {
+    (void)hipStreamSynchronize(t->kern);
+    (void)hipStreamDestroy(t->kern);
+    (void)hipEventDestroy(t->staged);
+    (void)hipFree(t->first_bad);
+  }
+  for (auto& ch : t->stage) (void)hipFree(ch.p);
   for (hipEvent_t e : t->ev) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(t->copy);
   if (t->vmm) dfree(t->ctx, t->arena);
@@ -284,6 +399,7 @@ int rfx_text_fetch(rfx_text* t, void* host) {
   rfx_ctx* c = t->ctx;
   (void)hipSetDevice(c->device);
   HIPCHK(hipStreamSynchronize(t->copy));
+  if (const int rc = bgzf_check(t)) return rc;
   if (t->used) HIPCHK(hipMemcpyAsync(host, t->arena, t->used, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(ctx_sync(c));
   return RFX_OK;
@@ -293,9 +409,171 @@ void rfx_text_reset(rfx_text* t) {
   if (!t) return;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->copy);
+  if (t->kern) (void)hipStreamSynchronize(t->kern);
   std::lock_guard<std::mutex> g(t->mu);
   t->n_ev = 0;
   t->used = 0;
+  if (t->n_bgzf_blocks) {
+    if (t->stage.size() > 1) {  // one chunk of the size that was needed, next time
+      size_t all = 0;
+      for (auto& ch : t->stage) { all += ch.used; (void)hipFree(ch.p); }
+      t->stage.clear();
+      uint8_t* p = nullptr;
+      if (hipMalloc((void**)&p, all) == hipSuccess) t->stage.push_back({p, all, 0});
+      else (void)hipGetLastError();
+    }
+    for (auto& ch : t->stage) ch.used = 0;
+    t->bgzf.clear();
+    t->descs.clear();
+    t->n_bgzf_blocks = 0;
+    t->bgzf_failed = false;
+    (void)hipMemset(t->first_bad, 0xFF, 4);
+  }
+}
+
+long rfx_text_append_bgzf(rfx_text* t, const void* host, uint64_t n) {
+  if (!t || (!host && n)) return RFX_E_INVAL;
+  rfx_ctx* c = t->ctx;
+  (void)hipSetDevice(c->device);
+  uint32_t nb = 0;
+  uint64_t consumed = 0, inflated = 0;
+  const int src = rfx_bgzf_scan(host, n, 0xFFFFFFFFu, &nb, &consumed, &inflated);
+  if (src != RFX_OK || consumed != n) {
+    rfxi::set_error("rfx_text_append_bgzf: not a run of whole BGZF blocks");
+    return RFX_E_FORMAT;
+  }
+  std::lock_guard<std::mutex> g(t->mu);
+  if (inflated > t->cap - t->used || (uint64_t)t->n_bgzf_blocks + nb > 0xFFFFFFF0ull) return RFX_E_RANGE;
+  if (!t->kern) {
+    if (hipStreamCreateWithFlags(&t->kern, hipStreamNonBlocking) != hipSuccess) { t->kern = nullptr; return hip_fail(hipGetLastError(), "rfx_text_append_bgzf"); }
+    hipError_t e = hipEventCreateWithFlags(&t->staged, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->first_bad, 4);
+    if (e == hipSuccess) e = hipMemset(t->first_bad, 0xFF, 4);
+    if (e != hipSuccess) return hip_fail(e, "rfx_text_append_bgzf");
+  }
+  if (t->n_ev == t->ev.size()) {
+    hipEvent_t e;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return RFX_E_HIP;
+    t->ev.push_back(e);
+  }
+  // descriptors: every block's payload inside the staged bytes, its text inside the arena's room (checked above)
+  t->descs.emplace_back(nb);
+  std::vector<bgzf_desc>& ds = t->descs.back();
+  const uint8_t* b = (const uint8_t*)host;
+  uint64_t at = 0, out = t->used;
+  for (uint32_t i = 0; i < nb; ++i) {
+    uint32_t bsize, pay_off, pay_len, isize, crc;
+    (void)bgzf_block_header(b + at, n - at, &bsize, &pay_off, &pay_len, &isize, &crc);  // (the scan accepted it)
+    ds[i] = bgzf_desc{at + pay_off, out, pay_len, isize, crc, 0};
+    at += bsize;
+    out += isize;
+  }
+  // (a failure below gives back what this call took: the descriptors and the staging bytes)
+  std::vector<size_t> marks;
+  for (const auto& ch : t->stage) marks.push_back(ch.used);
+  auto undo = [&] {
+    while (t->stage.size() > marks.size()) {
+      (void)hipFree(t->stage.back().p);
+      t->stage.pop_back();
+    }
+    for (size_t i = 0; i < marks.size(); ++i) t->stage[i].used = marks[i];
+    t->descs.pop_back();
+  };
+  uint8_t* d_in = nb ? stage_alloc(t, (size_t)n + 8) : nullptr;  // 8 bytes of padding behind the compressed bytes
+  bgzf_desc* d_desc = nb ? (bgzf_desc*)stage_alloc(t, (size_t)nb * sizeof(bgzf_desc)) : nullptr;
+  uint32_t* d_status = nb ? (uint32_t*)stage_alloc(t, (size_t)nb * 4) : nullptr;
+  if (nb && (!d_in || !d_desc || !d_status)) {
+    undo();
+    rfxi::set_error("rfx_text_append_bgzf: no device memory for the staging area");
+    return RFX_E_NOMEM;
+  }
+  hipError_t rc = hipSuccess;
+  if (nb) {  // (the spans: rfx_prof_* from ONE appending thread, as the measurement scripts do)
+    rfx_span sp(c, "bgzf_copy", t->copy);
+    rc = hipMemcpyAsync(d_in, host, n, hipMemcpyHostToDevice, t->copy);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(d_desc, ds.data(), (size_t)nb * sizeof(bgzf_desc), hipMemcpyHostToDevice, t->copy);
+  }
+  if (rc == hipSuccess) rc = hipEventRecord(t->ev[t->n_ev], t->copy);  // the host buffer is free
+  if (rc == hipSuccess && nb) {
+    rc = hipEventRecord(t->staged, t->copy);
+    if (rc == hipSuccess) rc = hipStreamWaitEvent(t->kern, t->staged, 0);
+    if (rc == hipSuccess) {
+      rfx_span sp(c, "k_bgzf_inflate", t->kern);
+      rfxk::bgzf_inflate(c, t->kern, d_in, d_desc, nb, t->n_bgzf_blocks, t->arena, d_status, t->first_bad);
+      rc = hipGetLastError();
+    }
+  }
+  if (rc != hipSuccess) {
+    // (what was queued before the failing call may still read the staging bytes: they are handed out again only after
+    // the streams have drained)
+    (void)hipStreamSynchronize(t->copy);
+    (void)hipStreamSynchronize(t->kern);
+    undo();
+    return hip_fail(rc, "rfx_text_append_bgzf");
+  }
+  if (nb) {
+    t->bgzf.push_back({t->n_bgzf_blocks, nb, d_status});
+    t->n_bgzf_blocks += nb;
+  }
+  t->used += inflated;
+  return (long)t->n_ev++;
+}
+
+int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried) {
+  if (!t || !carried || next == t) return RFX_E_INVAL;
+  *carried = 0;
+  if (next && (next->used != 0 || next->ctx != t->ctx)) return RFX_E_INVAL;
+  rfx_ctx* c = t->ctx;
+  (void)hipSetDevice(c->device);
+  HIPCHK(hipStreamSynchronize(t->copy));
+  if (t->kern) HIPCHK(hipStreamSynchronize(t->kern));
+  if (const int rc = bgzf_check(t)) return rc;
+  const uint64_t n = t->used;
+  if (n == 0) return RFX_OK;
+  HIPCHK(hipMemsetAsync(t->arena + n, 0, 2 * TX_TILE, c->stream));  // whole tiles are read, as in rfx_text_parse
+  const uint64_t n_tiles = (n + TX_TILE - 1) / TX_TILE;
+  uint64_t* tile_off = (uint64_t*)dmalloc(c, (n_tiles + 2) * 8);  // [n_tiles + 1]: the cut
+  if (!tile_off) return RFX_E_NOMEM;
+  const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8);
+  {
+    rfx_span sp(c, "k_txt_count");
+    hipLaunchKernelGGL(k_txt_count, dim3(grid), dim3(TX_BLOCK), 0, c->stream, (const uint4*)t->arena, n_tiles, tile_off);
+  }
+  rfxk::scan_tail(c, tile_off, n_tiles);
+  uint64_t n_lines = 0, cut = 0;
+  hipError_t e = queue_read(c, &n_lines, tile_off + n_tiles, 8);
+  if (e == hipSuccess) e = ctx_sync(c);
+  const uint64_t want = n_lines & ~3ull;  // newline number 4 * floor(N / 4) ends the last whole record
+  if (e == hipSuccess && want) {
+    {
+      rfx_span sp(c, "k_txt_nth");
+      hipLaunchKernelGGL(k_txt_nth, dim3(1), dim3(TX_BLOCK), 0, c->stream, (const uint4*)t->arena, n_tiles, tile_off, want,
+                         tile_off + n_tiles + 1);
+    }
+    e = queue_read(c, &cut, tile_off + n_tiles + 1, 8);
+    if (e == hipSuccess) e = ctx_sync(c);
+  }
+  dfree(c, tile_off);
+  if (e != hipSuccess) return hip_fail(e, "rfx_text_settle");
+  if (cut > n) {
+    rfxi::set_error("rfx_text_settle: the cut lies behind the text");
+    return RFX_E_HIP;
+  }
+  const uint64_t tail = n - cut;
+  if (tail) {
+    if (!next) {
+      rfxi::set_error("rfx_text_settle: the text ends inside a record");
+      return RFX_E_FORMAT;
+    }
+    if (tail > next->cap) return RFX_E_RANGE;
+    HIPCHK(hipMemcpyAsync(next->arena, t->arena + cut, tail, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(ctx_sync(c));
+    std::lock_guard<std::mutex> g(next->mu);
+    next->used = tail;
+  }
+  t->used = cut;
+  *carried = tail;
+  return RFX_OK;
 }
 
 rfx_reads* rfx_text_parse(rfx_text* t, int flags, int min_q, int* strict) {
@@ -309,10 +587,12 @@ rfx_reads* rfx_text_parse(rfx_text* t, int flags, int min_q, int* strict) {
     return nullptr;
   };
   if (n == 0) return not_strict();
+  if (bgzf_check(t) != RFX_OK) return nullptr;  // (an arena that never saw a BGZF append: nothing happens here)
   {  // the ctx stream waits for the copies (they ran on the arena's own stream)
     std::lock_guard<std::mutex> g(t->mu);
     if (t->n_ev && hipStreamWaitEvent(c->stream, t->ev[t->n_ev - 1], 0) != hipSuccess) return nullptr;
   }
+  // (BGZF appends: bgzf_check above has waited for their kernels)
   // whole tiles are read: what lies behind the text holds no newline
   if (hipMemsetAsync(t->arena + n, 0, 2 * TX_TILE, c->stream) != hipSuccess) return nullptr;
   const uint64_t n_tiles = (n + TX_TILE - 1) / TX_TILE;
