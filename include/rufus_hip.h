@@ -150,6 +150,9 @@ void rfx_reads_free(rfx_reads*);
 uint32_t rfx_reads_count(const rfx_reads*);
 uint64_t rfx_reads_bases(const rfx_reads*);
 uint64_t rfx_reads_words(const rfx_reads*);
+/* Reads of the block that are exactly `len` bases long, for len < 32 (kept with the block since it was made; 0 for len
+ * >= 32).  len = 0: the empty sequence lines the paired filter rejects (src/RUFUS.Filter.cpp:203 reads length() - 1). */
+uint64_t rfx_reads_of_length(const rfx_reads*, uint32_t len);
 /* D2H copy of a block's arrays (sized by rfx_reads_words / rfx_reads_count; any pointer may be NULL). */
 int rfx_reads_get(const rfx_reads*, uint64_t* codes, uint32_t* acgt, uint32_t* good, uint32_t* word_off, uint32_t* len);
 
@@ -251,6 +254,35 @@ void rfx_text_reset(rfx_text*);
 int rfx_bgzf_scan(const void* buf, uint64_t n, uint32_t max_blocks, uint32_t* n_blocks, uint64_t* consumed, uint64_t* inflated);
 long rfx_text_append_bgzf(rfx_text*, const void* host, uint64_t n);
 int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried);
+
+/* -------------------------------------------------------------------------------------------
+ * Two bgzip'd mate files in lock step, and the text of the hit records gathered on the device
+ * Replaces the two host inflaters in front of the filter, `RUFUS.Filter HashList <(zcat A) <(zcat B) ...`
+ * (runRufus.sh:974-977), and, for text that exists only in HBM, the write loop of src/RUFUS.Filter.cpp after :196-277.
+ *
+ * rfx_text_records (replaces the `getline` x 4 count of src/RUFUS.Filter.cpp:165-173 as the measure of what an arena
+ * holds): waits for t's appends as rfx_text_settle does and reports floor(N / 4) for the arena's N newlines.  Changes
+ * nothing.  RFX_E_FORMAT for a BGZF block that did not inflate.
+ *
+ * rfx_text_settle_records (replaces the lock step of src/RUFUS.Filter.cpp:165-173: record i of file 1 with record i of
+ * file 2): rfx_text_settle with the cut behind newline number 4 * min(floor(N / 4), max_records); *records = that
+ * minimum.  Two arenas filled from two files hold different numbers of whole records: both are cut at the smaller
+ * number.  max_records == 0 carries everything.  Preconditions and error codes are rfx_text_settle's.
+ *
+ * rfx_text_gather (replaces the output loop of src/RUFUS.Filter.cpp:237-277 on lines the host no longer has): for every
+ * set bit r < n_records of hitmask (host memory, ceil(n_records / 64) words; bits at and above n_records are ignored),
+ * ascending, the arena's bytes from the beginning of line 4r to the beginning of line 4r + 4, as they are ('\r'
+ * included), concatenated, to host_out.  "Four lines per record" is all it asks of the text.  The arena must hold exactly
+ * n_records whole records -- 4 * n_records newlines, the last byte a newline -- else RFX_E_INVAL.  *bytes = the bytes the
+ * selection has, *n_selected (may be NULL) its records; cap too small: RFX_E_RANGE with *bytes set and nothing written.
+ * Works before or after rfx_text_parse on the same arena (it finds the lines itself), until rfx_text_reset.  One wait
+ * for the device between the mask upload and the copy of the result.  Called like parse: from one thread, while nobody
+ * appends.
+ * ------------------------------------------------------------------------------------------- */
+int rfx_text_records(rfx_text* t, uint64_t* records);
+int rfx_text_settle_records(rfx_text* t, rfx_text* next, uint64_t max_records, uint64_t* records, uint64_t* carried);
+int rfx_text_gather(rfx_text* t, const uint64_t* hitmask, uint64_t n_records, void* host_out, uint64_t cap, uint64_t* bytes,
+                    uint64_t* n_selected);
 
 /* Synthetic trio workload (BASELINE.json configs[1]-[4]) -- benchmark and scale-test input,
  * not a replacement of any reference code.  Every base is a pure function of (parameters, pair, mate, base

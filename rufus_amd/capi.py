@@ -99,6 +99,10 @@ SIGNATURES = {
     "rfx_bgzf_scan": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, u32p, u64p, u64p]),
     "rfx_text_append_bgzf": (C.c_long, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "rfx_text_settle": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
+    "rfx_text_records": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_text_settle_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p]),
+    "rfx_text_gather": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]),
+    "rfx_reads_of_length": (C.c_uint64, [C.c_void_p, C.c_uint32]),
     "rfx_synth_text": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rfx_synth_snv": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_char_p, C.c_char_p]),
     "rfx_synth_genome": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
@@ -454,6 +458,42 @@ class TextArena:
         carried = C.c_uint64(0)
         _check(lib().rfx_text_settle(self._h, next._h if next is not None else None, C.byref(carried)), "rfx_text_settle")
         return int(carried.value)
+
+    def records(self) -> int:
+        """Whole records (groups of four lines) the arena holds (rfx_text_records)."""
+        n = C.c_uint64(0)
+        _check(lib().rfx_text_records(self._h, C.byref(n)), "rfx_text_records")
+        return int(n.value)
+
+    def settle_records(self, next: "TextArena | None", max_records: int):
+        """settle() with the cut behind record min(records(), max_records): (records kept, bytes carried)
+        (rfx_text_settle_records)."""
+        rec, carried = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rfx_text_settle_records(self._h, next._h if next is not None else None, max_records, C.byref(rec),
+                                             C.byref(carried)), "rfx_text_settle_records")
+        return int(rec.value), int(carried.value)
+
+    def gather_into(self, mask: np.ndarray, n_records: int, out: np.ndarray, cap: "int | None" = None):
+        """rfx_text_gather into `out` (uint8; cap: what the call is told the buffer holds, default all of it):
+        (return code, bytes, records selected).  E_RANGE: bytes = the need, nothing written."""
+        mask = np.ascontiguousarray(mask, dtype=np.uint64)
+        if len(mask) < (n_records + 63) // 64:
+            raise ValueError("mask too short")
+        nb, ns = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().rfx_text_gather(self._h, _p(mask, u64p) if len(mask) else None, n_records, out.ctypes.data_as(C.c_void_p),
+                                   len(out) if cap is None else cap, C.byref(nb), C.byref(ns))
+        return int(rc), int(nb.value), int(ns.value)
+
+    def gather(self, mask: np.ndarray, n_records: int) -> bytes:
+        """The text of the records whose bit is set in `mask` (uint64 words), in order, as it lies in the arena; the arena
+        must hold exactly n_records whole records."""
+        out = np.zeros(1, np.uint8)
+        rc, nb, _ = self.gather_into(mask, n_records, out, cap=0)
+        if rc == E_RANGE:
+            out = np.zeros(nb, np.uint8)
+            rc, nb, _ = self.gather_into(mask, n_records, out)
+        _check(rc, "rfx_text_gather")
+        return out[:nb].tobytes()
 
     @property
     def bytes(self) -> int:

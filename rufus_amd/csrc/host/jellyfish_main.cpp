@@ -279,23 +279,10 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // bytes per read over PCIe and the host only reads the file.  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160).
   // Plain gzip (no `BC` subfield) is not BGZF and goes where it went before.
   std::unique_ptr<BgzfIngest> bgzf_ingest;
-  auto is_bgzf = [](const Input& in) {
-    if (!in.regular || in.size < 28) return false;
-    std::vector<char> head((size_t)std::min<uint64_t>(in.size, 1u << 16));
-    size_t got = 0;
-    while (got < head.size()) {
-      const ssize_t n = ::pread(in.fd, head.data() + got, head.size() - got, (off_t)got);
-      if (n < 0 && errno == EINTR) continue;
-      if (n <= 0) break;
-      got += (size_t)n;
-    }
-    uint32_t nb = 0;
-    return rfx_bgzf_scan(head.data(), got, 1, &nb, nullptr, nullptr) == RFX_OK && nb == 1;
-  };
   {
     for (Input& in : inputs) {
       bool done = false;
-      if (is_bgzf(in)) {
+      if (is_bgzf(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
         if (n_gpu != 1 || sam_chr || spool_path || keep_path)
           die("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
               "--spool, --keep-packed: inflate it and pipe it in");

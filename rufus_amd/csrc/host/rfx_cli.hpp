@@ -610,6 +610,22 @@ inline void drop_mapped(const char* b, const char* e) {
   if (hi > lo) (void)madvise((void*)lo, (size_t)(hi - lo), MADV_DONTNEED);
 }
 
+// Is the open file bgzip'd?  A regular file of `size` bytes whose first block rfx_bgzf_scan accepts (plain gzip has no
+// `BC` subfield and is not).  What sends an input down the device-inflate routes of `jellyfish count` and `RUFUS.Filter`.
+inline bool is_bgzf(int fd, bool regular, uint64_t size) {
+  if (!regular || size < 28) return false;
+  std::vector<char> head((size_t)std::min<uint64_t>(size, 1u << 16));
+  size_t got = 0;
+  while (got < head.size()) {
+    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
+    if (n < 0 && errno == EINTR) continue;
+    if (n <= 0) break;
+    got += (size_t)n;
+  }
+  uint32_t nb = 0;
+  return rfx_bgzf_scan(head.data(), got, 1, &nb, nullptr, nullptr) == RFX_OK && nb == 1;
+}
+
 // RFX_CLI_TRACE=1: wall-clock marks of a tool's phases on stderr (scratch/cli_scale.sh reads them)
 inline void trace(const char* what) {
   static const bool on = getenv("RFX_CLI_TRACE") != nullptr;

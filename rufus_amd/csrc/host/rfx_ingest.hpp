@@ -1241,4 +1241,249 @@ class BgzfIngest {
   }
 };
 
+// ---- two bgzip'd mate files in lock step: inflated, parsed, filtered and the hit pairs' text gathered on the device -------
+// Replaces `RUFUS.Filter HashList <(zcat A) <(zcat B) STUB ...` (runRufus.sh:974-977): the host reads the two files and
+// writes the pulled records, nothing else.  Record i of A pairs with record i of B (src/RUFUS.Filter.cpp:165-173), but
+// BGZF blocks end anywhere and the mates' lines differ in length, so two full arenas hold different numbers of whole
+// records.  Two arenas per mate; one thread feeds (BgzfIngest's run rule), and a STEP is
+//   fill A[cur], B[cur]                      until the next run does not fit or the file ends
+//   R = min(records(A[cur]), records(B[cur]))                                              rfx_text_records
+//   cut both behind record R, the rest moves to the front of A[cur ^ 1], B[cur ^ 1]        rfx_text_settle_records
+//   fill A[cur ^ 1], B[cur ^ 1]              queued, not waited for: inflated beside what follows
+//   parse both (RFX_PACK_FILTER), filter both, OR the two masks            (a pair is pulled when either mate was hit)
+//   gather the OR'd records' text of both arenas into page-locked memory                  rfx_text_gather
+//   hand the two runs of bytes to the sink, reset A[cur], B[cur], cur ^= 1
+// Every step takes at least one record off both mates or ends the run, so the loop ends.
+// The end of a file: one '\n' is appended behind its last run.  A file that ended with a newline then ends with one blank
+// line, a file that did not ends as it should: what is left of mate 1 behind its last whole record must be that one byte
+// or nothing -- anything else is a file that ends inside a record.  Mate 1 at its end ends the run (what mate 2 still
+// holds is ignored, as src/RUFUS.Filter.cpp:165 stops at the end of file 1); mate 2 at its end with records of mate 1
+// left is refused -- the text route's records of empty lines for the missing mates are not reproduced.
+// (weak, as above: tests/host/filter_sam_harness.cpp links the executable's source against a stand-in without a text arena)
+#pragma weak rfx_text_open
+#pragma weak rfx_text_close
+#pragma weak rfx_text_room
+#pragma weak rfx_text_bytes
+#pragma weak rfx_text_append
+#pragma weak rfx_text_wait
+#pragma weak rfx_text_reset
+#pragma weak rfx_text_parse
+#pragma weak rfx_text_records
+#pragma weak rfx_text_settle_records
+#pragma weak rfx_text_gather
+#pragma weak rfx_reads_of_length
+class BgzfPairFilter {
+ public:
+  // (mate 1's bytes, mate 2's bytes, pairs of this step, pairs pulled)
+  using Sink = std::function<void(const char*, size_t, const char*, size_t, uint64_t, uint64_t)>;
+
+ private:
+  rfx_ctx* ctx_;
+  rfx_set* set_;
+  int min_q_, thresh_;
+  Sink sink_;
+  size_t piece_;
+  uint64_t arena_bytes_;
+  struct Run { size_t at, n; uint64_t inflated; };
+  struct Mate {
+    const char* m = nullptr;
+    std::vector<Run> runs;
+    size_t i = 0;         // the next run to queue
+    bool closed = false;  // every run is queued and the final newline lies behind them
+    rfx_text* arena[2] = {nullptr, nullptr};
+    std::vector<uint64_t> mask;
+    char* out = nullptr;  // page-locked: the gathered text
+    uint64_t out_cap = 0;
+  };
+  Mate mate_[2];
+  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
+  std::vector<Buf> ring_;
+  size_t next_buf_ = 0, buf_cap_ = 0;
+  uint64_t blocks_ = 0, appends_ = 0, steps_ = 0, pairs_ = 0, pulled_ = 0;
+
+  [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
+  [[noreturn]] static void fail(const char* what, int rc) {
+    if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string("rufus_amd RUFUS.Filter: ") + rfx_last_error());
+    die(std::string("rufus_amd: ") + what + ": " + rfx_strerror(rc) + " " + rfx_last_error());
+  }
+
+  void settle_buf(Buf& b) {
+    if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
+    b.ticket = -1;
+  }
+  void reset(rfx_text* t) {  // (an arena's tickets die with its reset)
+    for (Buf& b : ring_)
+      if (b.t == t) settle_buf(b);
+    rfx_text_reset(t);
+  }
+  void scan(Mate& M, size_t size) {  // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of text
+    const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
+    for (size_t at = 0; at < size;) {
+      uint32_t nb = 0;
+      uint64_t used = 0, inf = 0;
+      const int rc = rfx_bgzf_scan(M.m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
+      if (nb == 0) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "rufus_amd RUFUS.Filter: %s BGZF block at byte %llu of the compressed input",
+                 rc == RFX_OK ? "truncated" : "no", (unsigned long long)at);
+        die(msg);
+      }
+      M.runs.push_back({at, (size_t)used, inf});
+      blocks_ += nb;
+      at += (size_t)used;
+    }
+  }
+  // queues runs into arena `a` until the next does not fit or the file is at its end (then the newline behind it)
+  void fill(Mate& M, rfx_text* a) {
+    for (; M.i < M.runs.size(); ++M.i) {
+      const Run& r = M.runs[M.i];
+      if (r.inflated > rfx_text_room(a)) return;
+      Buf& b = ring_[next_buf_];
+      next_buf_ = (next_buf_ + 1) % ring_.size();
+      settle_buf(b);
+      memcpy(b.p, M.m + r.at, r.n);
+      const long tk = rfx_text_append_bgzf(a, b.p, r.n);
+      if (tk < 0) fail("rfx_text_append_bgzf", (int)tk);
+      b.t = a;
+      b.ticket = tk;
+      ++appends_;
+    }
+    if (!M.closed && rfx_text_room(a) >= 1) {
+      static const char nl = '\n';
+      const long tk = rfx_text_append(a, &nl, 1);
+      if (tk < 0) fail("rfx_text_append", (int)tk);
+      M.closed = true;
+    }
+  }
+  uint64_t records(rfx_text* t) {
+    uint64_t n = 0;
+    const int rc = rfx_text_records(t, &n);
+    if (rc != RFX_OK) fail("rfx_text_records", rc);
+    return n;
+  }
+  void cut(rfx_text* t, rfx_text* next, uint64_t n) {
+    uint64_t kept = 0, carried = 0;
+    const int rc = rfx_text_settle_records(t, next, n, &kept, &carried);
+    if (rc == RFX_E_RANGE) not_strict();  // (cannot be: the arenas of a mate are equally large)
+    if (rc != RFX_OK) fail("rfx_text_settle_records", rc);
+    if (kept != n) die("rufus_amd RUFUS.Filter: an arena lost records between the count and the cut");
+  }
+  void gather(Mate& M, rfx_text* t, const uint64_t* mask, uint64_t n, uint64_t* bytes, uint64_t* n_sel) {
+    for (;;) {
+      const int rc = rfx_text_gather(t, mask, n, M.out, M.out_cap, bytes, n_sel);
+      if (rc == RFX_OK) return;
+      if (rc != RFX_E_RANGE) fail("rfx_text_gather", rc);
+      if (M.out) rfx_host_free(M.out);
+      M.out_cap = *bytes + *bytes / 4 + 4096;
+      M.out = (char*)rfx_host_alloc(M.out_cap);
+      if (!M.out) die("rufus_amd: cannot allocate page-locked memory for the pulled records");
+    }
+  }
+
+ public:
+  BgzfPairFilter(rfx_ctx* ctx, rfx_set* set, int min_q, int thresh, Sink sink, size_t arena_bytes = (size_t)1 << 30,
+                 size_t piece = 8u << 20)
+      : ctx_(ctx), set_(set), min_q_(min_q), thresh_(thresh), sink_(std::move(sink)), piece_(piece), arena_bytes_(arena_bytes) {
+    if (!rfx_text_open || !rfx_text_close || !rfx_text_room || !rfx_text_bytes || !rfx_text_append || !rfx_text_wait ||
+        !rfx_text_reset || !rfx_text_parse || !rfx_text_append_bgzf || !rfx_text_records || !rfx_text_settle_records ||
+        !rfx_text_gather || !rfx_reads_of_length)
+      die("rufus_amd RUFUS.Filter: this library cannot inflate BGZF input");
+    if (arena_bytes_ < 4 * 65536) die("rufus_amd RUFUS.Filter: RFX_FILTER_ARENA must be at least 262144 bytes");
+    for (Mate& M : mate_)
+      for (rfx_text*& a : M.arena) {
+        a = rfx_text_open(ctx_, arena_bytes_);
+        if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
+      }
+    buf_cap_ = std::max<size_t>(piece_, 1u << 16);  // (a block is at most 64 KiB)
+    ring_.resize(8);
+    for (Buf& b : ring_) {
+      b.p = (char*)rfx_host_alloc(buf_cap_);
+      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
+    }
+  }
+  ~BgzfPairFilter() {
+    for (Buf& b : ring_) {
+      settle_buf(b);
+      rfx_host_free(b.p);
+    }
+    for (Mate& M : mate_) {
+      for (rfx_text* a : M.arena) rfx_text_close(a);
+      if (M.out) rfx_host_free(M.out);
+    }
+  }
+  std::string counts() const {
+    char b[200];
+    snprintf(b, sizeof b, "filter: bgzf route: %llu blocks in %llu appends, %llu steps, %llu pairs, %llu pulled",
+             (unsigned long long)blocks_, (unsigned long long)appends_, (unsigned long long)steps_, (unsigned long long)pairs_,
+             (unsigned long long)pulled_);
+    return b;
+  }
+  uint64_t pairs() const { return pairs_; }
+  uint64_t pulled() const { return pulled_; }
+
+  // Two whole mapped BGZF files.  Dies on a block that is not BGZF, not whole or does not inflate, on text that is not
+  // strict 4-line FASTQ, on an empty sequence line in mate 1 and on a mate 2 with fewer records than mate 1.
+  void run(const char* m1, size_t n1, const char* m2, size_t n2) {
+    mate_[0].m = m1;
+    mate_[1].m = m2;
+    scan(mate_[0], n1);
+    scan(mate_[1], n2);
+    int cur = 0;
+    for (Mate& M : mate_) fill(M, M.arena[cur]);
+    for (;;) {
+      rfx_text* t[2] = {mate_[0].arena[cur], mate_[1].arena[cur]};
+      rfx_text* nx[2] = {mate_[0].arena[cur ^ 1], mate_[1].arena[cur ^ 1]};
+      const uint64_t r1 = records(t[0]), r2 = records(t[1]);
+      const uint64_t n = std::min(r1, r2);
+      if (n == 0) {
+        if (r1 == 0) {
+          if (!mate_[0].closed || rfx_text_bytes(t[0]) > 1) not_strict();  // a full arena without a record / a file that ends inside one
+          break;                                                           // mate 1 is at its end
+        }
+        if (!mate_[1].closed || rfx_text_bytes(t[1]) > 1) not_strict();
+        die("rufus_amd RUFUS.Filter: mate files hold different numbers of records");
+      }
+      for (int m = 0; m < 2; ++m) cut(t[m], nx[m], n);
+      for (int m = 0; m < 2; ++m) fill(mate_[m], nx[m]);  // queued, not waited for
+      rfx_reads* rd[2] = {nullptr, nullptr};
+      for (int m = 0; m < 2; ++m) {
+        int strict = 1;
+        rd[m] = rfx_text_parse(t[m], RFX_PACK_FILTER, min_q_, &strict);
+        if (!rd[m] && !strict) not_strict();
+        if (!rd[m]) fail("rfx_text_parse", RFX_E_HIP);
+      }
+      if (rfx_reads_of_length(rd[0], 0))
+        die("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
+      const size_t nw = (size_t)((n + 63) / 64);
+      for (int m = 0; m < 2; ++m) {
+        mate_[m].mask.assign(nw, 0);
+        uint64_t nh = 0;
+        // paired tool: `i < length()-1`, the last base is never examined (src/RUFUS.Filter.cpp:203)
+        const int rc = rfx_filter(set_, rd[m], thresh_, 1, nullptr, mate_[m].mask.data(), &nh);
+        if (rc) fail("rfx_filter", rc);
+      }
+      std::vector<uint64_t>& either = mate_[0].mask;  // == the reference's "mate 2 only if mate 1 failed" (:237-277)
+      uint64_t any = 0;
+      for (size_t w = 0; w < nw; ++w) {
+        either[w] |= mate_[1].mask[w];
+        if (w == nw - 1 && (n & 63)) either[w] &= (1ull << (n & 63)) - 1;
+        any |= either[w];
+      }
+      uint64_t bytes[2] = {0, 0}, sel[2] = {0, 0};
+      if (any)
+        for (int m = 0; m < 2; ++m) gather(mate_[m], t[m], either.data(), n, &bytes[m], &sel[m]);
+      if (sel[0] != sel[1]) die("rufus_amd RUFUS.Filter: the two mates' gathers disagree");
+      sink_(mate_[0].out, (size_t)bytes[0], mate_[1].out, (size_t)bytes[1], n, sel[0]);
+      ++steps_;
+      pairs_ += n;
+      pulled_ += sel[0];
+      for (int m = 0; m < 2; ++m) {
+        rfx_reads_free(rd[m]);
+        reset(t[m]);
+      }
+      cur ^= 1;
+    }
+  }
+};
+
 }  // namespace rfxcli

@@ -26,6 +26,62 @@ using namespace rfxcli;
 
 #include "rfx_sam.hpp"
 #include "rfx_packed_cache.hpp"
+#include "rfx_ingest.hpp"
+// ---- RUFUS.Filter HashList A.fastq.gz B.fastq.gz STUB K MinQ HashCountThreshold Threads --------------------------------
+// Both mate files bgzip'd (regular files whose first block rfx_bgzf_scan accepts): replaces runRufus.sh:974-977's
+// `<(zcat A) <(zcat B)`.  The files are mapped and handed to rfx_ingest.hpp's BgzfPairFilter: inflated, parsed, scanned
+// and the pulled pairs' text gathered on the device; this thread reads the files and appends what comes back to
+// STUB.Mutations.Mate1.fastq / .Mate2.fastq, in input order.  RFX_FILTER_ARENA: bytes of text per arena (four arenas).
+namespace bgzff {
+static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<uint64_t>& keys, long nk, int k, int min_q, int thresh,
+               std::ofstream& out1, std::ofstream& out2) {
+  const std::vector<int> gpus = gpu_list();
+  if (gpus.size() != 1)
+    die("rufus_amd RUFUS.Filter: BGZF input is inflated on the device, which needs one device (RUFUS_GPUS names more): "
+        "inflate it and pipe it in");
+  rfx_ctx* ctx = open_ctxs(gpus)[0];
+  rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
+  if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
+  trace("filter: device open, set built");
+  const char* map[2];
+  const int fds[2] = {fd1, fd2};
+  const size_t sizes[2] = {size1, size2};
+  for (int m = 0; m < 2; ++m) {
+    void* p = mmap(nullptr, sizes[m], PROT_READ, MAP_PRIVATE, fds[m], 0);
+    if (p == MAP_FAILED) die(std::string("rufus_amd RUFUS.Filter: cannot map a mate file: ") + strerror(errno));
+    (void)madvise(p, sizes[m], MADV_SEQUENTIAL);
+    map[m] = (const char*)p;
+  }
+  size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
+  if (const char* ev = getenv("RFX_FILTER_ARENA")) arena = (size_t)std::max(0ll, atoll(ev));
+  if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+  unsigned long long total = 0, found = 0;
+  {
+    BgzfPairFilter route(
+        ctx, set, min_q, thresh,
+        [&](const char* a, size_t na, const char* b, size_t nb, uint64_t pairs, uint64_t pulled) {
+          out1.write(a, (std::streamsize)na);
+          out2.write(b, (std::streamsize)nb);
+          total += pairs;
+          found += pulled;
+          printf("Read in %llu lines: Found %llu \r", total * 4, found);
+        },
+        arena, piece);
+    trace("filter: bgzf route, text arenas open");
+    route.run(map[0], sizes[0], map[1], sizes[1]);
+    trace(route.counts().c_str());
+    trace("filter: all pieces written");
+    out1.close();
+    out2.close();
+    printf("\nDone running RUFUS.Filter.cpp\n");
+    leave(0);  // (outputs closed: see the text route's end)
+  }
+  rfx_set_free(set);
+  rfx_close(ctx);
+  return 0;
+}
+}  // namespace bgzff
+
 // ---- RUFUS.Filter --sam CHRFILE HashList SAM|stdin STUB K MinQ HashCountThreshold Threads -----------------------------
 // SURVEY row N1, filter half.  runRufus.sh:964-967 runs `generator | PassThroughSamCheck.stranded CHR STUB.temp` into two
 // named pipes that RUFUS.Filter reads in lock step: SAM text -> pairing by QNAME -> FASTQ text -> two pipes -> parsed
@@ -761,6 +817,21 @@ int main(int argc, char** argv) {
   printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
 
   trace("filter: hash list parsed");
+#ifndef RFX_SINGLE_END
+  {  // two bgzip'd mate files: the device inflates them (namespace bgzff); one of the two is a mistake
+    struct stat sb[2];
+    const int fds[2] = {fd1, fd2};
+    bool z[2];
+    for (int m = 0; m < 2; ++m) {
+      const bool regular = fds[m] != 0 && fstat(fds[m], &sb[m]) == 0 && S_ISREG(sb[m].st_mode);
+      z[m] = is_bgzf(fds[m], regular, regular ? (uint64_t)sb[m].st_size : 0);
+    }
+    if (z[0] != z[1])
+      die(std::string("rufus_amd RUFUS.Filter: ") + (z[0] ? m1 : m2) + " is BGZF and " + (z[0] ? m2 : m1) +
+          " is not: give both mates compressed or both as text");
+    if (z[0]) return bgzff::run(fd1, (size_t)sb[0].st_size, fd2, (size_t)sb[1].st_size, keys, nk, k, min_q, thresh, out1, out2);
+  }
+#endif
   // RUFUS_GPUS: the pieces are dealt to the devices by worker thread (the filter shards by read block)
   const std::vector<int> gpus = gpu_list();
   const int n_gpu = (int)gpus.size();

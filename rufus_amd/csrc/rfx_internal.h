@@ -555,6 +555,14 @@ rfx_reads* reads_tile(rfx_ctx*, const rfx_reads* src, int k, uint32_t tile_len, 
 // the caller queued.  nullptr with "<who>: RFX_E_...: ..." as the error text.
 rfx_reads* reads_select_dev(rfx_ctx*, const rfx_reads* const* blocks, const uint64_t* const* d_masks, int n_blocks, int mode,
                             const char* who);
+// A text arena as rfx_gather.hip sees it (rfx_text.hip).  text_ready waits for the arena's appends and reports a BGZF block
+// that did not inflate (RFX_E_FORMAT), as rfx_text_settle does.  The other two queue on the ctx stream and wait for nothing:
+// tile_off[0 .. n_tiles] (n_tiles = ceil(n / 4096)) = the exclusive scan of the newlines per tile, tile_off[n_tiles] = all
+// of them; line_start[0] = 0, line_start[i] = the byte behind newline i for i <= max_lines (later newlines are not stored).
+int text_ready(rfx_text* t, rfx_ctx** c, const uint8_t** arena, uint64_t* used);
+hipError_t text_count_lines(rfx_ctx*, const uint8_t* arena, uint64_t n, uint64_t* tile_off);
+hipError_t text_line_starts(rfx_ctx*, const uint8_t* arena, uint64_t n, const uint64_t* tile_off, uint32_t* line_start,
+                            uint64_t max_lines);
 }  // namespace rfxi
 
 // Launch bracket: records a HIP-event span on the ctx stream (or `stream`: an arena's own, rfx_text.hip) when profiling

@@ -25,6 +25,11 @@
 // area of the arena and k_bgzf_inflate (rfx_bgzf.hip) writes their text into the arena; BGZF blocks end anywhere, so
 // rfx_text_settle cuts the arena at its last whole group of four lines (k_txt_count again, then k_txt_nth finds the byte
 // behind newline number 4 * floor(N / 4)) and carries the tail into the next arena.
+//
+// Two bgzip'd mate files in lock step (replaces runRufus.sh:974-977's `<(zcat A) <(zcat B)`): two arenas filled from two
+// files hold different numbers of whole records, so rfx_text_records reports an arena's floor(N / 4) and
+// rfx_text_settle_records -- rfx_text_settle's body -- cuts at a record count the caller gives (the smaller of the two).
+// rfx_gather.hip copies the text of selected records out of an arena; it finds the lines through rfxi::text_* below.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -87,7 +92,7 @@ __global__ __launch_bounds__(TX_BLOCK) void k_txt_count(const uint4* __restrict_
 
 __global__ __launch_bounds__(TX_BLOCK) void k_txt_lines(const uint4* __restrict__ text, uint64_t n_tiles,
                                                          const uint64_t* __restrict__ tile_off,
-                                                         uint32_t* __restrict__ line_start) {
+                                                         uint32_t* __restrict__ line_start, uint64_t max_lines) {
   __shared__ uint32_t s_wave[TX_BLOCK / 64];
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const uint4 v = text[tile * (TX_TILE / 16) + threadIdx.x];
@@ -111,7 +116,8 @@ __global__ __launch_bounds__(TX_BLOCK) void k_txt_lines(const uint4* __restrict_
       while (m) {
         const int bit = __ffs((int)m) - 1;  // 7, 15, 23, 31
         m &= m - 1u;
-        line_start[++rank] = pos0 + (uint32_t)q * 4u + (uint32_t)(bit >> 3) + 1u;
+        // (line_start has max_lines + 1 entries: rfx_text_gather sizes it by the caller's record count, not by the text)
+        if (++rank <= max_lines) line_start[rank] = pos0 + (uint32_t)q * 4u + (uint32_t)(bit >> 3) + 1u;
       }
     }
     __syncthreads();
@@ -302,6 +308,48 @@ int bgzf_check(rfx_text* t) {
 }
 
 }  // namespace
+
+// ---- what rfx_gather.hip needs of an arena ---------------------------------------------------------------------------
+namespace rfxi {
+
+int text_ready(rfx_text* t, rfx_ctx** c, const uint8_t** arena, uint64_t* used) {
+  (void)hipSetDevice(t->ctx->device);
+  HIPCHK(hipStreamSynchronize(t->copy));
+  if (t->kern) HIPCHK(hipStreamSynchronize(t->kern));
+  if (const int rc = bgzf_check(t)) return rc;
+  *c = t->ctx;
+  *arena = t->arena;
+  *used = t->used;
+  return RFX_OK;
+}
+
+hipError_t text_count_lines(rfx_ctx* c, const uint8_t* arena, uint64_t n, uint64_t* tile_off) {
+  // whole tiles are read: what lies behind the text holds no newline (the arena has 2 * TX_TILE bytes behind its capacity)
+  const hipError_t e = hipMemsetAsync(const_cast<uint8_t*>(arena) + n, 0, 2 * TX_TILE, c->stream);
+  if (e != hipSuccess) return e;
+  const uint64_t n_tiles = (n + TX_TILE - 1) / TX_TILE;
+  const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8);
+  {
+    rfx_span sp(c, "k_txt_count");
+    hipLaunchKernelGGL(k_txt_count, dim3(grid), dim3(TX_BLOCK), 0, c->stream, (const uint4*)arena, n_tiles, tile_off);
+  }
+  rfxk::scan_tail(c, tile_off, n_tiles);
+  return hipGetLastError();
+}
+
+hipError_t text_line_starts(rfx_ctx* c, const uint8_t* arena, uint64_t n, const uint64_t* tile_off, uint32_t* line_start,
+                            uint64_t max_lines) {
+  const hipError_t e = hipMemsetAsync(line_start, 0, 4, c->stream);
+  if (e != hipSuccess) return e;
+  const uint64_t n_tiles = (n + TX_TILE - 1) / TX_TILE;
+  const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8);
+  rfx_span sp(c, "k_txt_lines");
+  hipLaunchKernelGGL(k_txt_lines, dim3(grid), dim3(TX_BLOCK), 0, c->stream, (const uint4*)arena, n_tiles, tile_off, line_start,
+                     max_lines);
+  return hipGetLastError();
+}
+
+}  // namespace rfxi
 
 extern "C" {
 
@@ -519,9 +567,12 @@ long rfx_text_append_bgzf(rfx_text* t, const void* host, uint64_t n) {
   return (long)t->n_ev++;
 }
 
-int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried) {
+// rfx_text_settle (max_records = all of them) and rfx_text_settle_records: the cut lies behind newline number
+// 4 * min(floor(N / 4), max_records); *records (may be null) = that minimum
+static int settle_at(rfx_text* t, rfx_text* next, uint64_t max_records, uint64_t* records, uint64_t* carried, const char* who) {
   if (!t || !carried || next == t) return RFX_E_INVAL;
   *carried = 0;
+  if (records) *records = 0;
   if (next && (next->used != 0 || next->ctx != t->ctx)) return RFX_E_INVAL;
   rfx_ctx* c = t->ctx;
   (void)hipSetDevice(c->device);
@@ -543,7 +594,8 @@ int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried) {
   uint64_t n_lines = 0, cut = 0;
   hipError_t e = queue_read(c, &n_lines, tile_off + n_tiles, 8);
   if (e == hipSuccess) e = ctx_sync(c);
-  const uint64_t want = n_lines & ~3ull;  // newline number 4 * floor(N / 4) ends the last whole record
+  const uint64_t n_rec = std::min(n_lines / 4, max_records);
+  const uint64_t want = 4 * n_rec;  // newline number 4 * floor(N / 4) ends the last whole record
   if (e == hipSuccess && want) {
     {
       rfx_span sp(c, "k_txt_nth");
@@ -554,15 +606,15 @@ int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried) {
     if (e == hipSuccess) e = ctx_sync(c);
   }
   dfree(c, tile_off);
-  if (e != hipSuccess) return hip_fail(e, "rfx_text_settle");
+  if (e != hipSuccess) return hip_fail(e, who);
   if (cut > n) {
-    rfxi::set_error("rfx_text_settle: the cut lies behind the text");
+    rfxi::set_error((std::string(who) + ": the cut lies behind the text").c_str());
     return RFX_E_HIP;
   }
   const uint64_t tail = n - cut;
   if (tail) {
     if (!next) {
-      rfxi::set_error("rfx_text_settle: the text ends inside a record");
+      rfxi::set_error((std::string(who) + ": the text ends inside a record").c_str());
       return RFX_E_FORMAT;
     }
     if (tail > next->cap) return RFX_E_RANGE;
@@ -573,6 +625,37 @@ int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried) {
   }
   t->used = cut;
   *carried = tail;
+  if (records) *records = n_rec;
+  return RFX_OK;
+}
+
+int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried) {
+  return settle_at(t, next, ~0ull, nullptr, carried, "rfx_text_settle");
+}
+
+int rfx_text_settle_records(rfx_text* t, rfx_text* next, uint64_t max_records, uint64_t* records, uint64_t* carried) {
+  if (!records) return RFX_E_INVAL;
+  return settle_at(t, next, max_records, records, carried, "rfx_text_settle_records");
+}
+
+int rfx_text_records(rfx_text* t, uint64_t* records) {
+  if (!t || !records) return RFX_E_INVAL;
+  *records = 0;
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t n = 0;
+  if (const int rc = rfxi::text_ready(t, &c, &arena, &n)) return rc;
+  if (n == 0) return RFX_OK;
+  const uint64_t n_tiles = (n + TX_TILE - 1) / TX_TILE;
+  uint64_t* tile_off = (uint64_t*)dmalloc(c, (n_tiles + 1) * 8);
+  if (!tile_off) return RFX_E_NOMEM;
+  uint64_t n_lines = 0;
+  hipError_t e = rfxi::text_count_lines(c, arena, n, tile_off);
+  if (e == hipSuccess) e = queue_read(c, &n_lines, tile_off + n_tiles, 8);
+  const hipError_t es = ctx_sync(c);  // (also when queueing failed: nothing may still point at n_lines)
+  dfree(c, tile_off);
+  if (e != hipSuccess || es != hipSuccess) return hip_fail(e != hipSuccess ? e : es, "rfx_text_records");
+  *records = n_lines / 4;
   return RFX_OK;
 }
 
@@ -644,7 +727,8 @@ rfx_reads* rfx_text_parse(rfx_text* t, int flags, int min_q, int* strict) {
   if (e != hipSuccess) return fail("rfx_text_parse", e);
   {
     rfx_span sp(c, "k_txt_lines");
-    hipLaunchKernelGGL(k_txt_lines, dim3(grid), dim3(TX_BLOCK), 0, c->stream, (const uint4*)t->arena, n_tiles, tile_off, line_start);
+    hipLaunchKernelGGL(k_txt_lines, dim3(grid), dim3(TX_BLOCK), 0, c->stream, (const uint4*)t->arena, n_tiles, tile_off, line_start,
+                       n_lines);
   }
   {
     rfx_span sp(c, "k_txt_reads");
