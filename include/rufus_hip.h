@@ -564,6 +564,10 @@ void rfx_binned_free(rfx_binned*);
  * shard and k.  The subject's store is used up (counts of fallen candidates may be overwritten): strike once. */
 rfx_candidates* rfx_binned_strike(rfx_ctx*, rfx_binned* subject, const rfx_binned* control, uint32_t min_count,
                                   uint32_t max_count);
+/* The route the context's last rfx_binned_strike took: out[0] = its units of work (a unit: a bin of the coarser of the two
+ * sides), out[1] = how many of them went through the workgroup-per-unit kernel -- the units beyond the capacities of the
+ * wave-per-unit kernel that takes the plain ones, or all of them under RFX_STRIKE_WG=1.  For tests and measurements. */
+int rfx_binned_strike_stats(const rfx_ctx*, uint64_t out[2]);
 /* rfx_records_subtract(candidates, {control}, 0, ~0) for every further control: its keys are struck off the list */
 int rfx_candidates_strike(rfx_candidates*, const rfx_binned* control);
 /* entries of the list (struck ones included); _get: all of them, a struck one as ~0 -- canonical keys, no order */

@@ -23,7 +23,7 @@ import sys
 NOT_CHAIN = frozenset((
     "k_synth_reads", "k_copy16",
     "k_flag_absent", "k_flag_absent_tiled", "k_fa_bounds", "k_flag_gather", "k_flag_range", "k_flag_rank", "k_flag_present",
-    "k_compact_count", "k_compact_scatter", "k_scan_u64", "k_query", "k_strike_bins", "k_strike_cands",
+    "k_compact_count", "k_compact_scatter", "k_scan_u64", "k_query", "k_strike_bins", "k_strike_wave", "k_strike_cands",
     "k_strike_query", "k_binned_sizes", "k_binned_scan", "k_binned_gather", "k_binned_checksum", "k_binned_verify", "k_binned_query",
     "k_filter", "k_filter_q", "k_filter_p", "k_filter_fast", "k_filter_big", "k_hits_mask", "k_mask_count", "k_set_bitmap",
     "k_set_bitmap_big", "k_set_bitmap_q", "k_set_bitmap_p",

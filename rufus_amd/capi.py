@@ -62,6 +62,7 @@ SIGNATURES = {
     "rfx_binned_bits": (C.c_int, [C.c_void_p]),
     "rfx_binned_free": (None, [C.c_void_p]),
     "rfx_binned_strike": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rfx_binned_strike_stats": (C.c_int, [C.c_void_p, u64p]),
     "rfx_candidates_strike": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rfx_candidates_size": (C.c_uint64, [C.c_void_p]),
     "rfx_candidates_get": (C.c_int, [C.c_void_p, u64p]),
@@ -1016,6 +1017,14 @@ def binned_strike(ctx: Context, subject: Binned, control, min_count: int = 0, ma
     """Survivors of `subject` with min_count <= count <= max_count that `control` (a Binned, or None) does not hold."""
     return Candidates(ctx, lib().rfx_binned_strike(ctx._h, subject._h, control._h if control is not None else None,
                                                    min_count, max_count))
+
+
+def binned_strike_stats(ctx: Context) -> dict:
+    """The route of the context's last binned_strike: its units of work and how many of them the workgroup-per-unit kernel
+    took (those beyond the wave-per-unit kernel's capacities; all of them under RFX_STRIKE_WG=1) -- rfx_binned_strike_stats."""
+    o = np.zeros(2, dtype=np.uint64)
+    _check(lib().rfx_binned_strike_stats(ctx._h, _p(o, u64p)), "rfx_binned_strike_stats")
+    return {"units": int(o[0]), "deferred": int(o[1])}
 
 
 OVL_SAM, OVL_CONTIG, OVL_REGION = 0, 1, 2

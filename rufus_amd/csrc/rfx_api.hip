@@ -3182,17 +3182,21 @@ rfx_candidates* rfx_binned_strike(rfx_ctx* c, rfx_binned* subject, const rfx_bin
     uint64_t* keys = (uint64_t*)dmalloc(c, cap * 8);
     uint32_t* bins = (uint32_t*)dmalloc(c, cap * 4);
     uint32_t* counts = (uint32_t*)dmalloc(c, cap * 4);
-    uint32_t* d_n = (uint32_t*)dmalloc(c, 4);
+    // d_n: the list's counter, the number of deferred units, then the deferred units themselves (k_strike_wave's to k_strike_bins)
+    const uint32_t n_units = rfxk::strike_units(S, C);
+    uint32_t* d_n = (uint32_t*)dmalloc(c, ((size_t)n_units + 2) * 4);
     auto drop = [&] { dfree(c, keys); dfree(c, bins); dfree(c, counts); dfree(c, d_n); };
     if (!keys || !bins || !counts || !d_n) { drop(); snprintf(g_err, sizeof g_err, "rfx_binned_strike: out of device memory"); return nullptr; }
-    hipError_t e = hipMemsetAsync(d_n, 0, 4, c->stream);
-    uint32_t n = 0;
+    hipError_t e = hipMemsetAsync(d_n, 0, 8, c->stream);
+    uint32_t got[2] = {0, 0};
     if (e == hipSuccess) {
-      rfxk::strike_bins(c, S, C, min_count, max_count, keys, bins, counts, (uint32_t)cap, d_n);
-      e = queue_read(c, &n, d_n, 4);
+      rfxk::strike_bins(c, S, C, min_count, max_count, keys, bins, counts, (uint32_t)cap, d_n, d_n + 2, d_n + 1);
+      e = queue_read(c, got, d_n, 8);
     }
     if (e == hipSuccess) e = ctx_sync(c);
     if (e != hipSuccess) { hip_fail(e, "rfx_binned_strike"); (void)ctx_sync(c); drop(); return nullptr; }
+    const uint32_t n = got[0];
+    c->strike_deferred = c->strike_by_wave ? got[1] : c->strike_units;
     dfree(c, d_n);
     if (n > cap) {
       dfree(c, keys);
@@ -3213,6 +3217,13 @@ rfx_candidates* rfx_binned_strike(rfx_ctx* c, rfx_binned* subject, const rfx_bin
   }
   snprintf(g_err, sizeof g_err, "rfx_binned_strike: the candidate list did not converge (internal error)");
   return nullptr;
+}
+
+int rfx_binned_strike_stats(const rfx_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return RFX_E_INVAL;
+  out[0] = c->strike_units;
+  out[1] = c->strike_deferred;
+  return RFX_OK;
 }
 
 int rfx_candidates_strike(rfx_candidates* a, const rfx_binned* control) {

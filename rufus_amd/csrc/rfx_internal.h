@@ -64,6 +64,10 @@ struct rfx_ctx {
   hipError_t launch_error = hipSuccess;
   std::vector<struct rfx_table*> pend_tables;  // tables with unread MSP capacity flags
   double msp_surv_frac[2] = {0, 0};            // survivors / instances seen by the last MSP emit ([lower >= 2])
+  // the last rfx_binned_strike (rfx_binned_strike_stats): its units, how many of them k_strike_wave left to k_strike_bins
+  // (all of them when k_strike_wave did not run), and whether it ran
+  uint64_t strike_units = 0, strike_deferred = 0;
+  bool strike_by_wave = false;
   // ... and by the last emit of a table of (about) the same number of k-mer instances: a driver that counts samples of
   // different depth in turn (tumor 60x / normal 30x: BASELINE configs[4]) finds each sample's own ratio, not its
   // predecessor's -- the normal's store was sized by the tumor's ratio, half its own, overflowed, and the whole leaf
@@ -495,9 +499,11 @@ uint32_t msp_leaf_chunk_kept(uint32_t chunk);           // the chunk size of a p
 // count-of-counts of the staged survivors (span k_histo) + their number
 void histo_staged(rfx_ctx*, const msp_stage&, unsigned long long* d_histo, unsigned long long* d_total);
 // candidates of S (lo <= count <= hi) that C (bin_at == null: nobody) does not hold -> (key, bin of S, count in S), *out_n
-// counts on beyond cap; S's counts of fallen candidates may be put to 0
+// counts on beyond cap; S's counts of fallen candidates may be put to 0.  defer (room for every unit: a bin of the coarser
+// side each) and *n_defer (zeroed): the units k_strike_wave leaves to k_strike_bins; null: k_strike_bins takes them all
 void strike_bins(rfx_ctx*, const binned_view& S, const binned_view& C, uint32_t lo, uint32_t hi, uint64_t* out_k, uint32_t* out_b,
-                 uint32_t* out_c, uint32_t cap, uint32_t* out_n);
+                 uint32_t* out_c, uint32_t cap, uint32_t* out_n, uint32_t* defer, uint32_t* n_defer);
+uint32_t strike_units(const binned_view& S, const binned_view& C);  // the units strike_bins will take
 // keys[i] = RFX_EMPTY where C holds candidate i (of bin bins[i] of 2^bits)
 void strike_cands(rfx_ctx*, uint64_t* keys, const uint32_t* bins, uint32_t n, int bits, const binned_view& C);
 // ---- reading a binned store where it lies (rfx_binned_get / _checksum / _verify / _query) ----

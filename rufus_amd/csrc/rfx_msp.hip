@@ -1642,10 +1642,15 @@ __device__ __forceinline__ uint32_t sb_hash(uint64_t key) { return (uint32_t)((k
 __global__ __launch_bounds__(SB_BLK) void k_strike_bins(const rfxk::binned_view S, const rfxk::binned_view C, int ubits, uint32_t u_lo,
                                                         uint32_t u_hi, uint32_t lo, uint32_t hi, uint64_t* __restrict__ out_k,
                                                         uint32_t* __restrict__ out_b, uint32_t* __restrict__ out_c, uint32_t cap,
-                                                        uint32_t* __restrict__ out_n) {
+                                                        uint32_t* __restrict__ out_n, const uint32_t* __restrict__ units,
+                                                        const uint32_t* __restrict__ n_units) {
   __shared__ unsigned long long s_set[SB_SET];
   const int ds = S.bits - ubits, dc = C.bin_at ? C.bits - ubits : 0;
-  for (uint32_t u = u_lo + blockIdx.x; u < u_hi; u += gridDim.x) {
+  // (units: the list k_strike_wave left of the units it did not take, its length read here; null: every unit of [u_lo, u_hi))
+  const uint32_t n_u = units ? min(*n_units, u_hi - u_lo) : u_hi - u_lo;
+  for (uint32_t ui = blockIdx.x; ui < n_u; ui += gridDim.x) {
+    const uint32_t u = units ? units[ui] : u_lo + ui;
+    if (u < u_lo || u >= u_hi) continue;
     uint32_t n_s = 0, n_c = 0;
     const uint32_t s0 = u << ds, s1 = (u + 1u) << ds, c0 = u << dc, c1 = C.bin_at ? (u + 1u) << dc : c0;
     const uint4 ms = binned_marks(S, s0), mc = binned_marks(C, c0);  // (both sides' first marks are asked for at once)
@@ -1715,6 +1720,192 @@ __global__ __launch_bounds__(SB_BLK) void k_strike_bins(const rfxk::binned_view 
             cand_append(c != 0, c ? S.keys[first + i] : 0ull, b, c, out_k, out_b, out_c, cap, out_n);
           }
         });
+  }
+}
+
+// The same difference for the plain unit -- at most cap_c control and cap_s subject survivors, either side in at most
+// SW_SEGS stretches of its pool: nearly every unit of a trio -- with a WAVE per unit and no workgroup barrier.
+// k_strike_bins keeps one phase of one bin in flight per workgroup (marks, then the control's keys, then the subject's:
+// three dependent round trips of 3-5 KB), which leaves the memory system most of what it can take.  Here a wave walks both
+// sides first (marks only; `fill` where a bin crosses a chunk boundary), then asks for everything the unit has -- lane l
+// holds entries l, l + 64, .. of either side, up to SW_PER of each, rows beyond the unit's end left out by a scalar branch --
+// and for the marks of its NEXT unit behind that, and only then touches LDS: a unit costs one round trip, and sixteen waves
+// per CU (124 VGPRs, 8 KB of LDS each) have their units out at once.  The wave's set is its own SW_SET slots; a lane
+// remembers the slots it filled and empties exactly those.  The four waves of a workgroup never wait for each other.
+// Nothing is written to a store.  A unit that is not plain goes to `defer` (one atomic; they must be few: atomics on one
+// address take ~50 ns each) and k_strike_bins takes the list right behind this launch.  Every loop is bounded: the walks by
+// binned_segments, the probes by the set's size (and they end far earlier: cap_c <= 3/4 SW_SET keys, emptied after every
+// unit), the units by the grid stride.
+#ifndef RFX_SW_SET_LOG2  // (-DRFX_SW_SET_LOG2=9 -DRFX_SW_PER=6 ..: the variants of profiles/strike_wave.txt)
+#define RFX_SW_SET_LOG2 10
+#endif
+#ifndef RFX_SW_PER
+#define RFX_SW_PER 12
+#endif
+constexpr int SW_BLK = 256, SW_WAVES = SW_BLK / 64, SW_SET_LOG2 = RFX_SW_SET_LOG2, SW_SET = 1 << SW_SET_LOG2, SW_PER = RFX_SW_PER;
+constexpr uint32_t SW_CAP_C = 3 * SW_SET / 4 < 64 * SW_PER ? 3 * SW_SET / 4 : 64 * SW_PER, SW_CAP_S = 64 * SW_PER;
+
+__device__ __forceinline__ void sw_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// marks are the same in every lane: kept in scalar registers, the walk's arithmetic and branches with them
+__device__ __forceinline__ uint4 sw_uniform(const uint4 m) {
+  return make_uint4(__builtin_amdgcn_readfirstlane(m.x), __builtin_amdgcn_readfirstlane(m.y), __builtin_amdgcn_readfirstlane(m.z),
+                    __builtin_amdgcn_readfirstlane(m.w));
+}
+// One side of a unit as the walk finds it, in scalar registers: its entries are at most SW_SEGS stretches of the pool (one,
+// unless the unit crosses a chunk boundary or is several bins of the finer side).  Stretch q holds entries [start[q],
+// start[q + 1]) of the unit at pool indices base[q] + entry (base: modulo 2^64, the stretch's first index less start[q]).
+constexpr int SW_SEGS = 2;
+struct sw_side {
+  size_t base[SW_SEGS];
+  uint32_t start[SW_SEGS], bin[SW_SEGS];
+  uint32_t n = 0, segs = 0;
+  __device__ __forceinline__ sw_side() {
+#pragma unroll
+    for (int q = 0; q < SW_SEGS; ++q) {
+      base[q] = 0;
+      start[q] = ~0u;
+      bin[q] = 0;
+    }
+  }
+  __device__ __forceinline__ void add(uint32_t b, size_t first, uint32_t o, uint32_t e) {
+#pragma unroll
+    for (int q = 0; q < SW_SEGS; ++q)
+      if (segs == (uint32_t)q) {
+        base[q] = first + o - n;
+        start[q] = n;
+        bin[q] = b;
+      }
+    ++segs;
+    n += e - o;
+  }
+  // (what the walk read of `fill` on its way came through vector loads: said to be the same in every lane, so that what
+  // is decided by it is decided once per wave, by a scalar branch)
+  __device__ __forceinline__ void uniform() {
+#pragma unroll
+    for (int q = 0; q < SW_SEGS; ++q) {
+      base[q] = (size_t)__builtin_amdgcn_readfirstlane((uint32_t)base[q]) |
+                (size_t)__builtin_amdgcn_readfirstlane((uint32_t)(base[q] >> 32)) << 32;
+      start[q] = __builtin_amdgcn_readfirstlane(start[q]);
+      bin[q] = __builtin_amdgcn_readfirstlane(bin[q]);
+    }
+    n = __builtin_amdgcn_readfirstlane(n);
+    segs = __builtin_amdgcn_readfirstlane(segs);
+  }
+  // pool index and bin of entry min(j, n - 1) (1 <= n, segs <= SW_SEGS): a lane beyond the unit's end asks for the last
+  // entry once more, so that every lane loads, no load stands in a branch and the waits can be counted
+  __device__ __forceinline__ size_t at(uint32_t j, uint32_t* b) const {
+    static_assert(SW_SEGS == 2, "one select");
+    j = min(j, n - 1u);
+    const bool second = j >= start[1];  // (a stretch that is not there begins at ~0)
+    *b = second ? bin[1] : bin[0];
+    return (second ? base[1] : base[0]) + j;
+  }
+};
+
+template <bool FINE>  // FINE: the subject is the finer side, a unit is several of its bins and a lane notes the bin of each entry
+__global__ __launch_bounds__(SW_BLK) void k_strike_wave(const rfxk::binned_view S, const rfxk::binned_view C, int ubits, uint32_t u_lo,
+                                                        uint32_t u_hi, uint32_t lo, uint32_t hi, uint32_t cap_c, uint32_t cap_s,
+                                                        uint64_t* __restrict__ out_k, uint32_t* __restrict__ out_b,
+                                                        uint32_t* __restrict__ out_c, uint32_t cap, uint32_t* __restrict__ out_n,
+                                                        uint32_t* __restrict__ defer, uint32_t* __restrict__ n_defer) {
+  __shared__ unsigned long long s_sets[SW_WAVES][SW_SET];
+  constexpr uint32_t mask = SW_SET - 1u;
+  const uint32_t lane = threadIdx.x & 63u, n_waves = gridDim.x * SW_WAVES;
+  unsigned long long* const set = s_sets[threadIdx.x >> 6];
+  const int ds = S.bits - ubits, dc = C.bin_at ? C.bits - ubits : 0;
+  cap_c = min(cap_c, SW_CAP_C);
+  cap_s = min(cap_s, SW_CAP_S);
+  for (uint32_t i = lane; i < (uint32_t)SW_SET; i += 64u) set[i] = RFX_EMPTY;
+  sw_sync();
+  uint32_t u = u_lo + blockIdx.x * SW_WAVES + (threadIdx.x >> 6);
+  if (u >= u_hi) return;
+  uint4 ms = binned_marks(S, u << ds), mc = binned_marks(C, u << dc);
+  for (bool more = true; more; u += n_waves) {
+    const uint32_t s0 = u << ds, s1 = (u + 1u) << ds, c0 = u << dc, c1 = C.bin_at ? (u + 1u) << dc : c0;
+    const uint4 ms_u = sw_uniform(ms), mc_u = sw_uniform(mc);
+    more = u_hi - u > n_waves;
+    // ---- where the unit's entries lie (nothing read but, at a chunk boundary or for a further bin, fill and marks) ----
+    sw_side ss, cs;
+    binned_range(S, s0, s1, ms_u, [&](uint32_t b, size_t first, uint32_t o, uint32_t e) { ss.add(b, first, o, e); });
+    if (ss.n) binned_range(C, c0, c1, mc_u, [&](uint32_t b, size_t first, uint32_t o, uint32_t e) { cs.add(b, first, o, e); });
+    ss.uniform();
+    cs.uniform();
+    const uint32_t n_s = ss.n, n_c = cs.n;
+    const bool plain = n_c <= cap_c && n_s <= cap_s && ss.segs <= (uint32_t)SW_SEGS && cs.segs <= (uint32_t)SW_SEGS;
+    // ---- every load of the unit, one after the other: lane l asks for entries l, l + 64, .. of the control, then of the
+    // subject; rows beyond the unit's end are left out (the same in every lane: a scalar branch) ----
+    const uint32_t rows_c = plain ? (n_c + 63u) >> 6 : 0u, rows_s = plain ? (n_s + 63u) >> 6 : 0u;
+    unsigned long long ck[SW_PER], sk[SW_PER];
+    uint32_t sc[SW_PER], sb[SW_PER];
+#pragma unroll
+    for (int p = 0; p < SW_PER; ++p)
+      if ((uint32_t)p < rows_c) {
+        uint32_t b;
+        ck[p] = C.keys[cs.at(lane + 64u * (uint32_t)p, &b)];
+      }
+#pragma unroll
+    for (int p = 0; p < SW_PER; ++p)
+      if ((uint32_t)p < rows_s) {
+        const size_t a = ss.at(lane + 64u * (uint32_t)p, &sb[p]);
+        sk[p] = S.keys[a];
+        sc[p] = S.counts[a];
+      }
+    if (more) {  // the next unit's marks, asked for behind this unit's entries: they are here when the next trip begins
+      ms = binned_marks(S, (u + n_waves) << ds);
+      mc = binned_marks(C, (u + n_waves) << dc);
+    }
+    if (!n_s) continue;
+    if (!plain) {  // k_strike_bins' (tiles of control, a subject of any length or in many stretches)
+      if (lane == 0) defer[atomicAdd(n_defer, 1u)] = u;
+      continue;
+    }
+    // ---- the control's keys into the wave's set ----
+    uint32_t slot[SW_PER];
+#pragma unroll
+    for (int p = 0; p < SW_PER; ++p) {
+      slot[p] = ~0u;
+      if ((uint32_t)p >= rows_c) continue;
+      if (lane + 64u * (uint32_t)p < n_c) {
+        const unsigned long long key = ck[p];
+        uint32_t h = sb_hash(key) & mask;
+        for (uint32_t t = 0; t < (uint32_t)SW_SET; ++t) {
+          const unsigned long long old = atomicCAS(&set[h], (unsigned long long)RFX_EMPTY, key);
+          if (old == RFX_EMPTY) slot[p] = h;
+          if (old == RFX_EMPTY || old == key) break;
+          h = (h + 1u) & mask;
+        }
+      }
+    }
+    sw_sync();
+    // ---- the subject's entries: range, probe, list ----
+#pragma unroll
+    for (int p = 0; p < SW_PER; ++p) {
+      if ((uint32_t)p >= rows_s) continue;  // (the same in every lane: the list is filled wave by wave)
+      const unsigned long long key = sk[p];
+      uint32_t c = lane + 64u * (uint32_t)p < n_s ? sc[p] : 0u;
+      if (c && (c < lo || c > hi)) c = 0;
+      if (c && n_c) {
+        uint32_t h = sb_hash(key) & mask;
+        for (uint32_t t = 0; t < (uint32_t)SW_SET; ++t) {
+          const unsigned long long v = set[h];
+          if (v == key) c = 0;
+          if (v == key || v == RFX_EMPTY) break;
+          h = (h + 1u) & mask;
+        }
+      }
+      cand_append(c != 0, key, FINE ? sb[p] : u, c, out_k, out_b, out_c, cap, out_n);
+    }
+    sw_sync();
+    // ---- every lane empties the slots it filled ----
+#pragma unroll
+    for (int p = 0; p < SW_PER; ++p) {
+      if ((uint32_t)p < rows_c && slot[p] != ~0u) set[slot[p]] = RFX_EMPTY;
+    }
+    sw_sync();
   }
 }
 
@@ -2092,16 +2283,61 @@ void histo_staged(rfx_ctx* c, const msp_stage& st, unsigned long long* d_histo, 
                      d_histo, d_total);
 }
 
+uint32_t strike_units(const binned_view& S, const binned_view& C) {
+  const int ds = S.bits - (C.bin_at ? std::min(S.bits, C.bits) : S.bits);
+  const uint32_t u_lo = S.bin_lo >> ds, u_hi = (uint32_t)((((uint64_t)S.bin_hi + (1u << ds) - 1)) >> ds);
+  return u_hi > u_lo ? u_hi - u_lo : 0;
+}
+
 void strike_bins(rfx_ctx* c, const binned_view& S, const binned_view& C, uint32_t lo, uint32_t hi, uint64_t* out_k,
-                 uint32_t* out_b, uint32_t* out_c, uint32_t cap, uint32_t* out_n) {
-  rfx_span sp(c, "k_strike_bins");
+                 uint32_t* out_b, uint32_t* out_c, uint32_t cap, uint32_t* out_n, uint32_t* defer, uint32_t* n_defer) {
   const int ubits = C.bin_at ? std::min(S.bits, C.bits) : S.bits;
   const int ds = S.bits - ubits;
   const uint32_t u_lo = S.bin_lo >> ds, u_hi = (uint32_t)((((uint64_t)S.bin_hi + (1u << ds) - 1)) >> ds);
+  c->strike_units = strike_units(S, C);
+  c->strike_by_wave = false;
   if (u_hi <= u_lo) return;
   const uint32_t grid = std::min<uint32_t>(u_hi - u_lo, (uint32_t)c->n_cu * 10);  // 16 KB of LDS: ten workgroups of two waves per CU
+  // RFX_STRIKE_WG=1 (or no list to defer to): every unit through k_strike_bins
+  const char* const wg = getenv("RFX_STRIKE_WG");
+  if ((wg && atoi(wg)) || !defer || !n_defer) {
+    rfx_span sp(c, "k_strike_bins");
+    hipLaunchKernelGGL(k_strike_bins, dim3(grid), dim3(SB_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, out_k, out_b, out_c,
+                       cap, out_n, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+    return;
+  }
+  // RFX_STRIKE_WAVE_CAP=c,s lowers the capacities of the wave kernel (tests reach the deferral with small bins);
+  // RFX_STRIKE_WAVE_GRID=g its workgroups (a wave takes several units in turn)
+  uint32_t cap_c = SW_CAP_C, cap_s = SW_CAP_S;
+  if (const char* e = getenv("RFX_STRIKE_WAVE_CAP")) {
+    unsigned a = 0, b = 0;
+    if (sscanf(e, "%u,%u", &a, &b) == 2) {
+      cap_c = std::min<uint32_t>(cap_c, a);
+      cap_s = std::min<uint32_t>(cap_s, b);
+    }
+  }
+  // as many workgroups as are resident at once (8 KB of LDS per wave and ~124 VGPRs: four workgroups of four waves per CU),
+  // so that the static stride deals every wave the same share
+  int per_cu = 0;
+  const hipError_t oe = ds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_strike_wave<true>, SW_BLK, 0)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_strike_wave<false>, SW_BLK, 0);
+  if (oe != hipSuccess || per_cu < 1) per_cu = 4;
+  uint32_t wgrid = std::min<uint32_t>((u_hi - u_lo + SW_WAVES - 1) / SW_WAVES, (uint32_t)c->n_cu * (uint32_t)per_cu);
+  if (const char* e = getenv("RFX_STRIKE_WAVE_GRID")) wgrid = std::max<uint32_t>(1, std::min<uint32_t>(wgrid, (uint32_t)atoi(e)));
+  c->strike_by_wave = true;
+  {
+    rfx_span sp(c, "k_strike_wave");
+    if (ds)
+      hipLaunchKernelGGL(k_strike_wave<true>, dim3(wgrid), dim3(SW_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, cap_c, cap_s,
+                         out_k, out_b, out_c, cap, out_n, defer, n_defer);
+    else
+      hipLaunchKernelGGL(k_strike_wave<false>, dim3(wgrid), dim3(SW_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, cap_c, cap_s,
+                         out_k, out_b, out_c, cap, out_n, defer, n_defer);
+  }
+  // what it deferred, right behind it: the length of the list is read on the device
+  rfx_span sp(c, "k_strike_bins");
   hipLaunchKernelGGL(k_strike_bins, dim3(grid), dim3(SB_BLK), 0, c->stream, S, C, ubits, u_lo, u_hi, lo, hi, out_k, out_b, out_c,
-                     cap, out_n);
+                     cap, out_n, (const uint32_t*)defer, (const uint32_t*)n_defer);
 }
 
 void strike_cands(rfx_ctx* c, uint64_t* keys, const uint32_t* bins, uint32_t n, int bits, const binned_view& C) {
