@@ -1041,6 +1041,42 @@ def overlap_score(ctx: Context, a: bytes, cands, min_pct: float, min_ovl: int, v
     return out[:nb]
 
 
+class OvlPool:
+    """``rfx_ovl_pool``: the device-resident sequences of a greedy assembler, uploaded once; a merge patches one entry,
+    a score call moves only candidate indices and results."""
+
+    def __init__(self, ctx: Context, seqs):
+        self.ctx, self.n = ctx, len(seqs)
+        arr = (C.c_char_p * max(self.n, 1))(*seqs)
+        lens = (C.c_int * max(self.n, 1))(*[len(s) for s in seqs])
+        self._h = lib().rfx_ovl_pool_create(ctx._h, arr, lens, self.n)
+        if not self._h:
+            raise RufusError("rfx_ovl_pool_create failed: " + lib().rfx_last_error().decode())
+
+    def set(self, i: int, seq: bytes):
+        _check(lib().rfx_ovl_pool_set(self._h, i, seq, len(seq)), "rfx_ovl_pool_set")
+
+    def score(self, cands, min_pct: float, min_ovl: int, variant: int = OVL_SAM, strands: int = 0, query: int | None = None,
+              a_explicit: bytes | None = None) -> np.ndarray:
+        """(nstr, nb, 5) rows as overlap_score's, of pool entry `query` (or the string `a_explicit`) against the pool
+        entries `cands`.  strands: 0 = the query as it is, 1 = its reverse complement, 2 = both (forward rows first)."""
+        if (query is None) == (a_explicit is None):
+            raise ValueError("give either query (a pool index) or a_explicit (a string)")
+        cands = np.ascontiguousarray(cands, dtype=np.int32)
+        nb, nstr = len(cands), 2 if strands == 2 else 1
+        out = np.zeros((nstr, max(nb, 1), 5), dtype=np.int32)
+        _check(lib().rfx_ovl_pool_score(self._h, -1 if query is None else query, a_explicit,
+                                        0 if a_explicit is None else len(a_explicit), _p(cands, C.POINTER(C.c_int)), nb,
+                                        min_pct, min_ovl, variant, strands, _p(out, C.POINTER(C.c_int))),
+               "rfx_ovl_pool_score")
+        return out[:, :nb] if nb else out[:, :0]
+
+    def free(self):
+        if self._h:
+            lib().rfx_ovl_pool_free(self._h)
+            self._h = None
+
+
 def model_residuals(ctx: Context, histo, cands, log_resid: bool, inflection: int, max_copy: int = 5) -> np.ndarray:
     """Residuals of candidate coverage models (rows of (SC, stdev, factor, skew, power)) against a histogram:
     testModelLog / testModel of the reference's ModelDist (src/ModelDist.cpp:72-318), all candidates in one pass."""

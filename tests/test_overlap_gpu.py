@@ -10,6 +10,7 @@ import pytest
 import oracle
 from rufus_amd import capi
 from tests.conftest import ROOT
+from tests.overlap_ref import align3_one
 from tests.synth import make_trio
 
 pytestmark = pytest.mark.gpu
@@ -24,57 +25,6 @@ def _ref_built():
 
 
 needs_ref = pytest.mark.usefixtures("_ref_built")
-
-
-def align3_one(a: bytes, b: bytes, min_pct: float, min_ovl: int, strict3: bool, init: int):
-    """Per-candidate body of Align3 (src/OverlapSam.cpp:47-229 / src/Overlap.cpp:176-340), float32 as the
-    reference: returns (p1 score, p1 overlap, perfect, full score, full overlap)."""
-    f = np.float32
-    al, bl = len(a), len(b)
-    asm = not (bl > al)
-    window, longest = (bl, al) if asm else (al, bl)
-    mm = int(f(window) - f(window) * f(min_pct))
-    best, ovl, perfect = init, 0, False
-    ac = bc = 0
-    for i in range(longest - window + 1):
-        score = f(0)
-        for k in range(window):
-            if a[k + ac] == b[k + bc] and b[k + bc] != ord("N"):
-                score += f(1)
-            if f(k) - score > mm:
-                score = f(-1)
-                break
-        if asm:
-            ac += 1
-        else:
-            bc += 1
-        if window and f(score / f(window)) >= f(min_pct):
-            if best < score:
-                best, ovl = int(score), (-i if asm else i)
-            if score == window:
-                perfect = True
-                break
-    p1 = (best, ovl, perfect)
-    if not perfect:
-        for phase in (2, 3):
-            for i in range(window - 1, min_ovl - 1, -1):
-                score, k = f(0), 0
-                for k in range(i + 1):
-                    x, y = (a[al - i + k - 1], b[k]) if phase == 2 else (b[bl - i + k - 1], a[k])
-                    if x == y and y != ord("N"):
-                        score += f(1)
-                    if f(k) - score > mm:
-                        score = f(-1)
-                        break
-                else:
-                    k = i + 1
-                pct = f(score / f(k)) if k else f(0)
-                ok = pct > f(min_pct) if (phase == 3 and strict3) else pct >= f(min_pct)
-                if ok and best < score:
-                    best, ovl = int(score), (i - al + 1 if phase == 2 else bl - i - 1)
-                    if score == i:
-                        break
-    return p1[0], p1[1], int(p1[2]), best, ovl
 
 
 def test_overlap_score_kernel_matches_restatement(ctx):
