@@ -284,6 +284,52 @@ int rfx_text_settle_records(rfx_text* t, rfx_text* next, uint64_t max_records, u
 int rfx_text_gather(rfx_text* t, const uint64_t* hitmask, uint64_t n_records, void* host_out, uint64_t cap, uint64_t* bytes,
                     uint64_t* n_selected);
 
+/* -------------------------------------------------------------------------------------------
+ * BAM in: the records of a BAM found and their 4-bit sequences packed on the device
+ * Replaces the generator of every sample, `samtools view -F 3328 X.bam | PassThroughSamCheck CHR | jellyfish count`
+ * (runRufus.sh:599, :639; scripts/RunJellyForRUFUS.sh:28-29).  The container is BGZF: the arena is filled with the
+ * unchanged rfx_text_append_bgzf.  The record layout (section 4.2 of the SAM specification) is
+ * rufus_amd/csrc/rfx_bam_core.h, one source for host and device; the kernels are rufus_amd/csrc/rfx_bam.hip.
+ *
+ * rfx_bam_header (replaces samtools view's header read in front of runRufus.sh:599; pure host code, needs no device):
+ * buf[0, n) = the first bytes of the compressed file.  Inflates BGZF blocks until the BAM header is whole -- magic
+ * BAM\1, l_text, the text, n_ref, and for every reference l_name, name, l_ref -- and reports *n_ref, the references'
+ * names (each with its NUL, one behind the other, in names[0, *names_bytes); names may be NULL; names_cap too small:
+ * RFX_E_RANGE with *names_bytes set), *first_block = the compressed byte offset of the block that holds the first
+ * record's first byte and *skip = that byte's offset inside the block's inflated data (a header that ends with its block:
+ * the block behind it, skip 0).  *complete = 0 and RFX_OK when the header is not whole in these bytes -- no error, as
+ * rfx_bgzf_scan's incomplete tail: the caller maps more.  RFX_E_FORMAT for bytes that are not BGZF, for BGZF that is
+ * not BAM (a bgzip'd FASTQ) and for a block that does not inflate.
+ *
+ * rfx_bam_settle (replaces the line framing `samtools view | PassThroughSamCheck` gives the reference,
+ * scripts/RunJellyForRUFUS.sh:28): the BAM twin of rfx_text_settle, with its preconditions.  Waits for t's appends,
+ * finds the chain of records from byte `skip` (rfx_bam_header's for the arena that holds the first record, 0 behind it)
+ * -- in parallel and exactly: a guess per tile of 16 KiB, a walk per tile, repair rounds until every tile starts where
+ * its predecessor ends -- shortens t to the end of its last whole record and copies the tail, device to device, to the
+ * front of `next`.  *n_records = the whole records, *carried = the tail's bytes.  The record starts are kept with the
+ * arena until rfx_text_reset.  n_ref = the header's.  next == NULL with a tail: RFX_E_FORMAT (the file ends inside a
+ * record); no whole record in an arena no further BGZF block fits into (room < 64 KiB): RFX_E_RANGE; a record on the
+ * chain that rfx_bam_core.h's bam_valid refuses: RFX_E_FORMAT, rfx_last_error() = "rfx_bam: record at byte <offset in
+ * this arena>: <reason>" for the lowest such record, and nothing is changed; a block that did not inflate: RFX_E_FORMAT
+ * with the "rfx_bgzf:" text.  RFX_BAM_TILE (a power of two >= 256) and RFX_BAM_NO_GUESS=1 (no guesses: the whole chain
+ * comes from repair) are test knobs that change no result.
+ *
+ * rfx_bam_parse (replaces src/PassThroughSamCheck.cpp:51-155 and the `-F 3328` of runRufus.sh:599): the records of an
+ * arena settled by rfx_bam_settle with (flag & exclude_flags) == 0, in file order, as a dense count block -- exactly what
+ * rfx_pack_reads(RFX_PACK_COUNT) makes of the SEQ strings samtools view prints for them ("=ACMGRSVTWYHKDBN"[nibble], high
+ * nibble first, `*` for l_seq == 0).  ref_runs[2 i], [2 i + 1] = (first kept index, refID as uint32) wherever a kept
+ * record's refID differs from the kept record before it; *n_runs = their number (more than cap: NULL, "RFX_E_RANGE" in the
+ * error text, *n_runs set; cap = the arena's records always suffices).  NULL on failure, rfx_last_error() says why.
+ *
+ * rfx_bam_stats: of the last rfx_bam_settle on this ctx -- out[0] tiles, out[1] guesses that repair had to change, out[2]
+ * repair rounds, out[3] records.  For tests and measurements, like rfx_binned_strike_stats.
+ * ------------------------------------------------------------------------------------------- */
+int rfx_bam_header(const void* buf, uint64_t n, int* complete, int32_t* n_ref, char* names, uint64_t names_cap,
+                   uint64_t* names_bytes, uint64_t* first_block, uint32_t* skip);
+int rfx_bam_settle(rfx_text* t, rfx_text* next, uint64_t skip, int32_t n_ref, uint64_t* n_records, uint64_t* carried);
+rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs, uint64_t cap, uint64_t* n_runs);
+int rfx_bam_stats(const rfx_ctx*, uint64_t out[4]);
+
 /* Synthetic trio workload (BASELINE.json configs[1]-[4]) -- benchmark and scale-test input,
  * not a replacement of any reference code.  Every base is a pure function of (parameters, pair, mate, base
  * index) -- see rufus_amd/csrc/rfx_synth.h -- so a 30x WGS sample (6.2e8 reads) is generated straight into

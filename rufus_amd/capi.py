@@ -103,6 +103,11 @@ SIGNATURES = {
     "rfx_text_records": (C.c_int, [C.c_void_p, u64p]),
     "rfx_text_settle_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p]),
     "rfx_text_gather": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]),
+    "rfx_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_char_p, C.c_uint64, u64p,
+                                 u64p, u32p]),
+    "rfx_bam_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, u64p, u64p]),
+    "rfx_bam_parse": (C.c_void_p, [C.c_void_p, C.c_uint32, u32p, C.c_uint64, u64p]),
+    "rfx_bam_stats": (C.c_int, [C.c_void_p, u64p]),
     "rfx_reads_of_length": (C.c_uint64, [C.c_void_p, C.c_uint32]),
     "rfx_synth_text": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rfx_synth_snv": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_char_p, C.c_char_p]),
@@ -317,6 +322,24 @@ def bgzf_scan(data: bytes, max_blocks: int = 0xFFFFFFFF):
     return int(nb.value), int(used.value), int(inf.value)
 
 
+def bam_header(data: bytes):
+    """``rfx_bam_header`` on the first bytes of a BAM file: None while the header is not whole in `data` (map more), else
+    {"n_ref", "names" (list of bytes), "first_block" (compressed offset of the block with the first record's first byte),
+    "skip" (that byte's offset in the block's inflated data)}.  Pure host code."""
+    done, n_ref, nbytes = C.c_int(0), C.c_int32(0), C.c_uint64(0)
+    first, skip = C.c_uint64(0), C.c_uint32(0)
+    L = lib()
+    _check(L.rfx_bam_header(data, len(data), C.byref(done), C.byref(n_ref), None, 0, C.byref(nbytes), C.byref(first),
+                            C.byref(skip)), "rfx_bam_header")
+    if not done.value:
+        return None
+    buf = C.create_string_buffer(max(int(nbytes.value), 1))
+    _check(L.rfx_bam_header(data, len(data), C.byref(done), C.byref(n_ref), buf, len(buf), C.byref(nbytes), C.byref(first),
+                            C.byref(skip)), "rfx_bam_header")
+    names = buf.raw[:nbytes.value].split(b"\0")[:-1] if nbytes.value else []
+    return {"n_ref": int(n_ref.value), "names": names, "first_block": int(first.value), "skip": int(skip.value)}
+
+
 class PackedReads:
     """Host-side packed block: 32 bases per 64-bit code word, one mask bit per base."""
 
@@ -422,6 +445,13 @@ class Context:
             self._pin_arr = np.ctypeslib.as_array((C.c_uint64 * max(n_words, 1)).from_address(p))
         return self._pin_arr[:max(n_words, 1)]
 
+    def bam_stats(self) -> dict:
+        """The last TextArena.bam_settle on this context: tiles, guesses that repair had to change, repair rounds, records
+        (rfx_bam_stats)."""
+        o = np.zeros(4, np.uint64)
+        _check(lib().rfx_bam_stats(self._h, _p(o, u64p)), "rfx_bam_stats")
+        return {"tiles": int(o[0]), "changed": int(o[1]), "rounds": int(o[2]), "records": int(o[3])}
+
     def __enter__(self):
         return self
 
@@ -459,6 +489,28 @@ class TextArena:
         carried = C.c_uint64(0)
         _check(lib().rfx_text_settle(self._h, next._h if next is not None else None, C.byref(carried)), "rfx_text_settle")
         return int(carried.value)
+
+    def bam_settle(self, next: "TextArena | None" = None, skip: int = 0, n_ref: int = 0):
+        """The BAM twin of settle(): finds the records of the inflated BAM bytes from byte `skip`, shortens the arena to its
+        last whole record and moves the tail to the front of `next`: (whole records, bytes carried) (rfx_bam_settle)."""
+        rec, carried = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rfx_bam_settle(self._h, next._h if next is not None else None, skip, n_ref, C.byref(rec),
+                                    C.byref(carried)), "rfx_bam_settle")
+        self._bam_records = int(rec.value)
+        return int(rec.value), int(carried.value)
+
+    def bam_parse(self, exclude_flags: int = 3328):
+        """(block, runs): the records with flag & exclude_flags == 0 of an arena settled by bam_settle as a count block, and
+        an (n_runs, 2) int64 array of (first kept index, refID) wherever the kept records' refID changes (rfx_bam_parse)."""
+        cap = max(getattr(self, "_bam_records", 0), 1)
+        runs = np.zeros(2 * cap, np.uint32)
+        n_runs = C.c_uint64(0)
+        h = lib().rfx_bam_parse(self._h, exclude_flags, _p(runs, u32p), cap, C.byref(n_runs))
+        if not h:
+            raise RufusError("rfx_bam_parse failed: " + lib().rfx_last_error().decode())
+        pairs = runs[:2 * int(n_runs.value)].reshape(-1, 2)
+        out = np.stack([pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int32).astype(np.int64)], axis=1)
+        return ReadBlock.from_handle(self.ctx, h), out
 
     def records(self) -> int:
         """Whole records (groups of four lines) the arena holds (rfx_text_records)."""

@@ -28,6 +28,26 @@ static double secs_since(std::chrono::steady_clock::time_point t0) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Does the BGZF file begin with a BAM header?  (rfx_bam_header refuses BGZF whose first bytes are not BAM's magic; a header
+// that is not whole in the first 64 KiB is still BAM.)  What turns `jellyfish count X.bam` without --bam into a message
+// that says --bam instead of the FASTQ one.
+static bool is_bam(int fd, uint64_t size) {
+  if (!rfx_bam_header) return false;
+  std::vector<char> head((size_t)std::min<uint64_t>(size, 1u << 16));
+  size_t got = 0;
+  while (got < head.size()) {
+    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
+    if (n < 0 && errno == EINTR) continue;
+    if (n <= 0) break;
+    got += (size_t)n;
+  }
+  int complete = 0;
+  int32_t n_ref = 0;
+  uint64_t names_bytes = 0, first_block = 0;
+  uint32_t skip = 0;
+  return rfx_bam_header(head.data(), got, &complete, &n_ref, nullptr, 0, &names_bytes, &first_block, &skip) == RFX_OK;
+}
+
 static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   const auto t_start = std::chrono::steady_clock::now();
   int k = 0, threads = 1, out_counter_len = 4;
@@ -49,12 +69,19 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // scans that instead of parsing the stream a second time.
   const char* keep_path = nullptr;
   int keep_minq = 15;
-  enum { OPT_DISK = 1000, OPT_OCL, OPT_TIMING, OPT_TEXT, OPT_SAM, OPT_SPOOL, OPT_KEEP, OPT_KEEPQ };
+  // --bam CHR_FILE [--bam-exclude N] (not in jellyfish): the input is a BAM file and this process does what
+  // `samtools view -F N X.bam | PassThroughSamCheck CHR_FILE | jellyfish count` does (runRufus.sh:599,
+  // scripts/RunJellyForRUFUS.sh:28-29; N defaults to 3328) -- BGZF inflated, the records found and their sequences packed
+  // on the device (rfx_ingest.hpp BamIngest; csrc/rfx_bam.hip), the chromosome log written.
+  const char* bam_chr = nullptr;
+  uint32_t bam_exclude = 3328;
+  enum { OPT_DISK = 1000, OPT_OCL, OPT_TIMING, OPT_TEXT, OPT_SAM, OPT_SPOOL, OPT_KEEP, OPT_KEEPQ, OPT_BAM, OPT_BAMX };
   static option lo[] = {{"mer-len", 1, 0, 'm'},      {"size", 1, 0, 's'},        {"threads", 1, 0, 't'},
                         {"output", 1, 0, 'o'},       {"counter-len", 1, 0, 'c'}, {"out-counter-len", 1, 0, OPT_OCL},
                         {"canonical", 0, 0, 'C'},    {"disk", 0, 0, OPT_DISK},   {"lower-count", 1, 0, 'L'},
                         {"upper-count", 1, 0, 'U'},  {"timing", 1, 0, OPT_TIMING}, {"text", 0, 0, OPT_TEXT}, {"sam", 1, 0, OPT_SAM},
                         {"spool", 1, 0, OPT_SPOOL},  {"keep-packed", 1, 0, OPT_KEEP}, {"keep-minq", 1, 0, OPT_KEEPQ},
+                        {"bam", 1, 0, OPT_BAM},      {"bam-exclude", 1, 0, OPT_BAMX},
                         {"reprobes", 1, 0, 'p'},     {0, 0, 0, 0}};
   optind = 1;
   int ch;
@@ -76,12 +103,18 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
       case OPT_SPOOL: spool_path = optarg; break;
       case OPT_KEEP: keep_path = optarg; break;
       case OPT_KEEPQ: keep_minq = atoi(optarg); break;
+      case OPT_BAM: bam_chr = optarg; break;
+      case OPT_BAMX: bam_exclude = (uint32_t)strtoul(optarg, nullptr, 0); break;
       case OPT_TEXT: die("rufus_amd jellyfish: --text output is not on the RUFUS path");
       default: die("Usage: jellyfish count -m K -s SIZE [-C] [-L n] [-U n] [-t T] [-o OUT] [--disk] file...");
     }
   }
   if (k < 1 || !size_given) die("Missing required switch: -m, --mer-len and -s, --size");
   if (optind >= argc) die("Missing sequence file");
+  static const char* const bam_alone =
+      "rufus_amd jellyfish count: --bam finds and packs the records on the device, which needs one device and none of --sam, "
+      "--spool, --keep-packed";
+  if (bam_chr && (sam_chr || spool_path || keep_path)) die(bam_alone);
   int lsize = 0;
   while ((1ull << lsize) < size) ++lsize;
   if (lsize < 1) lsize = 1;
@@ -279,9 +312,36 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // bytes per read over PCIe and the host only reads the file.  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160).
   // Plain gzip (no `BC` subfield) is not BGZF and goes where it went before.
   std::unique_ptr<BgzfIngest> bgzf_ingest;
+  // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, none of --sam, --spool,
+  // --keep-packed, as the bgzf route.
+  std::unique_ptr<BamIngest> bam_ingest;
+  if (bam_chr && n_gpu != 1) die(bam_alone);
   {
     for (Input& in : inputs) {
       bool done = false;
+      if (bam_chr) {
+        if (!in.regular) die("rufus_amd jellyfish count: --bam needs a regular file, not a pipe: the BAM is mapped");
+        if (!is_bgzf(in.fd, in.regular, in.size)) die(std::string("rufus_amd jellyfish count: --bam: '") + in.path + "' is not BGZF");
+        if (!bam_ingest) {
+          device_ready();
+          size_t arena_bytes = (size_t)1 << 30;  // RFX_BAM_ARENA (a test knob, bytes, >= 1 MiB): small files cross arenas
+          if (const char* ev = getenv("RFX_BAM_ARENA")) arena_bytes = (size_t)std::max(1ll << 20, atoll(ev));
+          bam_ingest.reset(new BamIngest(
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, bam_exclude, arena_bytes,
+              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20));
+          trace("count: bam route, arenas open");
+        }
+        void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
+        if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
+        (void)madvise(m, in.size, MADV_SEQUENTIAL);
+        bam_ingest->feed_mapped((const char*)m, in.size);
+        munmap(m, in.size);
+        trace(("count: " + bam_ingest->counts()).c_str());
+        if (in.fd > 0) ::close(in.fd);
+        continue;
+      }
+      if (is_bgzf(in.fd, in.regular, in.size) && is_bam(in.fd, in.size))
+        die(std::string("rufus_amd jellyfish count: '") + in.path + "' is a BAM file: count it with --bam CHR_FILE");
       if (is_bgzf(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
         if (n_gpu != 1 || sam_chr || spool_path || keep_path)
           die("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
@@ -413,6 +473,18 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   }
   // the packed-read cache is a cache only from here on: its header now says how many chunks describe how long a stream
   if (keep_path && ingest) ingest->finish_keep_packed(inputs[0].regular ? inputs[0].size : ingest->spooled_bytes());
+  if (bam_chr) {
+    FILE* cf = fopen(bam_chr, "w");
+    if (!cf) {  // src/PassThroughSamCheck.cpp:37-44
+      printf("ERROR, Output file could not be opened -%s\n", bam_chr);
+    } else {
+      if (bam_ingest)
+        for (const std::string& name : bam_ingest->chr_log()) fprintf(cf, "%s\n", name.c_str());
+      else fprintf(cf, "notachr\n");
+      fclose(cf);
+    }
+  }
+  bam_ingest.reset();
   if (sam_chr) {
     FILE* cf = fopen(sam_chr, "w");
     if (!cf) {  // src/PassThroughSamCheck.cpp:37-44

@@ -1241,6 +1241,179 @@ class BgzfIngest {
   }
 };
 
+// ---- BAM: inflated, its records found and their sequences packed on the device (rfx_bam_*; rufus_amd/csrc/rfx_bam.hip) --
+// Replaces `samtools view -F 3328 X.bam | PassThroughSamCheck CHR | jellyfish count ... /dev/fd/0` (runRufus.sh:599,
+// scripts/RunJellyForRUFUS.sh:28-29): the host only reads the file.  BgzfIngest's shape -- the run rule, the ring of
+// page-locked buffers, two arenas, settle -> fill the next arena -> parse and sink -- with rfx_bam_settle for the carry
+// (a record straddles blocks and arenas as a FASTQ record does) and rfx_bam_parse for the block.  The runs start at the
+// block rfx_bam_header names; `skip`, the header's bytes in that block, goes to the first arena's settle only.  The
+// chromosome log of PassThroughSamCheck (src/PassThroughSamCheck.cpp:140-155) is stitched on the host from the arenas'
+// run lists: a run that begins an arena with the refID the arena before ended with is no change.
+// (weak, as above: the host harnesses link the executable's source against stand-in libraries without these)
+#pragma weak rfx_bam_header
+#pragma weak rfx_bam_settle
+#pragma weak rfx_bam_parse
+class BamIngest {
+  rfx_ctx* ctx_;
+  std::function<void(rfx_reads*)> sink_;
+  size_t piece_;
+  uint32_t exclude_;
+  rfx_text* arena_[2] = {nullptr, nullptr};
+  uint64_t arena_bytes_;
+  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
+  std::vector<Buf> ring_;
+  size_t next_buf_ = 0, buf_cap_ = 0;
+  uint64_t blocks_ = 0, arenas_ = 0, records_ = 0, reads_ = 0, appends_ = 0;
+  int32_t n_ref_ = 0;
+  std::vector<std::string> ref_names_;
+  std::vector<int32_t> chr_runs_;  // the kept records' refID wherever it changes, over the whole input
+  std::vector<uint32_t> runs_buf_;
+
+  void settle_buf(Buf& b) {
+    if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
+    b.ticket = -1;
+  }
+  void settle_ring_of(rfx_text* t) {  // before an arena is reset: its tickets die with the reset
+    for (Buf& b : ring_)
+      if (b.t == t) settle_buf(b);
+  }
+  void parse_and_sink(rfx_text* t, uint64_t n_records) {
+    if (n_records) {
+      runs_buf_.resize((size_t)2 * n_records);
+      uint64_t n_runs = 0;
+      rfx_reads* r = rfx_bam_parse(t, exclude_, runs_buf_.data(), n_records, &n_runs);
+      if (!r) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
+      for (uint64_t i = 0; i < n_runs; ++i) {
+        const int32_t ref = (int32_t)runs_buf_[2 * i + 1];
+        if (chr_runs_.empty() || chr_runs_.back() != ref) chr_runs_.push_back(ref);
+      }
+      reads_ += rfx_reads_count(r);
+      records_ += n_records;
+      ++arenas_;
+      sink_(r);
+    }
+    settle_ring_of(t);
+    rfx_text_reset(t);
+  }
+  // the whole records of t; *carried = the bytes moved to `next`
+  uint64_t settle(rfx_text* t, rfx_text* next, uint64_t skip, uint64_t* carried) {
+    uint64_t n_records = 0;
+    const int rc = rfx_bam_settle(t, next, skip, n_ref_, &n_records, carried);
+    if (rc == RFX_E_FORMAT) die(std::string("rufus_amd jellyfish count: --bam: ") + rfx_last_error());
+    if (rc == RFX_E_RANGE) die("rufus_amd jellyfish count: --bam: a record that is longer than an arena");
+    if (rc != RFX_OK) die(std::string("rufus_amd: rfx_bam_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
+    return n_records;
+  }
+
+ public:
+  BamIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, uint32_t exclude_flags, size_t arena_bytes = (size_t)1 << 30,
+            size_t piece = 8u << 20)
+      : ctx_(ctx), sink_(std::move(sink)), piece_(piece), exclude_(exclude_flags), arena_bytes_(arena_bytes) {
+    if (!rfx_text_append_bgzf || !rfx_bam_header || !rfx_bam_settle || !rfx_bam_parse)
+      die("rufus_amd jellyfish count: this library cannot read BAM input");
+    for (rfx_text*& a : arena_) {
+      a = rfx_text_open(ctx_, arena_bytes);
+      if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
+    }
+    buf_cap_ = std::max<size_t>(piece_, 1u << 16);  // (a block is at most 64 KiB)
+    ring_.resize(4);
+    for (Buf& b : ring_) {
+      b.p = (char*)rfx_host_alloc(buf_cap_);
+      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
+    }
+  }
+  ~BamIngest() {
+    for (Buf& b : ring_) {
+      settle_buf(b);
+      rfx_host_free(b.p);
+    }
+    for (rfx_text* a : arena_) rfx_text_close(a);
+  }
+  uint64_t reads() const { return reads_; }
+  std::string counts() const {
+    char b[200];
+    snprintf(b, sizeof b, "bam route: %llu blocks in %llu appends, %llu arenas, %llu records, %llu reads", (unsigned long long)blocks_,
+             (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)records_, (unsigned long long)reads_);
+    return b;
+  }
+  // PassThroughSamCheck's side file (src/PassThroughSamCheck.cpp:140-155): its initial `current`, then the RNAME of every
+  // run of kept records in file order; refID -1 prints as `*`
+  std::vector<std::string> chr_log() const {
+    std::vector<std::string> out{"notachr"};
+    for (int32_t ref : chr_runs_) out.push_back(ref < 0 || (size_t)ref >= ref_names_.size() ? std::string("*") : ref_names_[(size_t)ref]);
+    return out;
+  }
+
+  // A whole mapped BAM file.  Dies on a header that is not BAM's, on a block that is not BGZF, not whole or does not
+  // inflate, on a record rfx_bam_core.h refuses and on a file that ends inside a record.
+  void feed_mapped(const char* m, size_t size) {
+    int complete = 0;
+    uint64_t names_bytes = 0, first_block = 0;
+    uint32_t skip0 = 0;
+    int rc = rfx_bam_header(m, size, &complete, &n_ref_, nullptr, 0, &names_bytes, &first_block, &skip0);
+    if (rc == RFX_OK && complete) {
+      std::vector<char> names((size_t)names_bytes + 1);
+      rc = rfx_bam_header(m, size, &complete, &n_ref_, names.data(), names_bytes, &names_bytes, &first_block, &skip0);
+      ref_names_.clear();
+      for (size_t at = 0; at < (size_t)names_bytes; at += strlen(names.data() + at) + 1) ref_names_.emplace_back(names.data() + at);
+    }
+    if (rc != RFX_OK || !complete) die("rufus_amd jellyfish count: --bam: the input does not begin with a whole BAM header");
+    // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of inflated bytes
+    struct Run { size_t at, n; uint64_t inflated; };
+    std::vector<Run> runs;
+    const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
+    for (size_t at = (size_t)first_block; at < size;) {
+      uint32_t nb = 0;
+      uint64_t used = 0, inf = 0;
+      rc = rfx_bgzf_scan(m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
+      if (nb == 0) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "rufus_amd jellyfish count: %s BGZF block at byte %llu of the compressed input",
+                 rc == RFX_OK ? "truncated" : "no", (unsigned long long)at);
+        die(msg);
+      }
+      runs.push_back({at, (size_t)used, inf});
+      blocks_ += nb;
+      at += (size_t)used;
+    }
+    int cur = 0;
+    size_t i = 0;
+    // queues runs into arena `a` until the next does not fit (false: the file is at its end)
+    auto fill = [&](rfx_text* a) {
+      for (; i < runs.size(); ++i) {
+        const Run& r = runs[i];
+        if (r.inflated > rfx_text_room(a)) return true;
+        Buf& b = ring_[next_buf_];
+        next_buf_ = (next_buf_ + 1) % ring_.size();
+        settle_buf(b);
+        memcpy(b.p, m + r.at, r.n);
+        const long tk = rfx_text_append_bgzf(a, b.p, r.n);
+        if (tk < 0) die(std::string("rufus_amd: rfx_text_append_bgzf: ") + rfx_strerror((int)tk) + " " + rfx_last_error());
+        b.t = a;
+        b.ticket = tk;
+        ++appends_;
+      }
+      return false;
+    };
+    uint64_t skip = skip0;
+    bool more = fill(arena_[cur]);
+    while (more) {
+      rfx_text* t = arena_[cur];
+      rfx_text* nx = arena_[cur ^ 1];
+      uint64_t carried = 0;
+      const uint64_t n_records = settle(t, nx, skip, &carried);
+      if (n_records == 0) die("rufus_amd jellyfish count: --bam: a record that is longer than an arena");
+      skip = 0;
+      more = fill(nx);  // queued, not waited for: the device inflates it beside this arena's count
+      parse_and_sink(t, n_records);
+      cur ^= 1;
+    }
+    uint64_t carried = 0;
+    const uint64_t n_records = settle(arena_[cur], nullptr, skip, &carried);  // (a tail: the file ends inside a record)
+    parse_and_sink(arena_[cur], n_records);
+  }
+};
+
 // ---- two bgzip'd mate files in lock step: inflated, parsed, filtered and the hit pairs' text gathered on the device -------
 // Replaces `RUFUS.Filter HashList <(zcat A) <(zcat B) STUB ...` (runRufus.sh:974-977): the host reads the two files and
 // writes the pulled records, nothing else.  Record i of A pairs with record i of B (src/RUFUS.Filter.cpp:165-173), but

@@ -1,0 +1,490 @@
+// BAM records found and packed on the device: what `samtools view -F 3328 X.bam | PassThroughSamCheck` (runRufus.sh:599,
+// scripts/RunJellyForRUFUS.sh:28, src/PassThroughSamCheck.cpp:51-155) hands `jellyfish count`, from the inflated bytes
+// rfx_text_append_bgzf leaves in a text arena.  The record layout is rfx_bam_core.h's, one source for host and device.
+//
+// A record is found only through its predecessor's block_size.  The arena is cut into tiles of T bytes (16 KiB;
+// RFX_BAM_TILE: a power of two >= 256) and the chain is found by speculate, verify, repair:
+//
+//   k_bam_guess    a wave per tile t >= 1: 64 candidate offsets at a time from the tile's first byte, the first that
+//                  bam_guess_ok accepts (a ballot) is in[t]; none: the sentinel, which equals no offset.  in[0] = skip.
+//   k_bam_walk     a lane per tile: from in[t] along bam_next until the offset is >= the tile's end -> exit[t], and the
+//                  number of records that START in the tile.  An entry behind the tile's end is passed through.
+//   k_bam_repair   one round: every t >= 1 with in[t] != exit[t - 1] takes in[t] = exit[t - 1], is walked again and
+//                  counted in `changed`.  exit[] is double-buffered, so a round reads only the round before.  The host
+//                  repeats rounds until changed == 0 (4 bytes read back per round).
+//
+// Exact and finite: tile 0 is exact; after round r tiles 0 .. r are exact and never change again (in[r] is compared with
+// an exit that is final); a fixed point has in[t] == exit[t - 1] everywhere, which IS the chain from `skip`.  A bad guess
+// costs a round, never a result, and there are at most as many rounds as tiles.
+//
+//   scan of the counts, then
+//   k_bam_starts   a lane per tile walks once more and writes rec_start[]; every record on the chain is checked with
+//                  bam_valid, the lowest failing offset kept (atomicMin)
+//
+// rfx_bam_parse, shaped as rfx_select.hip:
+//   k_bam_fields   a thread per record: flag, l_seq -> keep, code words, bases  -> three scans
+//                  (+ the longest kept read and the histogram of lengths < 32: atomics on 33 counters)
+//   k_bam_table    a thread per record: len[], word_off[], the sequence's byte offset and refID of the kept, at their rank
+//                  (l_seq == 0: the read is the `*` samtools view prints, one base that is none of ACGT)
+//   k_bam_runs     a thread per kept record: 1 where its refID differs from the kept record before it -> scan
+//   k_bam_run_out  ... and the (first kept index, refID) pairs at their rank
+//   k_bam_pack     a thread per OUTPUT code word: owner by binary search in word_off, its 16 source bytes by aligned
+//                  dwords + alignbyte, bam_pack_word
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rfx_bam_core.h"
+#include "rfx_internal.h"
+
+using rfxi::dfree;
+using rfxi::dmalloc;
+using rfxi::queue_read;
+
+namespace {
+
+constexpr uint32_t BAM_NONE = 0xFFFFFFFFu;  // no guess: an arena is shorter than 2^32 - 8192 bytes, so no offset equals it
+
+int hip_fail(hipError_t e, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
+  rfxi::set_error(msg);
+  return RFX_E_HIP;
+}
+
+__global__ __launch_bounds__(256) void k_bam_guess(const uint8_t* __restrict__ b, uint64_t end, uint32_t tile, uint32_t n_tiles,
+                                                    int32_t n_ref, uint32_t skip, int no_guess, uint32_t* __restrict__ in,
+                                                    uint32_t* __restrict__ guess) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // (wave-uniform)
+  if (t >= n_tiles) return;
+  uint32_t g = BAM_NONE;
+  if (t == 0) {
+    g = skip;
+  } else if (!no_guess) {
+    const uint64_t lo = (uint64_t)t * tile, hi = min(lo + tile, end);
+    for (uint64_t base = lo; base < hi; base += 64) {
+      const uint64_t c = base + lane;
+      const bool ok = c < hi && bam_guess_ok(b, c, end, n_ref);
+      const unsigned long long vote = __ballot(ok);
+      if (vote) {
+        g = (uint32_t)(base + (uint32_t)(__ffsll((long long)vote) - 1));
+        break;
+      }
+    }
+  }
+  if (lane == 0) {
+    in[t] = g;
+    guess[t] = g;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bam_walk(const uint8_t* __restrict__ b, uint64_t end, uint32_t tile, uint32_t n_tiles,
+                                                   const uint32_t* __restrict__ in, uint32_t* __restrict__ exit_out,
+                                                   uint64_t* __restrict__ cnt) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_tiles) return;
+  bam_no_visit nv;
+  uint32_t n = 0;
+  exit_out[t] = (uint32_t)bam_walk(b, in[t], min(((uint64_t)t + 1) * tile, end), end, &n, nv);
+  cnt[t] = n;
+}
+
+__global__ __launch_bounds__(256) void k_bam_repair(const uint8_t* __restrict__ b, uint64_t end, uint32_t tile, uint32_t n_tiles,
+                                                     uint32_t* __restrict__ in, const uint32_t* __restrict__ exit_prev,
+                                                     uint32_t* __restrict__ exit_next, uint64_t* __restrict__ cnt,
+                                                     uint32_t* __restrict__ changed) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_tiles) return;
+  if (t == 0 || in[t] == exit_prev[t - 1]) {
+    exit_next[t] = exit_prev[t];
+    return;
+  }
+  const uint32_t entry = exit_prev[t - 1];
+  in[t] = entry;
+  bam_no_visit nv;
+  uint32_t n = 0;
+  exit_next[t] = (uint32_t)bam_walk(b, entry, min(((uint64_t)t + 1) * tile, end), end, &n, nv);
+  cnt[t] = n;
+  atomicAdd(changed, 1u);
+}
+
+struct bam_start_visit {
+  const uint8_t* b;
+  uint32_t* out;
+  int32_t n_ref;
+  uint32_t* first_bad;
+  __device__ __forceinline__ void operator()(uint64_t p, uint32_t i) {
+    out[i] = (uint32_t)p;
+    if (bam_valid(b, p, n_ref) != BAM_OK) atomicMin(first_bad, (uint32_t)p);
+  }
+};
+
+// info[0] = the lowest offset of a chain record that is not bam_valid (BAM_NONE: none), info[1] = guesses repair changed
+__global__ __launch_bounds__(256) void k_bam_starts(const uint8_t* __restrict__ b, uint64_t end, uint32_t tile, uint32_t n_tiles,
+                                                     int32_t n_ref, const uint32_t* __restrict__ in,
+                                                     const uint32_t* __restrict__ guess, const uint64_t* __restrict__ off,
+                                                     uint32_t* __restrict__ rec_start, uint32_t* __restrict__ info) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_tiles) return;
+  bam_start_visit v{b, rec_start + off[t], n_ref, info};
+  uint32_t n = 0;
+  const uint64_t e = bam_walk(b, in[t], min(((uint64_t)t + 1) * tile, end), end, &n, v);  // (n == off[t + 1] - off[t])
+  if (t == n_tiles - 1) rec_start[off[n_tiles]] = (uint32_t)e;                             // the cut
+  if (guess[t] != in[t]) atomicAdd(&info[1], 1u);
+}
+
+// ---- rfx_bam_parse ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bam_fields(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
+                                                     uint64_t n_rec, uint32_t exclude, uint64_t* __restrict__ cnt,
+                                                     uint64_t* __restrict__ words, uint64_t* __restrict__ bases,
+                                                     unsigned int* __restrict__ d_stat) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = rec_start[r];
+    const bool keep = (bam_flag(b, p) & exclude) == 0;
+    const uint32_t len = max((uint32_t)bam_l_seq(b, p), 1u);  // (>= 0: rfx_bam_settle has checked every record; 0: SEQ is `*`)
+    cnt[r] = keep;
+    words[r] = keep ? (len + 31u) / 32u : 0u;
+    bases[r] = keep ? len : 0u;
+    if (keep) {
+      atomicMax(&d_stat[0], len);
+      if (len < 32u) atomicAdd(&d_stat[1u + len], 1u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bam_table(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
+                                                    uint64_t n_rec, uint32_t exclude, const uint64_t* __restrict__ cnt,
+                                                    const uint64_t* __restrict__ words, uint32_t* __restrict__ out_len,
+                                                    uint32_t* __restrict__ out_word_off, uint32_t* __restrict__ seq_at,
+                                                    int32_t* __restrict__ ref_id) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = rec_start[r];
+    if (bam_flag(b, p) & exclude) continue;
+    const uint32_t o = (uint32_t)cnt[r];  // (both totals are below 2^32: checked before this launch)
+    const uint32_t l_seq = (uint32_t)bam_l_seq(b, p);
+    out_len[o] = max(l_seq, 1u);  // (no sequence: samtools view prints `*`, one base that is none of ACGT)
+    out_word_off[o] = (uint32_t)words[r];
+    seq_at[o] = l_seq ? (uint32_t)bam_seq_offset(b, p) : BAM_NONE;
+    ref_id[o] = bam_ref_id(b, p);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bam_runs(const int32_t* __restrict__ ref_id, uint32_t n_kept, uint64_t* __restrict__ is_start) {
+  for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n_kept; o += (uint64_t)gridDim.x * blockDim.x)
+    is_start[o] = o == 0 || ref_id[o] != ref_id[o - 1];
+}
+
+__global__ __launch_bounds__(256) void k_bam_run_out(const int32_t* __restrict__ ref_id, uint32_t n_kept,
+                                                      const uint64_t* __restrict__ rank, uint32_t* __restrict__ runs) {
+  for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n_kept; o += (uint64_t)gridDim.x * blockDim.x)
+    if (rank[o + 1] != rank[o]) {  // (the exclusive scan: a start is where the rank goes up)
+      runs[2 * rank[o]] = (uint32_t)o;
+      runs[2 * rank[o] + 1] = (uint32_t)ref_id[o];
+    }
+}
+
+// the last i in [0, n) with off[i] <= x (off is non-decreasing, off[0] = 0 <= x)
+__device__ __forceinline__ uint32_t owner_of(const uint32_t* __restrict__ off, uint32_t n, uint32_t x) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// (five aligned dwords are read whatever the word needs: at most 19 bytes behind a sequence that lies inside the arena,
+// which has 8 KiB behind its capacity)
+__global__ __launch_bounds__(256) void k_bam_pack(const uint8_t* __restrict__ b, const uint32_t* __restrict__ word_off,
+                                                   const uint32_t* __restrict__ len, const uint32_t* __restrict__ seq_at,
+                                                   uint32_t n_kept, uint64_t n_words, uint64_t* __restrict__ codes,
+                                                   uint32_t* __restrict__ acgt) {
+  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n_words; x += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t o = owner_of(word_off, n_kept, (uint32_t)x);
+    const uint32_t j = (uint32_t)x - word_off[o];
+    const uint32_t nb = min(32u, len[o] - j * 32u);
+    if (seq_at[o] == BAM_NONE) {  // `*`
+      codes[x] = 0;
+      acgt[x] = 0;
+      continue;
+    }
+    const uint32_t src = seq_at[o] + j * 16u;
+    const uint32_t* w = (const uint32_t*)(b + (src & ~3u));
+    const uint32_t sh = src & 3u;
+    const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], d3 = w[3], d4 = w[4];
+    const uint32_t v[4] = {__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
+                           __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh)};
+    uint64_t c;
+    uint32_t m;
+    bam_pack_word(v, nb, &c, &m);
+    codes[x] = c;
+    acgt[x] = m;
+  }
+}
+
+uint32_t tile_bytes() {
+  if (const char* e = getenv("RFX_BAM_TILE")) {
+    const long long v = atoll(e);
+    if (v >= 256 && v <= (1 << 30) && (v & (v - 1)) == 0) return (uint32_t)v;
+  }
+  return 16384;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rfx_bam_settle(rfx_text* t, rfx_text* next, uint64_t skip, int32_t n_ref, uint64_t* n_records, uint64_t* carried) {
+  static const char* const who = "rfx_bam_settle";
+  if (!t || !carried || !n_records || next == t || n_ref < 0) return RFX_E_INVAL;
+  *carried = 0;
+  *n_records = 0;
+  if (next && (rfx_text_bytes(next) != 0 || rfxi::text_ctx(next) != rfxi::text_ctx(t))) return RFX_E_INVAL;
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t n = 0;
+  if (const int rc = rfxi::text_ready(t, &c, &arena, &n)) return rc;  // waits for the appends; a block that did not inflate
+  if (skip > n) return RFX_E_INVAL;
+  rfxi::text_bam& slot = rfxi::text_bam_of(t);
+  if (slot.rec_start) dfree(c, slot.rec_start);
+  slot = rfxi::text_bam();
+  memset(c->bam_stats, 0, sizeof c->bam_stats);
+  if (n == 0) {
+    slot.settled = true;
+    slot.n_ref = n_ref;
+    return RFX_OK;
+  }
+  const uint32_t T = tile_bytes();
+  const uint32_t n_tiles = (uint32_t)((n + T - 1) / T);
+  const int no_guess = getenv("RFX_BAM_NO_GUESS") != nullptr && atoi(getenv("RFX_BAM_NO_GUESS")) != 0;
+  uint32_t* u32s = (uint32_t*)dmalloc(c, ((size_t)4 * n_tiles + 4) * 4);  // in, guess, exit x 2, changed, info[2]
+  uint64_t* cnt = (uint64_t*)dmalloc(c, ((size_t)n_tiles + 1) * 8);
+  uint32_t* rec_start = nullptr;
+  auto fail = [&](int rc, hipError_t e) {
+    if (e != hipSuccess) hip_fail(e, who);
+    (void)rfxi::sync(c);  // (queued read-backs point at locals of this function: deliver them now)
+    dfree(c, u32s);
+    dfree(c, cnt);
+    dfree(c, rec_start);
+    return rc;
+  };
+  if (!u32s || !cnt) return fail(RFX_E_NOMEM, hipSuccess);
+  uint32_t *in = u32s, *guess = u32s + n_tiles, *ex[2] = {u32s + 2 * (size_t)n_tiles, u32s + 3 * (size_t)n_tiles};
+  uint32_t *changed = u32s + 4 * (size_t)n_tiles, *info = changed + 1;
+  const dim3 per_tile((n_tiles + 255) / 256), per_wave((n_tiles + 3) / 4);
+  {
+    rfx_span sp(c, "k_bam_guess");
+    hipLaunchKernelGGL(k_bam_guess, per_wave, dim3(256), 0, c->stream, arena, n, T, n_tiles, n_ref, (uint32_t)skip, no_guess, in, guess);
+  }
+  {
+    rfx_span sp(c, "k_bam_walk");
+    hipLaunchKernelGGL(k_bam_walk, per_tile, dim3(256), 0, c->stream, arena, n, T, n_tiles, in, ex[0], cnt);
+  }
+  uint64_t rounds = 0;
+  int cur = 0;
+  for (;;) {
+    hipError_t e = hipMemsetAsync(changed, 0, 4, c->stream);
+    if (e != hipSuccess) return fail(RFX_E_HIP, e);
+    {
+      rfx_span sp(c, "k_bam_repair");
+      hipLaunchKernelGGL(k_bam_repair, per_tile, dim3(256), 0, c->stream, arena, n, T, n_tiles, in, ex[cur], ex[cur ^ 1], cnt, changed);
+    }
+    uint32_t h_changed = 0;
+    e = queue_read(c, &h_changed, changed, 4);
+    if (e == hipSuccess) e = rfxi::sync(c);
+    if (e != hipSuccess) return fail(RFX_E_HIP, e);
+    cur ^= 1;
+    if (!h_changed) break;
+    if (++rounds > n_tiles) {  // (cannot happen: round r settles tile r)
+      rfxi::set_error("rfx_bam_settle: the record chain did not settle");
+      return fail(RFX_E_HIP, hipSuccess);
+    }
+  }
+  rfxk::scan_tail(c, cnt, n_tiles);
+  uint64_t n_rec = 0;
+  uint32_t cut = 0;
+  hipError_t e = queue_read(c, &n_rec, cnt + n_tiles, 8);
+  if (e == hipSuccess) e = queue_read(c, &cut, ex[cur] + (n_tiles - 1), 4);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return fail(RFX_E_HIP, e);
+  if (cut > n || cut < skip || n_rec > n / 4) {
+    rfxi::set_error("rfx_bam_settle: the cut lies outside the arena");
+    return fail(RFX_E_HIP, hipSuccess);
+  }
+  rec_start = (uint32_t*)dmalloc(c, ((size_t)n_rec + 1) * 4);
+  if (!rec_start) return fail(RFX_E_NOMEM, hipSuccess);
+  const uint32_t info0[2] = {BAM_NONE, 0};
+  e = hipMemcpyAsync(info, info0, 8, hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess) return fail(RFX_E_HIP, e);
+  {
+    rfx_span sp(c, "k_bam_starts");
+    hipLaunchKernelGGL(k_bam_starts, per_tile, dim3(256), 0, c->stream, arena, n, T, n_tiles, n_ref, in, guess, cnt, rec_start, info);
+  }
+  uint32_t h_info[2] = {BAM_NONE, 0};
+  e = queue_read(c, h_info, info, 8);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return fail(RFX_E_HIP, e);
+  c->bam_stats[0] = n_tiles;
+  c->bam_stats[1] = h_info[1];
+  c->bam_stats[2] = rounds;
+  c->bam_stats[3] = n_rec;
+  if (h_info[0] != BAM_NONE) {  // the lowest failing record: its fixed fields say why (a chain record is whole)
+    uint8_t head[BAM_FIXED];
+    memset(head, 0, sizeof head);
+    const uint64_t have = std::min<uint64_t>(BAM_FIXED, n - h_info[0]);
+    e = hipMemcpy(head, arena + h_info[0], have, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(RFX_E_HIP, e);
+    char msg[200];
+    snprintf(msg, sizeof msg, "rfx_bam: record at byte %u: %s", h_info[0], bam_status_text(bam_valid(head, 0, n_ref)));
+    rfxi::set_error(msg);
+    return fail(RFX_E_FORMAT, hipSuccess);
+  }
+  // a first record that does not end inside an arena no further block fits into: no arena of this size ever holds it
+  if (n_rec == 0 && cut < n && rfx_text_room(t) < 65536) {
+    rfxi::set_error("rfx_bam_settle: the first record does not end inside a full arena");
+    return fail(RFX_E_RANGE, hipSuccess);
+  }
+  if (const int rc = rfxi::text_cut(t, next, cut, carried, who)) return fail(rc, hipSuccess);
+  dfree(c, u32s);
+  dfree(c, cnt);
+  slot.rec_start = rec_start;
+  slot.n_records = n_rec;
+  slot.n_ref = n_ref;
+  slot.settled = true;
+  *n_records = n_rec;
+  return RFX_OK;
+}
+
+int rfx_bam_stats(const rfx_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return RFX_E_INVAL;
+  memcpy(out, c->bam_stats, sizeof c->bam_stats);
+  return RFX_OK;
+}
+
+rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs, uint64_t cap, uint64_t* n_runs) {
+  static const char* const who = "rfx_bam_parse";
+  char msg[256];
+  if (n_runs) *n_runs = 0;
+  if (!t || !n_runs || (!ref_runs && cap)) {
+    rfxi::set_error("rfx_bam_parse: RFX_E_INVAL: a NULL argument");
+    return nullptr;
+  }
+  rfxi::text_bam& slot = rfxi::text_bam_of(t);
+  if (!slot.settled) {
+    rfxi::set_error("rfx_bam_parse: RFX_E_INVAL: the arena has not been settled with rfx_bam_settle since its last reset");
+    return nullptr;
+  }
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t n = 0;
+  if (rfxi::text_ready(t, &c, &arena, &n) != RFX_OK) return nullptr;
+  const uint64_t R = slot.n_records;
+  rfx_reads* r = new rfx_reads();
+  memset(r, 0, sizeof *r);
+  r->gen = rfx_next_reads_gen();
+  r->ctx = c;
+  uint64_t* cnt = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  uint64_t* words = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  uint64_t* bases = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  unsigned int* d_stat = (unsigned int*)dmalloc(c, 33 * 4);  // [0] longest kept read, [1 + l] kept reads of l < 32 bases
+  uint32_t* seq_at = nullptr;
+  int32_t* ref_id = nullptr;
+  uint64_t* run_rank = nullptr;
+  uint32_t* d_runs = nullptr;
+  auto fail = [&](hipError_t e, const char* code, const char* text) -> rfx_reads* {
+    snprintf(msg, sizeof msg, "%s: %s: %s", who, code, e != hipSuccess ? hipGetErrorString(e) : text);
+    (void)rfxi::sync(c);  // (queued read-backs point at locals of this function: deliver them now)
+    rfxi::set_error(msg);
+    dfree(c, cnt); dfree(c, words); dfree(c, bases); dfree(c, d_stat); dfree(c, seq_at); dfree(c, ref_id); dfree(c, run_rank);
+    dfree(c, d_runs);
+    rfx_reads_free(r);
+    return nullptr;
+  };
+  if (!cnt || !words || !bases || !d_stat) return fail(hipSuccess, "RFX_E_NOMEM", "out of device memory");
+  auto grid_of = [&](uint64_t m, int per_cu) { return dim3((unsigned)std::min<uint64_t>((m + 255) / 256, (uint64_t)c->n_cu * per_cu)); };
+  uint64_t totals[3] = {0, 0, 0};  // kept reads, words, bases
+  unsigned int h_stat[33];
+  memset(h_stat, 0, sizeof h_stat);
+  if (R) {
+    hipError_t e = hipMemsetAsync(d_stat, 0, 33 * 4, c->stream);
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+    {
+      rfx_span sp(c, "k_bam_fields");
+      hipLaunchKernelGGL(k_bam_fields, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+                         bases, d_stat);
+    }
+    rfxk::scan_tail(c, cnt, R);
+    rfxk::scan_tail(c, words, R);
+    rfxk::scan_tail(c, bases, R);
+    e = queue_read(c, &totals[0], cnt + R, 8);
+    if (e == hipSuccess) e = queue_read(c, &totals[1], words + R, 8);
+    if (e == hipSuccess) e = queue_read(c, &totals[2], bases + R, 8);
+    if (e == hipSuccess) e = queue_read(c, h_stat, d_stat, sizeof h_stat);
+    if (e == hipSuccess) e = rfxi::sync(c);  // the first wait: the totals the result is allocated by
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  }
+  const uint64_t S = totals[0], W = totals[1];
+  if (S >= (1ull << 32) || W >= (1ull << 32)) return fail(hipSuccess, "RFX_E_RANGE", "the block would reach 2^32 reads or words");
+  r->n = (uint32_t)S;
+  r->n_words = W;
+  r->n_bases = totals[2];
+  r->max_len = h_stat[0];
+  for (int l = 0; l < 32; ++l) r->short_cnt[l] = h_stat[1 + l];
+  r->codes = (uint64_t*)dmalloc(c, std::max<uint64_t>(W, 1) * 8);
+  r->acgt = (uint32_t*)dmalloc(c, std::max<uint64_t>(W, 1) * 4);
+  r->word_off = (uint32_t*)dmalloc(c, ((size_t)S + 1) * 4);
+  r->len = (uint32_t*)dmalloc(c, std::max<uint64_t>(S, 1) * 4);
+  seq_at = (uint32_t*)dmalloc(c, std::max<uint64_t>(S, 1) * 4);
+  ref_id = (int32_t*)dmalloc(c, std::max<uint64_t>(S, 1) * 4);
+  run_rank = (uint64_t*)dmalloc(c, (S + 1) * 8);
+  if (!r->codes || !r->acgt || !r->word_off || !r->len || !seq_at || !ref_id || !run_rank)
+    return fail(hipSuccess, "RFX_E_NOMEM", "out of device memory");
+  const uint32_t w_end = (uint32_t)W;
+  uint64_t runs = 0;
+  hipError_t e = hipMemcpyAsync(r->word_off + S, &w_end, 4, hipMemcpyHostToDevice, c->stream);  // (w_end lives until the wait below)
+  if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  if (S) {
+    {
+      rfx_span sp(c, "k_bam_table");
+      hipLaunchKernelGGL(k_bam_table, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+                         r->len, r->word_off, seq_at, ref_id);
+    }
+    {
+      rfx_span sp(c, "k_bam_runs");
+      hipLaunchKernelGGL(k_bam_runs, grid_of(S, 16), dim3(256), 0, c->stream, ref_id, (uint32_t)S, run_rank);
+    }
+    rfxk::scan_tail(c, run_rank, S);
+    e = queue_read(c, &runs, run_rank + S, 8);
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+    if (W) {
+      rfx_span sp(c, "k_bam_pack");
+      hipLaunchKernelGGL(k_bam_pack, grid_of(W, 32), dim3(256), 0, c->stream, arena, r->word_off, r->len, seq_at, (uint32_t)S, W,
+                         r->codes, r->acgt);
+    }
+  }
+  e = rfxi::sync(c);  // the second wait: the block is packed, the number of runs is known
+  if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  *n_runs = runs;
+  if (runs > cap) return fail(hipSuccess, "RFX_E_RANGE", "more reference runs than the caller has room for");
+  if (runs) {
+    d_runs = (uint32_t*)dmalloc(c, runs * 8);
+    if (!d_runs) return fail(hipSuccess, "RFX_E_NOMEM", "out of device memory");
+    {
+      rfx_span sp(c, "k_bam_run_out");
+      hipLaunchKernelGGL(k_bam_run_out, grid_of(S, 16), dim3(256), 0, c->stream, ref_id, (uint32_t)S, run_rank, d_runs);
+    }
+    e = hipMemcpyAsync(ref_runs, d_runs, runs * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = rfxi::sync(c);
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  }
+  dfree(c, cnt); dfree(c, words); dfree(c, bases); dfree(c, d_stat); dfree(c, seq_at); dfree(c, ref_id); dfree(c, run_rank);
+  dfree(c, d_runs);
+  return r;
+}
+
+}  // extern "C"

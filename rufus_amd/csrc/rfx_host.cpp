@@ -197,6 +197,102 @@ int rfx_bgzf_scan(const void* buf, uint64_t n, uint32_t max_blocks, uint32_t* n_
   return rc;
 }
 
+// The BAM header, inflated with the host side of rfx_bgzf_core.h (a serial copy as its output policy).
+namespace {
+struct SerialInflate {
+  uint8_t* out;
+  void literal(uint32_t pos, uint32_t byte) { out[pos] = (uint8_t)byte; }
+  void match(uint32_t pos, uint32_t len, uint32_t dist) {
+    for (uint32_t i = 0; i < len; ++i) out[pos + i] = out[pos - dist + i % dist];
+  }
+  void stored(uint32_t pos, const uint8_t* src, uint32_t n) { memcpy(out + pos, src, n); }
+  void end() {}
+};
+inline uint32_t le32(const std::vector<uint8_t>& v, uint64_t i) {
+  return v[i] | (uint32_t)v[i + 1] << 8 | (uint32_t)v[i + 2] << 16 | (uint32_t)v[i + 3] << 24;
+}
+// 1: the header is whole in v (*end_at = its length, the names appended to *names), 0: not yet, -1: not BAM
+int bam_header_parse(const std::vector<uint8_t>& v, uint64_t* end_at, int32_t* n_ref, std::string* names) {
+  static const uint8_t magic[4] = {'B', 'A', 'M', 1};
+  for (size_t i = 0; i < 4 && i < v.size(); ++i)
+    if (v[i] != magic[i]) return -1;
+  if (v.size() < 8) return 0;
+  const int32_t l_text = (int32_t)le32(v, 4);
+  if (l_text < 0) return -1;
+  uint64_t at = 8ull + (uint32_t)l_text;
+  if (v.size() < at + 4) return 0;
+  const int32_t nr = (int32_t)le32(v, at);
+  if (nr < 0) return -1;
+  at += 4;
+  names->clear();
+  for (int32_t i = 0; i < nr; ++i) {
+    if (v.size() < at + 4) return 0;
+    const int32_t l_name = (int32_t)le32(v, at);
+    if (l_name < 1) return -1;
+    if (v.size() < at + 4 + (uint64_t)l_name + 4) return 0;
+    if (v[at + 4 + (uint64_t)l_name - 1] != 0) return -1;
+    names->append((const char*)&v[at + 4], (size_t)l_name);
+    at += 4 + (uint64_t)l_name + 4;
+  }
+  *n_ref = nr;
+  *end_at = at;
+  return 1;
+}
+}  // namespace
+
+int rfx_bam_header(const void* buf, uint64_t n, int* complete, int32_t* n_ref, char* names, uint64_t names_cap,
+                   uint64_t* names_bytes, uint64_t* first_block, uint32_t* skip) {
+  if ((!buf && n) || !complete || !n_ref || !names_bytes || !first_block || !skip) return RFX_E_INVAL;
+  *complete = 0;
+  *n_ref = 0;
+  *names_bytes = 0;
+  *first_block = 0;
+  *skip = 0;
+  const uint8_t* b = (const uint8_t*)buf;
+  std::vector<uint8_t> text;
+  std::vector<uint64_t> block_at, text_at;  // of every block inflated so far: its compressed offset, where its bytes begin
+  std::vector<bgzf_tables> tables(1);
+  std::string all_names;
+  uint64_t at = 0;
+  for (;;) {
+    uint64_t end_at = 0;
+    const int h = bam_header_parse(text, &end_at, n_ref, &all_names);
+    if (h < 0) return RFX_E_FORMAT;
+    if (h == 1) {
+      *first_block = at;  // a header that ends with its block: the block behind it
+      for (size_t i = 0; i < block_at.size(); ++i) {
+        const uint64_t hi = i + 1 < text_at.size() ? text_at[i + 1] : text.size();
+        if (text_at[i] <= end_at && end_at < hi) {
+          *first_block = block_at[i];
+          *skip = (uint32_t)(end_at - text_at[i]);
+          break;
+        }
+      }
+      *names_bytes = all_names.size();
+      *complete = 1;
+      if (names) {
+        if (all_names.size() > names_cap) return RFX_E_RANGE;
+        memcpy(names, all_names.data(), all_names.size());
+      }
+      return RFX_OK;
+    }
+    if (at >= n) return RFX_OK;  // not whole in these bytes
+    uint32_t bsize, pay_off, pay_len, isize, crc;
+    const int bh = bgzf_block_header(b + at, n - at, &bsize, &pay_off, &pay_len, &isize, &crc);
+    if (bh < 0) return RFX_E_FORMAT;
+    if (bh > 0) return RFX_OK;  // the next block is not whole
+    const size_t was = text.size();
+    text.resize(was + isize);
+    SerialInflate so{text.data() + was};
+    const uint8_t* pay = b + at + pay_off;
+    if (bgzf_inflate(pay, pay + pay_len, isize, tables[0], so) != BGZF_OK) return RFX_E_FORMAT;
+    if (~bgzf_crc_update(0xFFFFFFFFu, text.data() + was, isize) != crc) return RFX_E_FORMAT;
+    block_at.push_back(at);
+    text_at.push_back(was);
+    at += bsize;
+  }
+}
+
 int rfx_jf_matrix(int lsize, int k, uint64_t* cols) {
   const int r = lsize, c = 2 * k;
   if (r < 1 || r > 64 || k < 1 || c < r || !cols) return RFX_E_INVAL;

@@ -68,6 +68,8 @@ struct rfx_ctx {
   // (all of them when k_strike_wave did not run), and whether it ran
   uint64_t strike_units = 0, strike_deferred = 0;
   bool strike_by_wave = false;
+  // the last rfx_bam_settle (rfx_bam_stats): tiles, guesses that repair had to change, repair rounds, records
+  uint64_t bam_stats[4] = {0, 0, 0, 0};
   // ... and by the last emit of a table of (about) the same number of k-mer instances: a driver that counts samples of
   // different depth in turn (tumor 60x / normal 30x: BASELINE configs[4]) finds each sample's own ratio, not its
   // predecessor's -- the normal's store was sized by the tumor's ratio, half its own, overflowed, and the whole leaf
@@ -569,6 +571,20 @@ int text_ready(rfx_text* t, rfx_ctx** c, const uint8_t** arena, uint64_t* used);
 hipError_t text_count_lines(rfx_ctx*, const uint8_t* arena, uint64_t n, uint64_t* tile_off);
 hipError_t text_line_starts(rfx_ctx*, const uint8_t* arena, uint64_t n, const uint64_t* tile_off, uint32_t* line_start,
                             uint64_t max_lines);
+// What rfx_bam.hip needs of an arena.  text_cut is rfx_text_settle's tail move: the arena is shortened to `cut` bytes and
+// what lay behind moves, device to device, to the front of `next` (empty, of the same ctx: the caller has checked);
+// next == NULL with a tail is RFX_E_FORMAT "<who>: the text ends inside a record", a tail beyond next's capacity
+// RFX_E_RANGE.  text_bam_of: the record starts rfx_bam_settle found (device, n_records + 1 entries, the last one the
+// cut; allocated with dmalloc), which belong to the arena: rfx_text_reset and rfx_text_close free them.
+struct text_bam {
+  uint32_t* rec_start = nullptr;
+  uint64_t n_records = 0;
+  int32_t n_ref = 0;
+  bool settled = false;
+};
+rfx_ctx* text_ctx(rfx_text* t);
+text_bam& text_bam_of(rfx_text* t);
+int text_cut(rfx_text* t, rfx_text* next, uint64_t cut, uint64_t* carried, const char* who);
 }  // namespace rfxi
 
 // Launch bracket: records a HIP-event span on the ctx stream (or `stream`: an arena's own, rfx_text.hip) when profiling

@@ -262,6 +262,7 @@ struct rfx_text {
   uint32_t* first_bad = nullptr;  // device: the lowest index of a block that failed, or ~0
   bool bgzf_failed = false;
   std::string bgzf_msg;
+  rfxi::text_bam bam;  // rfx_bam.hip: the record starts of the last rfx_bam_settle, kept until the reset
 };
 
 namespace {
@@ -320,6 +321,29 @@ int text_ready(rfx_text* t, rfx_ctx** c, const uint8_t** arena, uint64_t* used) 
   *c = t->ctx;
   *arena = t->arena;
   *used = t->used;
+  return RFX_OK;
+}
+
+rfx_ctx* text_ctx(rfx_text* t) { return t->ctx; }
+text_bam& text_bam_of(rfx_text* t) { return t->bam; }
+
+int text_cut(rfx_text* t, rfx_text* next, uint64_t cut, uint64_t* carried, const char* who) {
+  rfx_ctx* c = t->ctx;
+  const uint64_t n = t->used;
+  const uint64_t tail = n - cut;
+  if (tail) {
+    if (!next) {
+      rfxi::set_error((std::string(who) + ": the text ends inside a record").c_str());
+      return RFX_E_FORMAT;
+    }
+    if (tail > next->cap) return RFX_E_RANGE;
+    HIPCHK(hipMemcpyAsync(next->arena, t->arena + cut, tail, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(ctx_sync(c));
+    std::lock_guard<std::mutex> g(next->mu);
+    next->used = tail;
+  }
+  t->used = cut;
+  *carried = tail;
   return RFX_OK;
 }
 
@@ -386,6 +410,7 @@ void rfx_text_close(rfx_text* t) {
     (void)hipEventDestroy(t->staged);
     (void)hipFree(t->first_bad);
   }
+  dfree(t->ctx, t->bam.rec_start);
   for (auto& ch : t->stage) (void)hipFree(ch.p);
   for (hipEvent_t e : t->ev) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(t->copy);
@@ -461,6 +486,8 @@ void rfx_text_reset(rfx_text* t) {
   std::lock_guard<std::mutex> g(t->mu);
   t->n_ev = 0;
   t->used = 0;
+  if (t->bam.rec_start) dfree(t->ctx, t->bam.rec_start);
+  t->bam = rfxi::text_bam();
   if (t->n_bgzf_blocks) {
     if (t->stage.size() > 1) {  // one chunk of the size that was needed, next time
       size_t all = 0;
@@ -611,20 +638,7 @@ static int settle_at(rfx_text* t, rfx_text* next, uint64_t max_records, uint64_t
     rfxi::set_error((std::string(who) + ": the cut lies behind the text").c_str());
     return RFX_E_HIP;
   }
-  const uint64_t tail = n - cut;
-  if (tail) {
-    if (!next) {
-      rfxi::set_error((std::string(who) + ": the text ends inside a record").c_str());
-      return RFX_E_FORMAT;
-    }
-    if (tail > next->cap) return RFX_E_RANGE;
-    HIPCHK(hipMemcpyAsync(next->arena, t->arena + cut, tail, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(ctx_sync(c));
-    std::lock_guard<std::mutex> g(next->mu);
-    next->used = tail;
-  }
-  t->used = cut;
-  *carried = tail;
+  if (const int rc = rfxi::text_cut(t, next, cut, carried, who)) return rc;
   if (records) *records = n_rec;
   return RFX_OK;
 }

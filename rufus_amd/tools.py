@@ -20,6 +20,7 @@ counting, sorting, set difference, read scan) runs in the HIP kernels behind ``r
 from __future__ import annotations
 
 import json
+import zlib
 
 import numpy as np
 
@@ -163,14 +164,65 @@ class JhashFile:
         return cls(rec, cols, bool(hdr.get("canonical", False)), hdr["counter_len"])
 
 
+def is_bam(data: bytes) -> bool:
+    """A BGZF file whose first block inflates to the BAM magic."""
+    if data[:4] != b"\x1f\x8b\x08\x04":
+        return False
+    try:
+        nb, used, _ = capi.bgzf_scan(data[:1 << 16], 1)
+        return nb == 1 and zlib.decompress(data[:used], 31)[:4] == b"BAM\x01"
+    except (capi.RufusError, zlib.error):
+        return False
+
+
+def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, arena_bytes: int = 256 << 20):
+    """The records of a BAM file with flag & exclude_flags == 0 as count blocks, an arena at a time: yields (block, runs,
+    reference names) -- what `samtools view -F 3328 X.bam | PassThroughSamCheck` hands the counter, found and packed on the
+    device (capi.bam_header, TextArena.append_bgzf / bam_settle / bam_parse).  The caller frees the blocks."""
+    hdr = capi.bam_header(data)
+    if hdr is None:
+        raise ValueError("the BAM header is not whole")
+    arenas = [capi.TextArena(ctx, arena_bytes), capi.TextArena(ctx, arena_bytes)]
+    try:
+        at, cur, skip = hdr["first_block"], 0, hdr["skip"]
+        while True:
+            a = arenas[cur]
+            while at < len(data) and a.bytes + 65536 <= arena_bytes:
+                nb, used, _ = capi.bgzf_scan(data[at:at + (8 << 20)], min((arena_bytes - a.bytes) // 65536, 4096))
+                if nb == 0:
+                    raise ValueError(f"no whole BGZF block at byte {at} of the BAM file")
+                a.append_bgzf(data[at:at + used])
+                at += used
+            last = at >= len(data)
+            n, _ = a.bam_settle(None if last else arenas[cur ^ 1], skip, hdr["n_ref"])
+            skip = 0
+            if n:
+                blk, runs = a.bam_parse(exclude_flags)
+                yield blk, runs, hdr["names"]
+            a.reset()
+            if last:
+                break
+            cur ^= 1
+    finally:
+        for a in arenas:
+            a.close()
+
+
 def jellyfish_count(ctx: capi.Context, inputs, k: int, size: int, canonical: bool = True, lower: int = 0,
                     upper: int = 2**64 - 1, out: str | None = None, capacity: int = 0, argv=(),
                     mode: int = capi.COUNT_AUTO) -> JhashFile:
-    """Count the k-mers of FASTA/FASTQ files (paths or bytes)."""
+    """Count the k-mers of FASTA/FASTQ files (paths or bytes); a BAM file is counted as `samtools view -F 3328` of it."""
     table = capi.CountTable(ctx, k, size, canonical, capacity, mode=mode)
     try:
         for src in inputs:
             data = src if isinstance(src, (bytes, bytearray)) else open(src, "rb").read()
+            if is_bam(bytes(data)):
+                for block, _, _ in bam_read_blocks(ctx, bytes(data)):
+                    try:
+                        table.add(block)
+                    finally:
+                        block.free()
+                continue
             seqs = parse_sequences(bytes(data))
             block = ctx.upload(capi.PackedReads.from_reads(seqs, flags=capi.PACK_COUNT))
             try:
