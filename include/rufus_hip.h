@@ -330,6 +330,56 @@ int rfx_bam_settle(rfx_text* t, rfx_text* next, uint64_t skip, int32_t n_ref, ui
 rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs, uint64_t cap, uint64_t* n_runs);
 int rfx_bam_stats(const rfx_ctx*, uint64_t out[4]);
 
+/* -------------------------------------------------------------------------------------------
+ * BAM in, for the filter: the subject's records scanned as the stranded feeder prints them, and the records of the hit
+ * names pulled out of the arena -- on the device
+ * Replaces the read pull's generator, `samtools view -F 3328 X.bam | PassThroughSamCheck.stranded CHR STUB.temp |
+ * RUFUS.Filter` (runRufus.sh:964-967).  All five work on an arena settled by rfx_bam_settle (else RFX_E_INVAL; the
+ * error texts begin with the function's name) and look at the records with (flag & exclude_flags) == 0, the KEPT
+ * records, numbered in file order.  Masks are host memory, ceil(n_kept / 64) words, bit i % 64 of word i / 64 = kept
+ * record i; input bits at and above n_kept are ignored.  An arena with no kept record and an empty selection are valid.
+ * The per-base and per-name rules are rufus_amd/csrc/rfx_bam_core.h's, one source for host and device.
+ *
+ * rfx_bam_parse_filter (replaces src/PassThroughSamCheck.stranded.cpp:184-281 and the packing in front of
+ * src/RUFUS.Filter.cpp:196-277): the kept records as a filter block -- codes, `good`, offsets and lengths byte for byte
+ * what the host packer makes, with RFX_PACK_FILTER and min_q, of the SEQ / QUAL strings the stranded feeder prints:
+ * SEQ = "=ACMGRSVTWYHKDBN"[nibble], `*` for l_seq == 0; QUAL = 33 + min(q, 93), `*` for l_seq == 0 or qual[0] == 0xFF;
+ * a record with flag & 16 reversed and complemented, every base other than A C G T N dropped (the read gets shorter,
+ * down to 0 bases), its whole quality string reversed, so that position j of the read meets reversed quality j; a
+ * position without a quality character is bad.  No ACGT mask: the block is for the scan.  ref_runs / cap / n_runs and
+ * the failures are rfx_bam_parse's, under this function's name.
+ *
+ * rfx_bam_name_hashes (replaces the QNAME column of runRufus.sh:964's stream as the key the mates are found by): out[j]
+ * = the hash of the QNAME -- the name field's bytes up to its first NUL; FNV-1a, then the splitmix64 finaliser -- of
+ * the j-th kept record whose mask bit is set (mask == NULL: of every kept record).  n_kept must be the arena's number
+ * of kept records (RFX_E_INVAL).  *n = the selected records; more than cap: RFX_E_RANGE with *n set, nothing written.
+ *
+ * rfx_nameset_build / rfx_nameset_size / rfx_nameset_free (replace the name -> waiting-mate map of
+ * src/PassThroughSamCheck.stranded.cpp:225-281 as the thing that finds a hit record's mate): a set of 64-bit hashes in
+ * device memory; any values, duplicates count once.  NULL on failure.
+ *
+ * rfx_bam_mark_names: mask_out bit i = the name hash of kept record i is in the set; *n_kept = the arena's kept records
+ * (mask_out must hold ceil(*n_kept / 64) words: the arena's record count always suffices), *n_marked (may be NULL) = the
+ * set bits.  A hash collision marks a record too many, never one too few.
+ *
+ * rfx_bam_gather (replaces the output loop of src/RUFUS.Filter.cpp:237-277 on records the host never saw): for every
+ * set bit of mask, ascending, the record's bytes from its block_size field to its end, as they lie, concatenated, to
+ * host_out.  *bytes = the bytes of the selection, *n_selected (may be NULL) its records; cap too small: RFX_E_RANGE
+ * with *bytes set and nothing written.  One wait for the device between the mask upload and the copy of the result.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rfx_nameset rfx_nameset;
+rfx_reads* rfx_bam_parse_filter(rfx_text* t, uint32_t exclude_flags, int min_q, uint32_t* ref_runs, uint64_t cap,
+                                uint64_t* n_runs);
+int rfx_bam_name_hashes(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, uint64_t n_kept, uint64_t* out, uint64_t cap,
+                        uint64_t* n);
+rfx_nameset* rfx_nameset_build(rfx_ctx*, const uint64_t* hashes, uint64_t n);
+uint64_t rfx_nameset_size(const rfx_nameset*);
+void rfx_nameset_free(rfx_nameset*);
+int rfx_bam_mark_names(rfx_text* t, uint32_t exclude_flags, const rfx_nameset*, uint64_t* mask_out, uint64_t* n_kept,
+                       uint64_t* n_marked);
+int rfx_bam_gather(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, uint64_t n_kept, void* host_out, uint64_t cap,
+                   uint64_t* bytes, uint64_t* n_selected);
+
 /* Synthetic trio workload (BASELINE.json configs[1]-[4]) -- benchmark and scale-test input,
  * not a replacement of any reference code.  Every base is a pure function of (parameters, pair, mate, base
  * index) -- see rufus_amd/csrc/rfx_synth.h -- so a 30x WGS sample (6.2e8 reads) is generated straight into

@@ -108,6 +108,13 @@ SIGNATURES = {
     "rfx_bam_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, u64p, u64p]),
     "rfx_bam_parse": (C.c_void_p, [C.c_void_p, C.c_uint32, u32p, C.c_uint64, u64p]),
     "rfx_bam_stats": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_bam_parse_filter": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_int, u32p, C.c_uint64, u64p]),
+    "rfx_bam_name_hashes": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_uint64, u64p, C.c_uint64, u64p]),
+    "rfx_nameset_build": (C.c_void_p, [C.c_void_p, u64p, C.c_uint64]),
+    "rfx_nameset_size": (C.c_uint64, [C.c_void_p]),
+    "rfx_nameset_free": (None, [C.c_void_p]),
+    "rfx_bam_mark_names": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u64p, u64p]),
+    "rfx_bam_gather": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]),
     "rfx_reads_of_length": (C.c_uint64, [C.c_void_p, C.c_uint32]),
     "rfx_synth_text": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rfx_synth_snv": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_char_p, C.c_char_p]),
@@ -502,15 +509,67 @@ class TextArena:
     def bam_parse(self, exclude_flags: int = 3328):
         """(block, runs): the records with flag & exclude_flags == 0 of an arena settled by bam_settle as a count block, and
         an (n_runs, 2) int64 array of (first kept index, refID) wherever the kept records' refID changes (rfx_bam_parse)."""
+        return self._bam_block("rfx_bam_parse", lambda runs, cap, n: lib().rfx_bam_parse(self._h, exclude_flags, runs, cap, n))
+
+    def _bam_block(self, what, call):
         cap = max(getattr(self, "_bam_records", 0), 1)
         runs = np.zeros(2 * cap, np.uint32)
         n_runs = C.c_uint64(0)
-        h = lib().rfx_bam_parse(self._h, exclude_flags, _p(runs, u32p), cap, C.byref(n_runs))
+        h = call(_p(runs, u32p), cap, C.byref(n_runs))
         if not h:
-            raise RufusError("rfx_bam_parse failed: " + lib().rfx_last_error().decode())
+            raise RufusError(what + " failed: " + lib().rfx_last_error().decode())
         pairs = runs[:2 * int(n_runs.value)].reshape(-1, 2)
         out = np.stack([pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int32).astype(np.int64)], axis=1)
         return ReadBlock.from_handle(self.ctx, h), out
+
+    def bam_parse_filter(self, min_q: int, exclude_flags: int = 3328):
+        """(block, runs) as bam_parse, the block in the stranded filter form: what PACK_FILTER with min_q makes of the
+        records as the stranded feeder prints them (rfx_bam_parse_filter)."""
+        return self._bam_block("rfx_bam_parse_filter",
+                               lambda runs, cap, n: lib().rfx_bam_parse_filter(self._h, exclude_flags, min_q, runs, cap, n))
+
+    def bam_name_hashes(self, n_kept: int, mask: "np.ndarray | None" = None, exclude_flags: int = 3328) -> np.ndarray:
+        """The QNAME hashes (uint64) of the kept records whose bit is set in `mask` (None: of all n_kept), in file order
+        (rfx_bam_name_hashes)."""
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            if len(mask) < (n_kept + 63) // 64:
+                raise ValueError("mask too short")
+        out = np.zeros(max(n_kept, 1), np.uint64)
+        n = C.c_uint64(0)
+        _check(lib().rfx_bam_name_hashes(self._h, exclude_flags, _p(mask, u64p) if mask is not None and len(mask) else None, n_kept,
+                                         _p(out, u64p), n_kept, C.byref(n)), "rfx_bam_name_hashes")
+        return out[:int(n.value)].copy()
+
+    def bam_mark_names(self, names: "NameSet", exclude_flags: int = 3328):
+        """(mask, kept records, marked records): bit i of the uint64 mask = the name hash of kept record i is in `names`
+        (rfx_bam_mark_names)."""
+        mask = np.zeros((max(getattr(self, "_bam_records", 0), 1) + 63) // 64, np.uint64)
+        n_kept, n_marked = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rfx_bam_mark_names(self._h, exclude_flags, names._h, _p(mask, u64p), C.byref(n_kept), C.byref(n_marked)),
+               "rfx_bam_mark_names")
+        return mask[:(int(n_kept.value) + 63) // 64].copy(), int(n_kept.value), int(n_marked.value)
+
+    def bam_gather_into(self, mask: np.ndarray, n_kept: int, out: np.ndarray, cap: "int | None" = None, exclude_flags: int = 3328):
+        """rfx_bam_gather into `out` (uint8; cap: what the call is told the buffer holds, default all of it):
+        (return code, bytes, records selected).  E_RANGE: bytes = the need, nothing written."""
+        mask = np.ascontiguousarray(mask, dtype=np.uint64)
+        if len(mask) < (n_kept + 63) // 64:
+            raise ValueError("mask too short")
+        nb, ns = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().rfx_bam_gather(self._h, exclude_flags, _p(mask, u64p) if len(mask) else None, n_kept,
+                                  out.ctypes.data_as(C.c_void_p), len(out) if cap is None else cap, C.byref(nb), C.byref(ns))
+        return int(rc), int(nb.value), int(ns.value)
+
+    def bam_gather(self, mask: np.ndarray, n_kept: int, exclude_flags: int = 3328) -> bytes:
+        """The bytes of the kept records whose bit is set in `mask`, block_size field included, in file order."""
+        out = np.zeros(1, np.uint8)
+        rc, nb, _ = self.bam_gather_into(mask, n_kept, out, cap=0, exclude_flags=exclude_flags)
+        if rc == E_RANGE:
+            out = np.zeros(nb, np.uint8)
+            rc, nb, _ = self.bam_gather_into(mask, n_kept, out, exclude_flags=exclude_flags)
+        _check(rc, "rfx_bam_gather")
+        return out[:nb].tobytes()
 
     def records(self) -> int:
         """Whole records (groups of four lines) the arena holds (rfx_text_records)."""
@@ -574,6 +633,25 @@ class TextArena:
     def close(self):
         if self._h:
             lib().rfx_text_close(self._h)
+            self._h = None
+
+
+class NameSet:
+    """A device set of 64-bit QNAME hashes: what TextArena.bam_mark_names looks the kept records up in (rfx_nameset_*)."""
+
+    def __init__(self, ctx: Context, hashes: np.ndarray):
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        self.ctx = ctx
+        self._h = lib().rfx_nameset_build(ctx._h, _p(hashes, u64p) if len(hashes) else None, len(hashes))
+        if not self._h:
+            raise RufusError("rfx_nameset_build failed: " + lib().rfx_last_error().decode())
+
+    def __len__(self) -> int:
+        return int(lib().rfx_nameset_size(self._h))
+
+    def free(self):
+        if self._h:
+            lib().rfx_nameset_free(self._h)
             self._h = None
 
 

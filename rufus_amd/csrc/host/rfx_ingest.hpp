@@ -32,6 +32,7 @@
 #include "rfx_cli.hpp"
 
 #include "rfx_sam.hpp"
+#include "rfx_bam_pairs.hpp"
 #include "rfx_packed_cache.hpp"
 
 namespace rfxcli {
@@ -1268,6 +1269,10 @@ class BamIngest {
   std::vector<std::string> ref_names_;
   std::vector<int32_t> chr_runs_;  // the kept records' refID wherever it changes, over the whole input
   std::vector<uint32_t> runs_buf_;
+  // `RUFUS.Filter --bam` (BamPairFilter below) walks the same arenas with another step per arena: when set, it is called
+  // for every settled arena instead of rfx_bam_parse + sink, and reports the arena's kept records
+  std::function<uint64_t(rfx_text*, uint64_t)> per_arena_;
+  std::string tool_ = "rufus_amd jellyfish count";
 
   void settle_buf(Buf& b) {
     if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
@@ -1278,15 +1283,16 @@ class BamIngest {
       if (b.t == t) settle_buf(b);
   }
   void parse_and_sink(rfx_text* t, uint64_t n_records) {
-    if (n_records) {
+    if (n_records && per_arena_) {
+      reads_ += per_arena_(t, n_records);
+      records_ += n_records;
+      ++arenas_;
+    } else if (n_records) {
       runs_buf_.resize((size_t)2 * n_records);
       uint64_t n_runs = 0;
       rfx_reads* r = rfx_bam_parse(t, exclude_, runs_buf_.data(), n_records, &n_runs);
-      if (!r) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
-      for (uint64_t i = 0; i < n_runs; ++i) {
-        const int32_t ref = (int32_t)runs_buf_[2 * i + 1];
-        if (chr_runs_.empty() || chr_runs_.back() != ref) chr_runs_.push_back(ref);
-      }
+      if (!r) die(tool_ + ": " + rfx_last_error());
+      add_runs(runs_buf_.data(), n_runs);
       reads_ += rfx_reads_count(r);
       records_ += n_records;
       ++arenas_;
@@ -1299,8 +1305,8 @@ class BamIngest {
   uint64_t settle(rfx_text* t, rfx_text* next, uint64_t skip, uint64_t* carried) {
     uint64_t n_records = 0;
     const int rc = rfx_bam_settle(t, next, skip, n_ref_, &n_records, carried);
-    if (rc == RFX_E_FORMAT) die(std::string("rufus_amd jellyfish count: --bam: ") + rfx_last_error());
-    if (rc == RFX_E_RANGE) die("rufus_amd jellyfish count: --bam: a record that is longer than an arena");
+    if (rc == RFX_E_FORMAT) die(tool_ + ": --bam: " + rfx_last_error());
+    if (rc == RFX_E_RANGE) die(tool_ + ": --bam: a record that is longer than an arena");
     if (rc != RFX_OK) die(std::string("rufus_amd: rfx_bam_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
     return n_records;
   }
@@ -1310,7 +1316,7 @@ class BamIngest {
             size_t piece = 8u << 20)
       : ctx_(ctx), sink_(std::move(sink)), piece_(piece), exclude_(exclude_flags), arena_bytes_(arena_bytes) {
     if (!rfx_text_append_bgzf || !rfx_bam_header || !rfx_bam_settle || !rfx_bam_parse)
-      die("rufus_amd jellyfish count: this library cannot read BAM input");
+      die(tool_ + ": this library cannot read BAM input");
     for (rfx_text*& a : arena_) {
       a = rfx_text_open(ctx_, arena_bytes);
       if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
@@ -1329,7 +1335,22 @@ class BamIngest {
     }
     for (rfx_text* a : arena_) rfx_text_close(a);
   }
+  // the other step per arena, and the tool the messages name (before feed_mapped)
+  void set_per_arena(std::function<uint64_t(rfx_text*, uint64_t)> f, const std::string& tool) {
+    per_arena_ = std::move(f);
+    tool_ = tool;
+  }
+  // an arena's run list (rfx_bam_parse's ref_runs) stitched to the log: a run that begins an arena with the refID the arena
+  // before ended with is no change
+  void add_runs(const uint32_t* runs, uint64_t n_runs) {
+    for (uint64_t i = 0; i < n_runs; ++i) {
+      const int32_t ref = (int32_t)runs[2 * i + 1];
+      if (chr_runs_.empty() || chr_runs_.back() != ref) chr_runs_.push_back(ref);
+    }
+  }
   uint64_t reads() const { return reads_; }
+  uint64_t records() const { return records_; }
+  uint64_t arenas() const { return arenas_; }
   std::string counts() const {
     char b[200];
     snprintf(b, sizeof b, "bam route: %llu blocks in %llu appends, %llu arenas, %llu records, %llu reads", (unsigned long long)blocks_,
@@ -1357,7 +1378,7 @@ class BamIngest {
       ref_names_.clear();
       for (size_t at = 0; at < (size_t)names_bytes; at += strlen(names.data() + at) + 1) ref_names_.emplace_back(names.data() + at);
     }
-    if (rc != RFX_OK || !complete) die("rufus_amd jellyfish count: --bam: the input does not begin with a whole BAM header");
+    if (rc != RFX_OK || !complete) die(tool_ + ": --bam: the input does not begin with a whole BAM header");
     // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of inflated bytes
     struct Run { size_t at, n; uint64_t inflated; };
     std::vector<Run> runs;
@@ -1368,9 +1389,9 @@ class BamIngest {
       rc = rfx_bgzf_scan(m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
       if (nb == 0) {
         char msg[128];
-        snprintf(msg, sizeof msg, "rufus_amd jellyfish count: %s BGZF block at byte %llu of the compressed input",
-                 rc == RFX_OK ? "truncated" : "no", (unsigned long long)at);
-        die(msg);
+        snprintf(msg, sizeof msg, "%s BGZF block at byte %llu of the compressed input", rc == RFX_OK ? "truncated" : "no",
+                 (unsigned long long)at);
+        die(tool_ + (per_arena_ ? ": --bam: " : ": ") + msg);
       }
       runs.push_back({at, (size_t)used, inf});
       blocks_ += nb;
@@ -1402,7 +1423,7 @@ class BamIngest {
       rfx_text* nx = arena_[cur ^ 1];
       uint64_t carried = 0;
       const uint64_t n_records = settle(t, nx, skip, &carried);
-      if (n_records == 0) die("rufus_amd jellyfish count: --bam: a record that is longer than an arena");
+      if (n_records == 0) die(tool_ + ": --bam: a record that is longer than an arena");
       skip = 0;
       more = fill(nx);  // queued, not waited for: the device inflates it beside this arena's count
       parse_and_sink(t, n_records);
@@ -1656,6 +1677,149 @@ class BgzfPairFilter {
       }
       cur ^= 1;
     }
+  }
+};
+
+// ---- the subject's hit pairs straight from its BAM: two passes over the file, only selected records leave the device ----
+// Replaces `samtools view -F 3328 X.bam | PassThroughSamCheck.stranded CHR STUB.temp | RUFUS.Filter ...`
+// (runRufus.sh:964-967).  Mates of a coordinate-sorted BAM lie anywhere and hits are rare, so:
+//   pass 1  BamIngest's walk; per arena rfx_bam_parse_filter -> rfx_filter (every record by itself, last base skipped) ->
+//           rfx_bam_name_hashes of the hit records.  Kept: the hit records' GLOBAL kept indices (kept records in front of the
+//           arena + index in it: the same however the arenas are cut), their name hashes, the refID runs for the log
+//   between rfx_nameset_build of the hashes.  No hit: no second pass
+//   pass 2  the same walk, no pack and no scan; per arena rfx_bam_mark_names -> rfx_bam_gather of the marked records
+//   tail    rfx_bam_pairs.hpp: each gathered record printed as the stranded feeder prints it, its hit bit looked up by
+//           global index, the pairing walk of `--sam` over this subset
+// Exact: what becomes of a name depends only on the records of that name, and the subset holds every record of every hit
+// name in stream order.  A hash collision brings records of a name without a hit: they pair among themselves and write
+// nothing.
+// (weak, as above)
+#pragma weak rfx_bam_parse_filter
+#pragma weak rfx_bam_name_hashes
+#pragma weak rfx_nameset_build
+#pragma weak rfx_nameset_size
+#pragma weak rfx_nameset_free
+#pragma weak rfx_bam_mark_names
+#pragma weak rfx_bam_gather
+#pragma weak rfx_reads_count
+class BamPairFilter {
+  rfx_ctx* ctx_;
+  rfx_set* set_;
+  int min_q_, thresh_;
+  uint32_t exclude_;
+  size_t arena_bytes_, piece_;
+  std::vector<uint64_t> hit_index_, hit_hash_, mask_;  // (hit_index_ ascending: arenas come in file order)
+  std::vector<uint32_t> runs_buf_;
+  std::vector<std::string> chr_log_;
+  std::vector<uint8_t> out_;
+  rfxsam::BamPairTail tail_;
+  uint64_t arenas_ = 0, records_ = 0, reads_ = 0, names_ = 0, passes_ = 0;
+  static constexpr const char* TOOL = "rufus_amd RUFUS.Filter";
+
+  [[noreturn]] static void fail(const char* what) { die(std::string(TOOL) + ": --bam: " + what + ": " + rfx_last_error()); }
+
+  uint64_t scan_arena(BamIngest& in, rfx_text* t, uint64_t n_records, uint64_t base) {
+    runs_buf_.resize((size_t)2 * n_records);
+    uint64_t n_runs = 0;
+    rfx_reads* rd = rfx_bam_parse_filter(t, exclude_, min_q_, runs_buf_.data(), n_records, &n_runs);
+    if (!rd) die(std::string(TOOL) + ": --bam: " + rfx_last_error());
+    in.add_runs(runs_buf_.data(), n_runs);
+    const uint64_t n = rfx_reads_count(rd);
+    mask_.assign((size_t)((n + 63) / 64) + 1, 0);
+    uint64_t nh = 0;
+    // every record by itself; paired tool: `i < length()-1`, the last base is never examined (src/RUFUS.Filter.cpp:203)
+    const int rc = rfx_filter(set_, rd, thresh_, 1, nullptr, mask_.data(), &nh);
+    rfx_reads_free(rd);
+    if (rc) fail("rfx_filter");
+    if (nh) {
+      const size_t at = hit_hash_.size();
+      hit_hash_.resize(at + (size_t)nh);
+      uint64_t got = 0;
+      if (rfx_bam_name_hashes(t, exclude_, mask_.data(), n, hit_hash_.data() + at, nh, &got) != RFX_OK || got != nh)
+        fail("rfx_bam_name_hashes");
+      for (uint64_t i = 0; i < n; ++i)
+        if ((mask_[i >> 6] >> (i & 63)) & 1) hit_index_.push_back(base + i);
+    }
+    return n;
+  }
+  uint64_t pull_arena(rfx_text* t, uint64_t n_records, uint64_t base, rfx_nameset* names) {
+    mask_.assign((size_t)((n_records + 63) / 64) + 1, 0);
+    uint64_t n_kept = 0, n_marked = 0;
+    if (rfx_bam_mark_names(t, exclude_, names, mask_.data(), &n_kept, &n_marked) != RFX_OK) fail("rfx_bam_mark_names");
+    if (!n_marked) return n_kept;
+    uint64_t bytes = 0, sel = 0;
+    int rc = rfx_bam_gather(t, exclude_, mask_.data(), n_kept, out_.data(), out_.size(), &bytes, &sel);
+    if (rc == RFX_E_RANGE) {
+      out_.resize((size_t)(bytes + bytes / 4 + 4096));
+      rc = rfx_bam_gather(t, exclude_, mask_.data(), n_kept, out_.data(), out_.size(), &bytes, &sel);
+    }
+    if (rc != RFX_OK || sel != n_marked) fail("rfx_bam_gather");
+    uint64_t p = 0;
+    for (uint64_t i = 0; i < n_kept; ++i) {
+      if (!((mask_[i >> 6] >> (i & 63)) & 1)) continue;
+      // (the device copied whole records the settle has checked; the sizes are checked again before anything is read)
+      if (p + BAM_FIXED > bytes || bam_next(out_.data(), p, bytes) == BAM_STOP || bam_valid(out_.data(), p, 0x7FFFFFFF) != BAM_OK)
+        die(std::string(TOOL) + ": --bam: the gathered records do not add up");
+      tail_.add(out_.data(), p, std::binary_search(hit_index_.begin(), hit_index_.end(), base + i));
+      p = bam_next(out_.data(), p, bytes);
+    }
+    if (p != bytes) die(std::string(TOOL) + ": --bam: the gathered records do not add up");
+    return n_kept;
+  }
+  void pass(const char* m, size_t size, rfx_nameset* names) {
+    BamIngest in(ctx_, nullptr, exclude_, arena_bytes_, piece_);
+    uint64_t base = 0;
+    in.set_per_arena(
+        [&](rfx_text* t, uint64_t n_records) {
+          const uint64_t n = names ? pull_arena(t, n_records, base, names) : scan_arena(in, t, n_records, base);
+          base += n;
+          return n;
+        },
+        TOOL);
+    in.feed_mapped(m, size);
+    if (!names) {
+      arenas_ = in.arenas();
+      records_ = in.records();
+      reads_ = in.reads();
+      chr_log_ = in.chr_log();
+    } else if (in.records() != records_ || in.reads() != reads_) {
+      die(std::string(TOOL) + ": --bam: the two passes saw different records");
+    }
+    ++passes_;
+  }
+
+ public:
+  BamPairFilter(rfx_ctx* ctx, rfx_set* set, int min_q, int thresh, uint32_t exclude_flags, size_t arena_bytes = (size_t)1 << 30,
+                size_t piece = 8u << 20)
+      : ctx_(ctx), set_(set), min_q_(min_q), thresh_(thresh), exclude_(exclude_flags), arena_bytes_(arena_bytes), piece_(piece) {
+    if (!rfx_bam_parse_filter || !rfx_bam_name_hashes || !rfx_nameset_build || !rfx_nameset_size || !rfx_nameset_free ||
+        !rfx_bam_mark_names || !rfx_bam_gather)
+      die(std::string(TOOL) + ": this library cannot read BAM input");
+  }
+  // A whole mapped BAM file.  Dies where BamIngest does.  Afterwards mate1() / mate2() hold the two output files' bytes and
+  // chr_log() the chromosome log's lines.
+  void run(const char* m, size_t size) {
+    pass(m, size, nullptr);
+    trace("filter --bam: pass 1 done (scan)");
+    if (hit_index_.empty()) return;
+    rfx_nameset* names = rfx_nameset_build(ctx_, hit_hash_.data(), hit_hash_.size());
+    if (!names) fail("rfx_nameset_build");
+    names_ = rfx_nameset_size(names);
+    pass(m, size, names);
+    rfx_nameset_free(names);
+    trace("filter --bam: pass 2 done (pull)");
+  }
+  const std::string& mate1() const { return tail_.walk.o1; }
+  const std::string& mate2() const { return tail_.walk.o2; }
+  const std::vector<std::string>& chr_log() const { return chr_log_; }
+  uint64_t passes() const { return passes_; }
+  std::string counts() const {
+    char b[240];
+    snprintf(b, sizeof b, "bam filter route: arenas %llu records %llu reads %llu hits %llu names %llu gathered %llu pairs %llu",
+             (unsigned long long)arenas_, (unsigned long long)records_, (unsigned long long)reads_,
+             (unsigned long long)hit_index_.size(), (unsigned long long)names_, (unsigned long long)tail_.records,
+             (unsigned long long)tail_.walk.n_found);
+    return b;
   }
 };
 

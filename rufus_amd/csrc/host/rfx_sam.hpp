@@ -166,6 +166,107 @@ struct CompLut {
   fputc('\n', f);
 }
 
+// ---- the pairing walk of the filter (`RUFUS.Filter --sam` and `--bam`) --------------------------------------------------
+// A record as the stranded feeder prints it: name, sequence and quality lie wherever the route keeps them.
+struct Rec {
+  const char *name, *seq, *qual;
+  uint32_t name_len, seq_len, qual_len;
+  uint64_t hash;
+};
+struct Owned {
+  Rec r;
+  std::string bytes;
+};
+struct Slot {
+  uint64_t hash = 0;
+  const Rec* rec = nullptr;
+  Owned* owned = nullptr;
+  uint32_t state = 0;  // 0 empty, 1 deleted, 2 live
+  uint32_t hit = 0;
+};
+struct WaitTable {
+  std::vector<Slot> slot;
+  size_t used = 0, filled = 0;
+  WaitTable() : slot(1 << 14) {}
+  void rehash(size_t n) {
+    std::vector<Slot> old;
+    old.swap(slot);
+    slot.assign(n, Slot());
+    filled = used;
+    for (const Slot& s : old)
+      if (s.state == 2) {
+        size_t j = (size_t)s.hash & (n - 1);
+        while (slot[j].state) j = (j + 1) & (n - 1);
+        slot[j] = s;
+      }
+  }
+  long find(uint64_t h, const char* name, size_t n) const {
+    const size_t mask = slot.size() - 1;
+    for (size_t j = (size_t)h & mask;; j = (j + 1) & mask) {
+      const Slot& s = slot[j];
+      if (s.state == 0) return -1;
+      if (s.state == 2 && s.hash == h && s.rec->name_len == n && memcmp(s.rec->name, name, n) == 0) return (long)j;
+    }
+  }
+  void insert(const Rec* r, uint32_t hit) {
+    if ((filled + 1) * 2 > slot.size()) rehash(used * 4 > slot.size() ? slot.size() * 2 : slot.size());
+    const size_t mask = slot.size() - 1;
+    size_t j = (size_t)r->hash & mask;
+    while (slot[j].state == 2) j = (j + 1) & mask;
+    if (slot[j].state == 0) ++filled;
+    slot[j].hash = r->hash;
+    slot[j].rec = r;
+    slot[j].owned = nullptr;
+    slot[j].state = 2;
+    slot[j].hit = hit;
+    ++used;
+  }
+  void erase(long j) {
+    delete slot[(size_t)j].owned;
+    slot[(size_t)j].owned = nullptr;
+    slot[(size_t)j].state = 1;
+    --used;
+  }
+};
+// The walk itself, as the feeder pairs (src/PassThroughSamCheck.stranded.cpp:225-281) and the filter writes
+// (src/RUFUS.Filter.cpp:237-277): in stream order a record meets its waiting mate or waits; a pair one of whose records
+// was hit is appended to o1 / o2 -- the LATER record is mate 1, the stored one mate 2 -- in the order the pairs complete.
+// The caller hands the records over one by one, writes o1 / o2 out when it likes and keeps a waiting record's bytes alive.
+struct PairWalk {
+  WaitTable waiting;
+  std::string o1, o2;
+  unsigned long long n_pairs = 0, n_found = 0;
+  static void put_text(std::string& o, const char* name, size_t nn, const char* seq, size_t ls, const char* qual, size_t lq) {
+    o.push_back('@');
+    o.append(name, nn);
+    o.push_back('\n');
+    o.append(seq, ls);
+    o.append("\n+\n", 3);
+    o.append(qual, lq);
+    o.push_back('\n');
+  }
+  // true: the record waits now (r must stay where it is until it has met its mate, or be replaced in its slot)
+  bool meet(const Rec& r, uint32_t hit) {
+    const long at = waiting.find(r.hash, r.name, r.name_len);
+    if (at < 0) {
+      waiting.insert(&r, hit);
+      return true;
+    }
+    const Slot& s = waiting.slot[(size_t)at];
+    // (the later record is mate 1 of the pair: the paired tool rejects an empty mate-1 sequence line)
+    if (r.seq_len == 0)
+      rfxcli::die("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
+    if (hit | s.hit) {
+      put_text(o1, r.name, r.name_len, r.seq, r.seq_len, r.qual, r.qual_len);
+      put_text(o2, r.name, r.name_len, s.rec->seq, s.rec->seq_len, s.rec->qual, s.rec->qual_len);
+      ++n_found;
+    }
+    ++n_pairs;
+    waiting.erase(at);
+    return false;
+  }
+};
+
 [[maybe_unused]] int sam_flag(const Field& fl) {  // atoi of the field: optional sign, digits, anything after them ignored
   int flag = 0;
   size_t i = 0;

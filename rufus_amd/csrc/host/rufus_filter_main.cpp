@@ -3,6 +3,8 @@
 //       -> STUB.Mutations.Mate1.fastq, STUB.Mutations.Mate2.fastq        src/RUFUS.Filter.cpp:28,:47-54
 //   RUFUS.Filter.single HashList FQ|stdin STUB K MinQ HashCountThreshold Threads
 //       -> STUB.Mutations.fastq with ":MH<hits>" appended to each header  src/RUFUS.Filter.ss.cpp:27,:43-49,:198
+//   RUFUS.Filter --sam | --packed | --bam ...: the subject's SAM stream, its packed cache or its BAM file as the input
+//       (not in the reference: namespaces samf and bamf below)
 // The two mate files may be named pipes written in lock step by PassThroughSamCheck.stranded, so
 // they are read interleaved, 4 lines each (src/RUFUS.Filter.cpp:165-173) -- never one file ahead.
 // Pulled records are written in input order (the reference's order depends on OpenMP scheduling; at
@@ -98,11 +100,6 @@ static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<u
 namespace samf {
 using namespace rfxsam;
 
-struct Rec {
-  const char *name, *seq, *qual;
-  uint32_t name_len, seq_len, qual_len;
-  uint64_t hash;
-};
 // Where the printed forms of a piece's records go (reverse strand: bases and qualities again; a quality string shorter
 // than its read: a padded copy): blocks taken as they are needed and kept for the next piece -- most records are
 // forward-strand and need none.  (Until round 4 every piece buffer had room for the worst case behind its lines,
@@ -138,62 +135,6 @@ struct SPiece {
   std::vector<uint32_t> waited;  // records of this piece that went into the waiting table
   uint64_t seq = 0;
 };
-struct Owned {
-  Rec r;
-  std::string bytes;
-};
-struct Slot {
-  uint64_t hash = 0;
-  const Rec* rec = nullptr;
-  Owned* owned = nullptr;
-  uint32_t state = 0;  // 0 empty, 1 deleted, 2 live
-  uint32_t hit = 0;
-};
-struct WaitTable {
-  std::vector<Slot> slot;
-  size_t used = 0, filled = 0;
-  WaitTable() : slot(1 << 14) {}
-  void rehash(size_t n) {
-    std::vector<Slot> old;
-    old.swap(slot);
-    slot.assign(n, Slot());
-    filled = used;
-    for (const Slot& s : old)
-      if (s.state == 2) {
-        size_t j = (size_t)s.hash & (n - 1);
-        while (slot[j].state) j = (j + 1) & (n - 1);
-        slot[j] = s;
-      }
-  }
-  long find(uint64_t h, const char* name, size_t n) const {
-    const size_t mask = slot.size() - 1;
-    for (size_t j = (size_t)h & mask;; j = (j + 1) & mask) {
-      const Slot& s = slot[j];
-      if (s.state == 0) return -1;
-      if (s.state == 2 && s.hash == h && s.rec->name_len == n && memcmp(s.rec->name, name, n) == 0) return (long)j;
-    }
-  }
-  void insert(const Rec* r, uint32_t hit) {
-    if ((filled + 1) * 2 > slot.size()) rehash(used * 4 > slot.size() ? slot.size() * 2 : slot.size());
-    const size_t mask = slot.size() - 1;
-    size_t j = (size_t)r->hash & mask;
-    while (slot[j].state == 2) j = (j + 1) & mask;
-    if (slot[j].state == 0) ++filled;
-    slot[j].hash = r->hash;
-    slot[j].rec = r;
-    slot[j].owned = nullptr;
-    slot[j].state = 2;
-    slot[j].hit = hit;
-    ++used;
-  }
-  void erase(long j) {
-    delete slot[(size_t)j].owned;
-    slot[(size_t)j].owned = nullptr;
-    slot[(size_t)j].state = 1;
-    --used;
-  }
-};
-
 static bool in_process = false;  // run() called by run_packed: it has a temporary file to remove afterwards
 
 static int run(int argc, char** argv) {
@@ -467,19 +408,13 @@ static int run(int argc, char** argv) {
   helpers = std::max(helpers, (unsigned)n_gpu);
   for (unsigned t = 0; t < helpers; ++t) workers.emplace_back(helper, t);
 
-  WaitTable waiting;
+  PairWalk walk;  // (rfx_sam.hpp: the walk `--bam` runs too)
+  WaitTable& waiting = walk.waiting;
+  std::string &o1 = walk.o1, &o2 = walk.o2;
+  unsigned long long &n_pairs = walk.n_pairs, &n_found = walk.n_found;
   std::deque<SPiece*> live;
-  std::string current = "notachr", o1, o2;
-  unsigned long long n_rec = 0, n_pairs = 0, n_found = 0;
-  auto put_text = [](std::string& o, const char* name, size_t nn, const char* seq, size_t ls, const char* qual, size_t lq) {
-    o.push_back('@');
-    o.append(name, nn);
-    o.push_back('\n');
-    o.append(seq, ls);
-    o.append("\n+\n", 3);
-    o.append(qual, lq);
-    o.push_back('\n');
-  };
+  std::string current = "notachr";
+  unsigned long long n_rec = 0;
   auto retire = [&](SPiece* pc) {  // what still waits from this piece leaves it
     for (uint32_t idx : pc->waited) {
       const Rec* r = &pc->recs[idx];
@@ -519,23 +454,7 @@ static int run(int argc, char** argv) {
     for (size_t i = 0; i < n; ++i) {
       const Rec& r = pc->recs[i];
       const uint32_t hit = (uint32_t)((pc->mask[i >> 6] >> (i & 63)) & 1);
-      const long at = waiting.find(r.hash, r.name, r.name_len);
-      if (at < 0) {
-        waiting.insert(&r, hit);
-        pc->waited.push_back((uint32_t)i);
-      } else {
-        const Slot& s = waiting.slot[(size_t)at];
-        // (the later record is mate 1 of the pair: the paired tool rejects an empty mate-1 sequence line)
-        if (r.seq_len == 0)
-          die("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
-        if (hit | s.hit) {
-          put_text(o1, r.name, r.name_len, r.seq, r.seq_len, r.qual, r.qual_len);
-          put_text(o2, r.name, r.name_len, s.rec->seq, s.rec->seq_len, s.rec->qual, s.rec->qual_len);
-          ++n_found;
-        }
-        ++n_pairs;
-        waiting.erase(at);
-      }
+      if (walk.meet(r, hit)) pc->waited.push_back((uint32_t)i);
     }
     n_rec += n;
     if (!o1.empty()) {
@@ -746,12 +665,99 @@ static int run_packed(int argc, char** argv) {
   return rc;
 }
 }  // namespace samf
+
+// ---- RUFUS.Filter --bam CHRFILE HashList X.bam STUB K MinQ HashCountThreshold Threads [--bam-exclude N] ---------------
+// The subject straight from its BAM: what `samtools view -F N X.bam | RUFUS.Filter --sam CHRFILE HashList stdin ...` writes
+// (runRufus.sh:964-967; N defaults to 3328), byte for byte, without samtools and without SAM text.  The file is mapped and
+// handed to rfx_ingest.hpp's BamPairFilter: two passes, inflated and framed on the device both times; this thread reads
+// the file and writes the three outputs.  One device: RUFUS_GPUS naming more is refused, as for the bgzip'd mates.
+// RFX_BAM_ARENA (bytes per arena, >= 1 MiB) and RFX_INGEST_PIECE as in `jellyfish count --bam`.  Threads is accepted and
+// not used: no host thread parses anything.
+namespace bamf {
+static int run(int argc, char** argv) {
+  printf("Call is --bam CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads [--bam-exclude N]\n");
+  if (argc < 10) {
+    printf("ERROR: expected 9 arguments\n");
+    return 0;
+  }
+  const char *chr_path = argv[2], *hashlist = argv[3], *bam = argv[4];
+  const std::string stub = argv[5];
+  const int k = atoi(argv[6]), min_q = atoi(argv[7]), thresh = atoi(argv[8]);
+  uint32_t exclude = 3328;
+  for (int a = 10; a < argc; ++a) {
+    if (strcmp(argv[a], "--bam-exclude") == 0 && a + 1 < argc) exclude = (uint32_t)strtoul(argv[++a], nullptr, 0);
+    else die(std::string("rufus_amd RUFUS.Filter: --bam: unknown argument ") + argv[a]);
+  }
+  std::string text;
+  {
+    std::ifstream f(hashlist, std::ios::binary);
+    if (!f.is_open()) {
+      printf("Error, ParentHashFile could not be opened");
+      return 0;
+    }
+    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+  }
+  const int fd = ::open(bam, O_RDONLY);
+  if (fd < 0) {
+    printf("Error, MutFile could not be opened");
+    return 0;
+  }
+  struct stat sb;
+  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode))
+    die("rufus_amd RUFUS.Filter: --bam needs a regular file, not a pipe: the BAM is mapped and read twice");
+  if (!is_bgzf(fd, true, (uint64_t)sb.st_size)) die(std::string("rufus_amd RUFUS.Filter: --bam: '") + bam + "' is not BGZF");
+  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
+  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, 0, nullptr, 0);
+  if (nk < 0) die("rufus_amd: cannot parse the hash list");
+  std::vector<uint64_t> keys((size_t)nk + 1);
+  rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
+  printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
+  const std::vector<int> gpus = gpu_list();
+  if (gpus.size() != 1)
+    die("rufus_amd RUFUS.Filter: --bam finds, scans and pulls the records on the device, which needs one device (RUFUS_GPUS names "
+        "more)");
+  FILE* chr = fopen(chr_path, "w");
+  std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
+  std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
+  if (!chr || !out1.is_open() || !out2.is_open()) {
+    printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
+    return 0;
+  }
+  rfx_ctx* ctx = open_ctxs(gpus)[0];
+  rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
+  if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
+  trace("filter --bam: device open, set built");
+  void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+  if (m == MAP_FAILED) die(std::string("rufus_amd RUFUS.Filter: --bam: cannot map the input: ") + strerror(errno));
+  (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
+  size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
+  if (const char* ev = getenv("RFX_BAM_ARENA")) arena = (size_t)std::max(1ll << 20, atoll(ev));
+  if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+  {
+    BamPairFilter route(ctx, set, min_q, thresh, exclude, arena, piece);
+    route.run((const char*)m, (size_t)sb.st_size);
+    for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
+    fclose(chr);
+    out1.write(route.mate1().data(), (std::streamsize)route.mate1().size());
+    out2.write(route.mate2().data(), (std::streamsize)route.mate2().size());
+    out1.close();
+    out2.close();
+    trace(route.counts().c_str());
+    printf("\nDone running RUFUS.Filter.cpp\n");
+    leave(0);  // (outputs closed: see the text route's end)
+  }
+  rfx_set_free(set);
+  rfx_close(ctx);
+  return 0;
+}
+}  // namespace bamf
 #endif
 
 int main(int argc, char** argv) {
 #ifndef RFX_SINGLE_END
   if (argc > 1 && strcmp(argv[1], "--sam") == 0) return samf::run(argc, argv);
   if (argc > 1 && strcmp(argv[1], "--packed") == 0) return samf::run_packed(argc, argv);
+  if (argc > 1 && strcmp(argv[1], "--bam") == 0) return bamf::run(argc, argv);
 #endif
 #ifdef RFX_SINGLE_END
   const int need = 8;

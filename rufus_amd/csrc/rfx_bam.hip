@@ -488,3 +488,579 @@ rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs
 }
 
 }  // extern "C"
+
+// ---- the subject's hit pairs straight from the BAM (RUFUS.Filter --bam) ------------------------------------------------
+// Replaces `samtools view -F 3328 X.bam | PassThroughSamCheck.stranded | RUFUS.Filter` (runRufus.sh:964-967).
+//
+// rfx_bam_parse_filter, rfx_bam_parse's shape with the STRANDED FILTER form of rfx_bam_core.h:
+//   k_bamf_fields  a thread per record: keep, bam_filter_len (a reverse record: its surviving nibbles) -> three scans
+//   k_bamf_table   a thread per record: len[], word_off[], the record's offset and refID of the kept, at their rank
+//   k_bam_runs / k_bam_run_out   as above
+//   k_bamf_pack    a thread per OUTPUT code word: owner by binary search in word_off, bam_filter_word
+//
+// The pull (pass 2 of the tool: no pack, no scan), over the KEPT records of a settled arena -- kept_of: k_bam_keep, a scan,
+// k_bam_kept_at = the offset of kept record o:
+//   k_bam_hashes   a thread per kept record: bam_name_hash of the records a mask selects, at their rank among the selected
+//                  (the rank of a mask word's first bit comes with the mask: the mask is the host's)
+//   k_bam_mark     a wave per 64 kept records = one mask word: bam_name_hash, a probe of the open-addressed table, a ballot
+//   k_bamg_sizes / k_bamg_table   rfx_gather.hip's two, with a record's bytes = 4 + block_size -> k_gather_copy
+namespace {
+
+__global__ __launch_bounds__(256) void k_bamf_fields(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
+                                                      uint64_t n_rec, uint32_t exclude, uint64_t* __restrict__ cnt,
+                                                      uint64_t* __restrict__ words, uint64_t* __restrict__ bases,
+                                                      unsigned int* __restrict__ d_stat) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = rec_start[r];
+    const bool keep = (bam_flag(b, p) & exclude) == 0;
+    const uint32_t len = keep ? bam_filter_len(b, p) : 0u;
+    cnt[r] = keep;
+    words[r] = (len + 31u) / 32u;
+    bases[r] = len;
+    if (keep) {
+      atomicMax(&d_stat[0], len);
+      if (len < 32u) atomicAdd(&d_stat[1u + len], 1u);
+    }
+  }
+}
+
+// (cnt, words: scanned; bases: scanned too, so a record's length is the difference of two entries)
+__global__ __launch_bounds__(256) void k_bamf_table(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
+                                                     uint64_t n_rec, uint32_t exclude, const uint64_t* __restrict__ cnt,
+                                                     const uint64_t* __restrict__ words, const uint64_t* __restrict__ bases,
+                                                     uint32_t* __restrict__ out_len, uint32_t* __restrict__ out_word_off,
+                                                     uint32_t* __restrict__ rec_at, int32_t* __restrict__ ref_id) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = rec_start[r];
+    if (bam_flag(b, p) & exclude) continue;
+    const uint32_t o = (uint32_t)cnt[r];  // (both totals are below 2^32: checked before this launch)
+    out_len[o] = (uint32_t)(bases[r + 1] - bases[r]);
+    out_word_off[o] = (uint32_t)words[r];
+    rec_at[o] = (uint32_t)p;
+    ref_id[o] = bam_ref_id(b, p);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bamf_pack(const uint8_t* __restrict__ b, const uint32_t* __restrict__ word_off,
+                                                    const uint32_t* __restrict__ len, const uint32_t* __restrict__ rec_at,
+                                                    uint32_t n_kept, uint64_t n_words, int min_q, uint64_t* __restrict__ codes,
+                                                    uint32_t* __restrict__ good) {
+  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n_words; x += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t o = owner_of(word_off, n_kept, (uint32_t)x);  // (a read of 0 bases owns no word: the LAST o with off <= x)
+    uint64_t c;
+    uint32_t g;
+    bam_filter_word(b, rec_at[o], (uint32_t)x - word_off[o], len[o], min_q, &c, &g);
+    codes[x] = c;
+    good[x] = g;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bam_keep(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
+                                                   uint64_t n_rec, uint32_t exclude, uint64_t* __restrict__ cnt) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x)
+    cnt[r] = (bam_flag(b, rec_start[r]) & exclude) == 0;
+}
+
+__global__ __launch_bounds__(256) void k_bam_kept_at(const uint32_t* __restrict__ rec_start, uint64_t n_rec,
+                                                      const uint64_t* __restrict__ cnt, uint32_t* __restrict__ kept_at) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x)
+    if (cnt[r + 1] != cnt[r]) kept_at[cnt[r]] = rec_start[r];
+}
+
+// mask == nullptr: every kept record, at its own index
+__global__ __launch_bounds__(256) void k_bam_hashes(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at,
+                                                     uint64_t n_kept, const uint64_t* __restrict__ mask,
+                                                     const uint64_t* __restrict__ word_rank, uint64_t* __restrict__ out) {
+  for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n_kept; o += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t at = o;
+    if (mask) {
+      const uint64_t m = mask[o >> 6], bit = 1ull << (o & 63u);
+      if (!(m & bit)) continue;
+      at = word_rank[o >> 6] + (uint64_t)__popcll(m & (bit - 1ull));
+    }
+    out[at] = bam_name_hash(b, kept_at[o]);
+  }
+}
+
+// The table: `slots` (a power of two) keys, 0 = empty, linear probing from nameset_slot; a key 0 is kept beside it.
+__host__ __device__ __forceinline__ uint64_t nameset_slot(uint64_t key, uint64_t slots) {
+  return ((key ^ (key >> 32)) * 0x9E3779B97F4A7C15ull >> 20) & (slots - 1ull);
+}
+
+// blockDim = 256 = four waves; wave w of the grid takes mask words w, w + waves, ...: 64 kept records each, a lane a record
+__global__ __launch_bounds__(256) void k_bam_mark(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at, uint64_t n_kept,
+                                                   const uint64_t* __restrict__ table, uint64_t slots, int has_zero,
+                                                   uint64_t* __restrict__ mask_out, unsigned long long* __restrict__ n_marked) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6), nw = (n_kept + 63) / 64;
+  for (uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < nw; w += waves) {  // (wave-uniform)
+    const uint64_t o = w * 64 + lane;
+    bool in = false;
+    if (o < n_kept) {
+      const uint64_t h = bam_name_hash(b, kept_at[o]);
+      if (h == 0) {
+        in = has_zero != 0;
+      } else {
+        for (uint64_t s = nameset_slot(h, slots);; s = (s + 1) & (slots - 1ull)) {  // (ends: the table is at most half full)
+          const uint64_t key = table[s];
+          if (key == h) in = true;
+          if (key == h || key == 0) break;
+        }
+      }
+    }
+    const unsigned long long vote = __ballot(in);
+    if (lane == 0) {
+      mask_out[w] = vote;
+      if (vote) atomicAdd(n_marked, (unsigned long long)__popcll(vote));
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t record_bytes(const uint8_t* b, uint32_t p) { return 4u + bam_block_size(b, p); }
+
+__global__ __launch_bounds__(256) void k_bamg_sizes(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at,
+                                                     const uint64_t* __restrict__ mask, uint32_t nw, uint64_t tail,
+                                                     uint64_t* __restrict__ cnt, uint64_t* __restrict__ bytes) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t w = (uint32_t)i;
+    uint64_t m = mask[w];
+    if (w == nw - 1u) m &= tail;  // bits at and above the kept count are ignored
+    uint64_t nbytes = 0;
+    for (uint32_t h = 0; h < 2u; ++h) {
+      uint32_t bits = h ? (uint32_t)(m >> 32) : (uint32_t)m;
+      while (bits) {
+        const uint32_t bit = (uint32_t)__ffs(bits) - 1u;
+        bits &= bits - 1u;
+        nbytes += record_bytes(b, kept_at[w * 64u + h * 32u + bit]);
+      }
+    }
+    cnt[w] = (uint32_t)__popcll(m);
+    bytes[w] = nbytes;
+  }
+}
+
+// cnt / bytes: the scanned arrays (positions in the result)
+__global__ __launch_bounds__(256) void k_bamg_table(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at,
+                                                     const uint64_t* __restrict__ mask, uint32_t nw, uint64_t tail,
+                                                     const uint64_t* __restrict__ cnt, const uint64_t* __restrict__ bytes,
+                                                     uint32_t* __restrict__ src_off, uint32_t* __restrict__ dst_off) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t w = (uint32_t)i;
+    uint64_t m = mask[w];
+    if (w == nw - 1u) m &= tail;
+    uint32_t o = (uint32_t)cnt[w], at = (uint32_t)bytes[w];  // (both totals are below 2^32: the arena is)
+    for (uint32_t h = 0; h < 2u; ++h) {
+      uint32_t bits = h ? (uint32_t)(m >> 32) : (uint32_t)m;
+      while (bits) {
+        const uint32_t bit = (uint32_t)__ffs(bits) - 1u;
+        bits &= bits - 1u;
+        const uint32_t s = kept_at[w * 64u + h * 32u + bit];
+        src_off[o] = s;
+        dst_off[o] = at;
+        ++o;
+        at += record_bytes(b, s);
+      }
+    }
+    if (w == nw - 1u) dst_off[o] = at;  // dst_off[n_sel] = all bytes
+  }
+}
+
+// What the three pull calls begin with: the arena settled and ready, kept_at[o] = the offset of kept record o (device,
+// dmalloc: the caller frees it; nullptr for 0 kept records), *n_kept.  One wait.
+struct kept_view {
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t n = 0, n_kept = 0;
+  uint32_t* kept_at = nullptr;
+};
+int kept_of(rfx_text* t, uint32_t exclude, const char* who, kept_view* v) {
+  char msg[200];
+  rfxi::text_bam& slot = rfxi::text_bam_of(t);
+  if (!slot.settled) {
+    snprintf(msg, sizeof msg, "%s: the arena has not been settled with rfx_bam_settle since its last reset", who);
+    rfxi::set_error(msg);
+    return RFX_E_INVAL;
+  }
+  if (const int rc = rfxi::text_ready(t, &v->c, &v->arena, &v->n)) return rc;
+  const uint64_t R = slot.n_records;
+  if (R == 0) return RFX_OK;
+  rfx_ctx* c = v->c;
+  uint64_t* cnt = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  auto fail = [&](int rc, hipError_t e) {
+    snprintf(msg, sizeof msg, "%s: %s", who, e != hipSuccess ? hipGetErrorString(e) : "out of device memory");
+    (void)rfxi::sync(c);
+    rfxi::set_error(msg);
+    dfree(c, cnt);
+    dfree(c, v->kept_at);
+    v->kept_at = nullptr;
+    return rc;
+  };
+  if (!cnt) return fail(RFX_E_NOMEM, hipSuccess);
+  const dim3 grid((unsigned)std::min<uint64_t>((R + 255) / 256, (uint64_t)c->n_cu * 16));
+  {
+    rfx_span sp(c, "k_bam_keep");
+    hipLaunchKernelGGL(k_bam_keep, grid, dim3(256), 0, c->stream, v->arena, slot.rec_start, R, exclude, cnt);
+  }
+  rfxk::scan_tail(c, cnt, R);
+  hipError_t e = queue_read(c, &v->n_kept, cnt + R, 8);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return fail(RFX_E_HIP, e);
+  if (v->n_kept) {
+    v->kept_at = (uint32_t*)dmalloc(c, (size_t)v->n_kept * 4);
+    if (!v->kept_at) return fail(RFX_E_NOMEM, hipSuccess);
+    rfx_span sp(c, "k_bam_kept_at");
+    hipLaunchKernelGGL(k_bam_kept_at, grid, dim3(256), 0, c->stream, slot.rec_start, R, cnt, v->kept_at);
+  }
+  e = rfxi::sync(c);  // (cnt is read by the launch: it is freed behind it)
+  if (e != hipSuccess) return fail(RFX_E_HIP, e);
+  dfree(c, cnt);
+  return RFX_OK;
+}
+
+int pull_fail(rfx_ctx* c, const char* who, int rc, hipError_t e, const char* text) {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s: %s", who, e != hipSuccess ? hipGetErrorString(e) : text);
+  if (c) (void)rfxi::sync(c);
+  rfxi::set_error(msg);
+  return rc;
+}
+
+}  // namespace
+
+struct rfx_nameset {
+  rfx_ctx* ctx;
+  uint64_t* table;  // device: `slots` keys, 0 = empty
+  uint64_t slots, n;
+  int has_zero;
+};
+
+extern "C" {
+
+rfx_reads* rfx_bam_parse_filter(rfx_text* t, uint32_t exclude_flags, int min_q, uint32_t* ref_runs, uint64_t cap, uint64_t* n_runs) {
+  static const char* const who = "rfx_bam_parse_filter";
+  char msg[256];
+  if (n_runs) *n_runs = 0;
+  if (!t || !n_runs || (!ref_runs && cap)) {
+    rfxi::set_error("rfx_bam_parse_filter: RFX_E_INVAL: a NULL argument");
+    return nullptr;
+  }
+  rfxi::text_bam& slot = rfxi::text_bam_of(t);
+  if (!slot.settled) {
+    rfxi::set_error("rfx_bam_parse_filter: RFX_E_INVAL: the arena has not been settled with rfx_bam_settle since its last reset");
+    return nullptr;
+  }
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t n = 0;
+  if (rfxi::text_ready(t, &c, &arena, &n) != RFX_OK) return nullptr;
+  const uint64_t R = slot.n_records;
+  rfx_reads* r = new rfx_reads();
+  memset(r, 0, sizeof *r);
+  r->gen = rfx_next_reads_gen();
+  r->ctx = c;
+  uint64_t* cnt = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  uint64_t* words = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  uint64_t* bases = (uint64_t*)dmalloc(c, (R + 1) * 8);
+  unsigned int* d_stat = (unsigned int*)dmalloc(c, 33 * 4);  // [0] longest kept read, [1 + l] kept reads of l < 32 bases
+  uint32_t* rec_at = nullptr;
+  int32_t* ref_id = nullptr;
+  uint64_t* run_rank = nullptr;
+  uint32_t* d_runs = nullptr;
+  auto fail = [&](hipError_t e, const char* code, const char* text) -> rfx_reads* {
+    snprintf(msg, sizeof msg, "%s: %s: %s", who, code, e != hipSuccess ? hipGetErrorString(e) : text);
+    (void)rfxi::sync(c);  // (queued read-backs point at locals of this function: deliver them now)
+    rfxi::set_error(msg);
+    dfree(c, cnt); dfree(c, words); dfree(c, bases); dfree(c, d_stat); dfree(c, rec_at); dfree(c, ref_id); dfree(c, run_rank);
+    dfree(c, d_runs);
+    rfx_reads_free(r);
+    return nullptr;
+  };
+  if (!cnt || !words || !bases || !d_stat) return fail(hipSuccess, "RFX_E_NOMEM", "out of device memory");
+  auto grid_of = [&](uint64_t m, int per_cu) { return dim3((unsigned)std::min<uint64_t>((m + 255) / 256, (uint64_t)c->n_cu * per_cu)); };
+  uint64_t totals[3] = {0, 0, 0};  // kept reads, words, bases
+  unsigned int h_stat[33];
+  memset(h_stat, 0, sizeof h_stat);
+  if (R) {
+    hipError_t e = hipMemsetAsync(d_stat, 0, 33 * 4, c->stream);
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+    {
+      rfx_span sp(c, "k_bamf_fields");
+      hipLaunchKernelGGL(k_bamf_fields, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+                         bases, d_stat);
+    }
+    rfxk::scan_tail(c, cnt, R);
+    rfxk::scan_tail(c, words, R);
+    rfxk::scan_tail(c, bases, R);
+    e = queue_read(c, &totals[0], cnt + R, 8);
+    if (e == hipSuccess) e = queue_read(c, &totals[1], words + R, 8);
+    if (e == hipSuccess) e = queue_read(c, &totals[2], bases + R, 8);
+    if (e == hipSuccess) e = queue_read(c, h_stat, d_stat, sizeof h_stat);
+    if (e == hipSuccess) e = rfxi::sync(c);  // the first wait: the totals the result is allocated by
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  }
+  const uint64_t S = totals[0], W = totals[1];
+  if (S >= (1ull << 32) || W >= (1ull << 32)) return fail(hipSuccess, "RFX_E_RANGE", "the block would reach 2^32 reads or words");
+  r->n = (uint32_t)S;
+  r->n_words = W;
+  r->n_bases = totals[2];
+  r->max_len = h_stat[0];
+  for (int l = 0; l < 32; ++l) r->short_cnt[l] = h_stat[1 + l];
+  r->codes = (uint64_t*)dmalloc(c, std::max<uint64_t>(W, 1) * 8);
+  r->good = (uint32_t*)dmalloc(c, std::max<uint64_t>(W, 1) * 4);
+  r->word_off = (uint32_t*)dmalloc(c, ((size_t)S + 1) * 4);
+  r->len = (uint32_t*)dmalloc(c, std::max<uint64_t>(S, 1) * 4);
+  rec_at = (uint32_t*)dmalloc(c, std::max<uint64_t>(S, 1) * 4);
+  ref_id = (int32_t*)dmalloc(c, std::max<uint64_t>(S, 1) * 4);
+  run_rank = (uint64_t*)dmalloc(c, (S + 1) * 8);
+  if (!r->codes || !r->good || !r->word_off || !r->len || !rec_at || !ref_id || !run_rank)
+    return fail(hipSuccess, "RFX_E_NOMEM", "out of device memory");
+  const uint32_t w_end = (uint32_t)W;
+  uint64_t runs = 0;
+  hipError_t e = hipMemcpyAsync(r->word_off + S, &w_end, 4, hipMemcpyHostToDevice, c->stream);  // (w_end lives until the wait below)
+  if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  if (S) {
+    {
+      rfx_span sp(c, "k_bamf_table");
+      hipLaunchKernelGGL(k_bamf_table, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+                         bases, r->len, r->word_off, rec_at, ref_id);
+    }
+    {
+      rfx_span sp(c, "k_bam_runs");
+      hipLaunchKernelGGL(k_bam_runs, grid_of(S, 16), dim3(256), 0, c->stream, ref_id, (uint32_t)S, run_rank);
+    }
+    rfxk::scan_tail(c, run_rank, S);
+    e = queue_read(c, &runs, run_rank + S, 8);
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+    if (W) {
+      rfx_span sp(c, "k_bamf_pack");
+      hipLaunchKernelGGL(k_bamf_pack, grid_of(W, 32), dim3(256), 0, c->stream, arena, r->word_off, r->len, rec_at, (uint32_t)S, W, min_q,
+                         r->codes, r->good);
+    }
+  }
+  e = rfxi::sync(c);  // the second wait: the block is packed, the number of runs is known
+  if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  *n_runs = runs;
+  if (runs > cap) return fail(hipSuccess, "RFX_E_RANGE", "more reference runs than the caller has room for");
+  if (runs) {
+    d_runs = (uint32_t*)dmalloc(c, runs * 8);
+    if (!d_runs) return fail(hipSuccess, "RFX_E_NOMEM", "out of device memory");
+    {
+      rfx_span sp(c, "k_bam_run_out");
+      hipLaunchKernelGGL(k_bam_run_out, grid_of(S, 16), dim3(256), 0, c->stream, ref_id, (uint32_t)S, run_rank, d_runs);
+    }
+    e = hipMemcpyAsync(ref_runs, d_runs, runs * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = rfxi::sync(c);
+    if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
+  }
+  dfree(c, cnt); dfree(c, words); dfree(c, bases); dfree(c, d_stat); dfree(c, rec_at); dfree(c, ref_id); dfree(c, run_rank);
+  dfree(c, d_runs);
+  return r;
+}
+
+int rfx_bam_name_hashes(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, uint64_t n_kept, uint64_t* out, uint64_t cap,
+                        uint64_t* n_out) {
+  static const char* const who = "rfx_bam_name_hashes";
+  if (n_out) *n_out = 0;
+  if (!t || !n_out || (cap && !out)) return RFX_E_INVAL;
+  kept_view v;
+  if (const int rc = kept_of(t, exclude_flags, who, &v)) return rc;
+  rfx_ctx* c = v.c;
+  if (v.n_kept != n_kept) {
+    dfree(c, v.kept_at);
+    return pull_fail(c, who, RFX_E_INVAL, hipSuccess, "n_kept is not the number of kept records of the arena");
+  }
+  const uint64_t nw = (n_kept + 63) / 64;
+  const uint64_t tail = (n_kept & 63u) ? (1ull << (n_kept & 63u)) - 1ull : ~0ull;
+  std::vector<uint64_t> h_mask, rank;  // the mask without the bits at and above n_kept; the selected in front of each word
+  uint64_t n_sel = n_kept;
+  if (mask) {
+    h_mask.assign(mask, mask + nw);
+    if (nw) h_mask[nw - 1] &= tail;
+    rank.resize(nw);
+    n_sel = 0;
+    for (uint64_t w = 0; w < nw; ++w) {
+      rank[w] = n_sel;
+      n_sel += (uint64_t)__builtin_popcountll(h_mask[w]);
+    }
+  }
+  *n_out = n_sel;
+  if (n_sel > cap) {
+    dfree(c, v.kept_at);
+    return pull_fail(c, who, RFX_E_RANGE, hipSuccess, "the output buffer is too small");
+  }
+  if (n_sel == 0) {
+    dfree(c, v.kept_at);
+    return RFX_OK;
+  }
+  uint64_t* d_mask = mask ? (uint64_t*)dmalloc(c, (size_t)nw * 16) : nullptr;  // the mask, then the ranks
+  uint64_t* d_out = (uint64_t*)dmalloc(c, (size_t)n_sel * 8);
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);
+    dfree(c, v.kept_at); dfree(c, d_mask); dfree(c, d_out);
+    return rc;
+  };
+  if ((mask && !d_mask) || !d_out) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  hipError_t e = hipSuccess;
+  if (mask) {  // (pageable host memory: the runtime has copied it out when the call returns)
+    e = hipMemcpyAsync(d_mask, h_mask.data(), (size_t)nw * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_mask + nw, rank.data(), (size_t)nw * 8, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  }
+  {
+    rfx_span sp(c, "k_bam_hashes");
+    const dim3 grid((unsigned)std::min<uint64_t>((n_kept + 255) / 256, (uint64_t)c->n_cu * 16));
+    hipLaunchKernelGGL(k_bam_hashes, grid, dim3(256), 0, c->stream, v.arena, v.kept_at, n_kept, (const uint64_t*)d_mask,
+                       (const uint64_t*)(d_mask ? d_mask + nw : nullptr), d_out);
+  }
+  e = hipMemcpyAsync(out, d_out, (size_t)n_sel * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  return done(RFX_OK, hipSuccess, "");
+}
+
+rfx_nameset* rfx_nameset_build(rfx_ctx* c, const uint64_t* hashes, uint64_t n) {
+  if (!c || (n && !hashes)) {
+    rfxi::set_error("rfx_nameset_build: RFX_E_INVAL: a NULL argument");
+    return nullptr;
+  }
+  (void)hipSetDevice(c->device);
+  uint64_t slots = 64;
+  while (slots < 2 * n + 2) slots <<= 1;  // at most half full: a probe ends at an empty slot
+  std::vector<uint64_t> table((size_t)slots, 0);
+  rfx_nameset* s = new rfx_nameset{c, nullptr, slots, 0, 0};
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t key = hashes[i];
+    if (key == 0) {
+      s->n += !s->has_zero;
+      s->has_zero = 1;
+      continue;
+    }
+    uint64_t at = nameset_slot(key, slots);
+    while (table[at] != 0 && table[at] != key) at = (at + 1) & (slots - 1);
+    s->n += table[at] == 0;
+    table[at] = key;
+  }
+  s->table = (uint64_t*)dmalloc(c, (size_t)slots * 8);
+  hipError_t e = s->table ? hipMemcpyAsync(s->table, table.data(), (size_t)slots * 8, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  if (s->table && e == hipSuccess) e = rfxi::sync(c);
+  if (!s->table || e != hipSuccess) {
+    pull_fail(c, "rfx_nameset_build", RFX_E_HIP, e, "RFX_E_NOMEM: out of device memory");
+    dfree(c, s->table);
+    delete s;
+    return nullptr;
+  }
+  return s;
+}
+uint64_t rfx_nameset_size(const rfx_nameset* s) { return s ? s->n : 0; }
+void rfx_nameset_free(rfx_nameset* s) {
+  if (!s) return;
+  dfree(s->ctx, s->table);
+  delete s;
+}
+
+int rfx_bam_mark_names(rfx_text* t, uint32_t exclude_flags, const rfx_nameset* set, uint64_t* mask_out, uint64_t* n_kept,
+                       uint64_t* n_marked) {
+  static const char* const who = "rfx_bam_mark_names";
+  if (n_kept) *n_kept = 0;
+  if (n_marked) *n_marked = 0;
+  if (!t || !set || !n_kept) return RFX_E_INVAL;
+  if (rfxi::text_ctx(t) != set->ctx) return pull_fail(nullptr, who, RFX_E_INVAL, hipSuccess, "the set belongs to another context");
+  kept_view v;
+  if (const int rc = kept_of(t, exclude_flags, who, &v)) return rc;
+  rfx_ctx* c = v.c;
+  *n_kept = v.n_kept;
+  if (v.n_kept == 0) return RFX_OK;
+  if (!mask_out) {
+    dfree(c, v.kept_at);
+    return pull_fail(c, who, RFX_E_INVAL, hipSuccess, "mask_out is NULL");
+  }
+  const uint64_t nw = (v.n_kept + 63) / 64;
+  uint64_t* d_mask = (uint64_t*)dmalloc(c, (size_t)(nw + 1) * 8);  // the mask, then the number of set bits
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);
+    dfree(c, v.kept_at); dfree(c, d_mask);
+    return rc;
+  };
+  if (!d_mask) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  hipError_t e = hipMemsetAsync(d_mask + nw, 0, 8, c->stream);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  {
+    rfx_span sp(c, "k_bam_mark");
+    const dim3 grid((unsigned)std::min<uint64_t>((nw + 3) / 4, (uint64_t)c->n_cu * 16));
+    hipLaunchKernelGGL(k_bam_mark, grid, dim3(256), 0, c->stream, v.arena, v.kept_at, v.n_kept, (const uint64_t*)set->table, set->slots,
+                       set->has_zero, d_mask, (unsigned long long*)(d_mask + nw));
+  }
+  uint64_t marked = 0;
+  e = hipMemcpyAsync(mask_out, d_mask, (size_t)nw * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = queue_read(c, &marked, d_mask + nw, 8);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  if (n_marked) *n_marked = marked;
+  return done(RFX_OK, hipSuccess, "");
+}
+
+int rfx_bam_gather(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, uint64_t n_kept, void* host_out, uint64_t cap,
+                   uint64_t* bytes_out, uint64_t* n_selected) {
+  static const char* const who = "rfx_bam_gather";
+  if (bytes_out) *bytes_out = 0;
+  if (n_selected) *n_selected = 0;
+  if (!t || !bytes_out || (n_kept && !mask) || (cap && !host_out)) return RFX_E_INVAL;
+  kept_view v;
+  if (const int rc = kept_of(t, exclude_flags, who, &v)) return rc;
+  rfx_ctx* c = v.c;
+  if (v.n_kept != n_kept) {
+    dfree(c, v.kept_at);
+    return pull_fail(c, who, RFX_E_INVAL, hipSuccess, "n_kept is not the number of kept records of the arena");
+  }
+  if (n_kept == 0) return RFX_OK;
+  const uint32_t nw = (uint32_t)((n_kept + 63) / 64);
+  const uint64_t tail = (n_kept & 63u) ? (1ull << (n_kept & 63u)) - 1ull : ~0ull;
+  uint64_t* d_mask = (uint64_t*)dmalloc(c, (size_t)nw * 8);
+  uint64_t* cnt = (uint64_t*)dmalloc(c, ((size_t)nw + 1) * 8);
+  uint64_t* sizes = (uint64_t*)dmalloc(c, ((size_t)nw + 1) * 8);
+  uint32_t *src_off = nullptr, *dst_off = nullptr, *out = nullptr;
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);
+    dfree(c, v.kept_at); dfree(c, d_mask); dfree(c, cnt); dfree(c, sizes); dfree(c, src_off); dfree(c, dst_off); dfree(c, out);
+    return rc;
+  };
+  if (!d_mask || !cnt || !sizes) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  const dim3 per_word((unsigned)std::min<uint64_t>(((uint64_t)nw + 255) / 256, (uint64_t)c->n_cu * 16));
+  // the mask upload (pageable host memory: the runtime has copied it out of `mask` when the call returns)
+  hipError_t e = hipMemcpyAsync(d_mask, mask, (size_t)nw * 8, hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  {
+    rfx_span sp(c, "k_bamg_sizes");
+    hipLaunchKernelGGL(k_bamg_sizes, per_word, dim3(256), 0, c->stream, v.arena, v.kept_at, d_mask, nw, tail, cnt, sizes);
+  }
+  rfxk::scan_tail(c, cnt, nw);
+  rfxk::scan_tail(c, sizes, nw);
+  uint64_t n_sel = 0, n_bytes = 0;
+  e = queue_read(c, &n_sel, cnt + nw, 8);
+  if (e == hipSuccess) e = queue_read(c, &n_bytes, sizes + nw, 8);
+  if (e == hipSuccess) e = rfxi::sync(c);  // the one wait between the mask and the result: what the result is sized by
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  *bytes_out = n_bytes;
+  if (n_selected) *n_selected = n_sel;
+  if (n_bytes > cap) return done(RFX_E_RANGE, hipSuccess, "the output buffer is too small");
+  if (n_bytes == 0) return done(RFX_OK, hipSuccess, "");
+  if (n_bytes > v.n) return done(RFX_E_HIP, hipSuccess, "the selection is larger than the arena");  // (cannot be: a subset)
+  src_off = (uint32_t*)dmalloc(c, (size_t)n_sel * 4);
+  dst_off = (uint32_t*)dmalloc(c, ((size_t)n_sel + 1) * 4);
+  out = (uint32_t*)dmalloc(c, ((size_t)n_bytes + 3) / 4 * 4);
+  if (!src_off || !dst_off || !out) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  {
+    rfx_span sp(c, "k_bamg_table");
+    hipLaunchKernelGGL(k_bamg_table, per_word, dim3(256), 0, c->stream, v.arena, v.kept_at, d_mask, nw, tail, cnt, sizes, src_off, dst_off);
+  }
+  // (every source dword lies inside the arena or in the 8 KiB behind its capacity: k_gather_copy reads at most 7 bytes
+  // behind a record's last byte, and a record lies in front of the arena's cut)
+  rfxi::gather_copy(c, v.arena, src_off, dst_off, (uint32_t)n_sel, (uint32_t)n_bytes, out);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(host_out, out, (size_t)n_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  return done(RFX_OK, hipSuccess, "");
+}
+
+}  // extern "C"

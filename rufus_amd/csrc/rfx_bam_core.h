@@ -168,3 +168,95 @@ RFX_BAM_HD void bam_pack_word(const uint32_t w[4], uint32_t nb, uint64_t* code, 
   *code = c;
   *mask = m;
 }
+
+// ---- the stranded filter form of a record (rfx_bam_parse_filter) --------------------------------------------------------
+// What rfx_pack_reads(RFX_PACK_FILTER) makes of the record as `samtools view | PassThroughSamCheck.stranded` prints it
+// (src/PassThroughSamCheck.stranded.cpp:184-223): SEQ = "=ACMGRSVTWYHKDBN"[nibble] (`*` for l_seq == 0), QUAL = 33 +
+// min(q, 93) per base (`*` for l_seq == 0 or qual[0] == 0xFF); a record with flag & 16 has its sequence reversed and
+// complemented, every base that is none of A C G T N VANISHES (the read gets shorter), and its whole quality string is
+// reversed: position j of the read meets reversed quality j.  The caller has a record bam_valid accepts, so sequence and
+// qualities lie inside the record.
+RFX_BAM_HD uint32_t bam_nibble(const uint8_t* b, uint64_t seq, uint32_t i) {
+  const uint32_t byte = bam_u8(b, seq + (i >> 1));
+  return (i & 1u) ? (byte & 15u) : (byte >> 4);
+}
+RFX_BAM_HD uint32_t bam_survives(uint32_t nib) { return (0x8116u >> nib) & 1u; }  // A C G T N: nibbles 1 2 4 8 15
+// bases of the printed read: forward max(l_seq, 1) (`*` is one base); reverse the surviving nibbles (`*` vanishes: 0)
+RFX_BAM_HD uint32_t bam_filter_len(const uint8_t* b, uint64_t p) {
+  const uint32_t l_seq = (uint32_t)bam_l_seq(b, p);
+  if (!(bam_flag(b, p) & 16u)) return l_seq ? l_seq : 1u;
+  const uint64_t seq = bam_seq_offset(b, p);
+  uint32_t n = 0;
+  for (uint32_t i = 0; i < l_seq; ++i) n += bam_survives(bam_nibble(b, seq, i));
+  return n;
+}
+// Code word j of the printed read of `len` bases (bam_filter_len) and its `good` mask: code = A C G T -> 0 .. 3, anything
+// else 0; good = (qualchar - 33 >= min_q) && base != 'N', a position without a quality character reading as '\0'
+// (rfx_pack_reads; src/RUFUS.Filter.cpp:205).  A reverse read with vanished bases is compacted by a walk from the
+// sequence's end (rare: one walk per word).
+RFX_BAM_HD void bam_filter_word(const uint8_t* b, uint64_t p, uint32_t j, uint32_t len, int min_q, uint64_t* code, uint32_t* good) {
+  const uint32_t l_seq = (uint32_t)bam_l_seq(b, p);
+  const bool rev = (bam_flag(b, p) & 16u) != 0;
+  const uint64_t seq = bam_seq_offset(b, p), qual = seq + (l_seq + 1u) / 2u;
+  const bool no_qual = l_seq == 0 || bam_u8(b, qual) == 0xFFu;
+  const uint32_t first = j * 32u, nb = len - first < 32u ? len - first : 32u;
+  uint64_t c = 0;
+  uint32_t g = 0;
+  // s: the source nibble of read position first + i.  Forward: the position; reverse: from the end, over survivors only
+  uint32_t s = rev ? l_seq : 0u, skipped = 0;
+  const bool compact = rev && len != l_seq;
+  if (rev && !compact) s = l_seq - first;
+  for (uint32_t i = 0; i < nb; ++i) {
+    const uint32_t pos = first + i;
+    uint32_t nib = 0;  // (`*`: a base that is none of A C G T N)
+    if (rev) {
+      if (compact) {
+        while (skipped <= pos) {  // (ends: the read has len > pos survivors)
+          --s;
+          skipped += bam_survives(bam_nibble(b, seq, s));
+        }
+      } else {
+        --s;
+      }
+      nib = bam_nibble(b, seq, s);
+    } else if (l_seq) {
+      nib = bam_nibble(b, seq, pos);
+    }
+    const uint32_t acgt = (0x0116u >> nib) & 1u;
+    const uint32_t fwd = (nib >> 1) - (nib >> 3);
+    c |= (uint64_t)(acgt ? (rev ? 3u - fwd : fwd) : 0u) << (2u * i);
+    // the quality character: `*` is ONE character; a reverse record's string is reversed whole
+    int q = 0;
+    if (no_qual) q = pos == 0 ? '*' : 0;
+    else if (pos < l_seq) {
+      const uint32_t v = bam_u8(b, qual + (rev ? l_seq - 1u - pos : pos));
+      q = 33 + (int)(v < 93u ? v : 93u);
+    }
+    g |= (uint32_t)(q - 33 >= min_q && nib != 15u) << i;
+  }
+  *code = c;
+  *good = g;
+}
+
+// The printed QNAME: the name field's bytes up to its first NUL (l_read_name counts the NUL; a field without one: all of
+// it).  bam_name_hash: FNV-1a over those bytes, then the splitmix64 finaliser.  Only which records are LOOKED AT depends on
+// it (rfx_bam_mark_names): names are compared as bytes wherever a result is decided.
+RFX_BAM_HD uint32_t bam_name_len(const uint8_t* b, uint64_t p) {
+  const uint32_t l = bam_l_read_name(b, p);
+  uint32_t n = 0;
+  while (n < l && bam_u8(b, p + BAM_FIXED + n) != 0) ++n;
+  return n;
+}
+RFX_BAM_HD uint64_t bam_name_hash(const uint8_t* b, uint64_t p) {
+  const uint32_t l = bam_l_read_name(b, p);
+  uint64_t h = 0xCBF29CE484222325ull;
+  for (uint32_t i = 0; i < l; ++i) {
+    const uint32_t ch = bam_u8(b, p + BAM_FIXED + i);
+    if (ch == 0) break;
+    h = (h ^ ch) * 0x100000001B3ull;
+  }
+  h += 0x9E3779B97F4A7C15ull;
+  h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+  h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+  return h ^ (h >> 31);
+}

@@ -131,6 +131,15 @@ int hip_fail(hipError_t e) {
 
 }  // namespace
 
+// k_gather_copy for another owner of the tables (rfx_bam_gather: a BAM record is at least 36 bytes, so what the kernel
+// asks of a record -- four bytes or more, and not the arena's first where it follows another -- holds)
+void rfxi::gather_copy(rfx_ctx* c, const uint8_t* arena, const uint32_t* src_off, const uint32_t* dst_off, uint32_t n_sel,
+                       uint32_t n_bytes, uint32_t* out) {
+  rfx_span sp(c, "k_gather_copy");
+  const dim3 grid((unsigned)std::min<uint64_t>(((uint64_t)n_bytes / 4 + 1 + 255) / 256, (uint64_t)c->n_cu * 32));
+  hipLaunchKernelGGL(k_gather_copy, grid, dim3(256), 0, c->stream, (const uint32_t*)arena, src_off, dst_off, n_sel, n_bytes, out);
+}
+
 extern "C" int rfx_text_gather(rfx_text* t, const uint64_t* hitmask, uint64_t n_records, void* host_out, uint64_t cap,
                                uint64_t* bytes_out, uint64_t* n_selected) {
   if (bytes_out) *bytes_out = 0;

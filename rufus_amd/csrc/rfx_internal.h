@@ -585,6 +585,12 @@ struct text_bam {
 rfx_ctx* text_ctx(rfx_text* t);
 text_bam& text_bam_of(rfx_text* t);
 int text_cut(rfx_text* t, rfx_text* next, uint64_t cut, uint64_t* carried, const char* who);
+// k_gather_copy (rfx_gather.hip) queued on the ctx stream for rfx_bam_gather: record o of the selection is the arena's
+// bytes from src_off[o], dst_off[o + 1] - dst_off[o] of them, and goes to byte dst_off[o] of `out` (dst_off[n_sel] =
+// n_bytes > 0; `out` holds n_bytes rounded up to a dword).  Every record is at least four bytes long and a record that
+// follows another in the selection does not start at the arena's first four bytes.
+void gather_copy(rfx_ctx*, const uint8_t* arena, const uint32_t* src_off, const uint32_t* dst_off, uint32_t n_sel, uint32_t n_bytes,
+                 uint32_t* out);
 }  // namespace rfxi
 
 // Launch bracket: records a HIP-event span on the ctx stream (or `stream`: an arena's own, rfx_text.hip) when profiling

@@ -175,10 +175,9 @@ def is_bam(data: bytes) -> bool:
         return False
 
 
-def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, arena_bytes: int = 256 << 20):
-    """The records of a BAM file with flag & exclude_flags == 0 as count blocks, an arena at a time: yields (block, runs,
-    reference names) -- what `samtools view -F 3328 X.bam | PassThroughSamCheck` hands the counter, found and packed on the
-    device (capi.bam_header, TextArena.append_bgzf / bam_settle / bam_parse).  The caller frees the blocks."""
+def _bam_arenas(ctx: capi.Context, data: bytes, arena_bytes: int):
+    """The settled arenas of a BAM file, one after the other: yields (arena, whole records, header).  The arena is reset
+    when the caller comes back for the next."""
     hdr = capi.bam_header(data)
     if hdr is None:
         raise ValueError("the BAM header is not whole")
@@ -197,8 +196,7 @@ def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, a
             n, _ = a.bam_settle(None if last else arenas[cur ^ 1], skip, hdr["n_ref"])
             skip = 0
             if n:
-                blk, runs = a.bam_parse(exclude_flags)
-                yield blk, runs, hdr["names"]
+                yield a, n, hdr
             a.reset()
             if last:
                 break
@@ -206,6 +204,15 @@ def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, a
     finally:
         for a in arenas:
             a.close()
+
+
+def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, arena_bytes: int = 256 << 20):
+    """The records of a BAM file with flag & exclude_flags == 0 as count blocks, an arena at a time: yields (block, runs,
+    reference names) -- what `samtools view -F 3328 X.bam | PassThroughSamCheck` hands the counter, found and packed on the
+    device (capi.bam_header, TextArena.append_bgzf / bam_settle / bam_parse).  The caller frees the blocks."""
+    for a, _, hdr in _bam_arenas(ctx, data, arena_bytes):
+        blk, runs = a.bam_parse(exclude_flags)
+        yield blk, runs, hdr["names"]
 
 
 def jellyfish_count(ctx: capi.Context, inputs, k: int, size: int, canonical: bool = True, lower: int = 0,
@@ -370,3 +377,87 @@ def decode_reads(arrays: dict) -> list:
         letters = np.where(valid.astype(bool), letters, np.uint8(ord("N")))
     flat = np.ascontiguousarray(letters, dtype=np.uint8).reshape(-1).tobytes()
     return [flat[32 * int(w):32 * int(w) + int(n)] for w, n in zip(word_off[:len(lens)], lens)]
+
+
+# ---------------------------------------------------------------------------------------------------
+# RUFUS.Filter --bam
+# ---------------------------------------------------------------------------------------------------
+_SEQ_LETTERS = b"=ACMGRSVTWYHKDBN"
+_REVCOMP = bytes.maketrans(b"ACGTN", b"TGCAN")
+
+
+def _bam_printed(rec: bytes):
+    """(QNAME, SEQ, QUAL) of one raw BAM record (block_size field first) as `samtools view | PassThroughSamCheck.stranded`
+    prints it: reverse strand reverse-complemented with every base but A C G T N dropped, its quality string reversed."""
+    l_name, flag, l_seq = rec[12], int.from_bytes(rec[18:20], "little"), int.from_bytes(rec[20:24], "little")
+    at = 36 + l_name + 4 * int.from_bytes(rec[16:18], "little")
+    name = rec[36:36 + l_name].split(b"\0")[0]
+    nib = np.frombuffer(rec[at:at + (l_seq + 1) // 2], np.uint8)
+    seq = np.frombuffer(_SEQ_LETTERS, np.uint8)[np.stack([nib >> 4, nib & 15], 1).reshape(-1)[:l_seq]].tobytes() if l_seq else b"*"
+    q = rec[at + (l_seq + 1) // 2:at + (l_seq + 1) // 2 + l_seq]
+    qual = b"*" if not l_seq or q[0] == 0xFF else bytes(33 + min(v, 93) for v in q)
+    if flag & 16:
+        seq = bytes(c for c in seq[::-1] if c in b"ACGTN").translate(_REVCOMP)
+        qual = qual[::-1]
+    return name, seq, qual
+
+
+def filter_bam(ctx: capi.Context, data: bytes, hash_list: bytes, k: int, min_q: int, thresh: int, exclude_flags: int = 3328,
+               arena_bytes: int = 256 << 20):
+    """``RUFUS.Filter --bam`` on the bytes of a BAM file: (Mate1 bytes, Mate2 bytes, chromosome log) -- what `samtools view
+    -F exclude_flags | PassThroughSamCheck.stranded | RUFUS.Filter` writes.  Two passes, both on the device: the scan of
+    every kept record in its stranded form (TextArena.bam_parse_filter, MutantSet.filter, bam_name_hashes of the hits),
+    then the pull of every record of a hit name (NameSet, bam_mark_names, bam_gather); the few pulled records are printed
+    and paired by name here."""
+    mset = capi.MutantSet(ctx, capi.hashlist_keys(hash_list, k, single_end=False), k)
+    hit_index, hit_hash, refs, names, base = [], [], [], [], 0
+    try:
+        for a, _, hdr in _bam_arenas(ctx, data, arena_bytes):
+            names = hdr["names"]
+            blk, runs = a.bam_parse_filter(min_q, exclude_flags)
+            try:
+                _, mask, n_hit = mset.filter(blk, thresh, last_base_skipped=True, want_hits=False)
+                n = blk.n
+            finally:
+                blk.free()
+            refs += [int(r) for r in runs[:, 1]]
+            if n_hit:
+                hit_hash.append(a.bam_name_hashes(n, mask, exclude_flags))
+                hit_index += [base + int(i) for i in np.flatnonzero(_mask_bits(mask, n))]
+            base += n
+    finally:
+        mset.free()
+    log, current = [], b"notachr"
+    for r in refs:
+        name = b"*" if r < 0 else names[r]
+        if name != current:
+            log.append(current)
+            current = name
+    log = b"".join(x + b"\n" for x in log + [current])
+    if not hit_index:
+        return b"", b"", log
+    hits, waiting, out1, out2, base = set(hit_index), {}, [], [], 0
+    nset = capi.NameSet(ctx, np.concatenate(hit_hash))
+    try:
+        for a, _, _ in _bam_arenas(ctx, data, arena_bytes):
+            mask, n_kept, n_marked = a.bam_mark_names(nset, exclude_flags)
+            if n_marked:
+                blob, p = a.bam_gather(mask, n_kept, exclude_flags), 0
+                for i in np.flatnonzero(_mask_bits(mask, n_kept)):
+                    size = 4 + int.from_bytes(blob[p:p + 4], "little")
+                    name, seq, qual = _bam_printed(blob[p:p + size])
+                    p += size
+                    hit = base + int(i) in hits
+                    if name not in waiting:
+                        waiting[name] = (seq, qual, hit)
+                        continue
+                    seq2, qual2, hit2 = waiting.pop(name)  # the later record is mate 1, the stored one mate 2
+                    if not seq:
+                        raise ValueError("empty sequence line (undefined behaviour in the reference; rejected)")
+                    if hit or hit2:
+                        out1.append(b"@" + name + b"\n" + seq + b"\n+\n" + qual + b"\n")
+                        out2.append(b"@" + name + b"\n" + seq2 + b"\n+\n" + qual2 + b"\n")
+            base += n_kept
+    finally:
+        nset.free()
+    return b"".join(out1), b"".join(out2), log
