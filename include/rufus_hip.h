@@ -380,6 +380,35 @@ int rfx_bam_mark_names(rfx_text* t, uint32_t exclude_flags, const rfx_nameset*, 
 int rfx_bam_gather(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, uint64_t n_kept, void* host_out, uint64_t cap,
                    uint64_t* bytes, uint64_t* n_selected);
 
+/* -------------------------------------------------------------------------------------------
+ * BAM in, by address: where the kept records lie, and records fetched out of blocks inflated on their own
+ * Replaces the repeated inflate of the subject's file: `samtools view` runs over all of X.bam once for the count
+ * (scripts/RunJellyForRUFUS.sh:28-29) and again for the read pull (runRufus.sh:964-967).  The count notes every kept
+ * record's address; the pull inflates only the blocks that hold the records it wants.
+ *
+ * rfx_bam_locate: for the kept records of an arena settled by rfx_bam_settle, in file order, start_out[i] = the arena
+ * offset of record i's block_size field and bytes_out[i] = 4 + block_size (host memory, n_kept entries each).  n_kept
+ * must be the arena's number of kept records (RFX_E_INVAL).
+ *
+ * rfx_bam_fetch: the arena need NOT be settled: it holds whatever BGZF blocks were appended, in any context, and the call
+ * waits for their inflate (a block that did not inflate: RFX_E_FORMAT with the "rfx_bgzf:" text).  start / bytes are host
+ * memory, n entries, in any order, duplicates allowed; the bytes [start[i], start[i] + bytes[i]) of the arena go to
+ * host_out one behind the other, in list order.  Before anything is copied every entry is checked on the device:
+ * bytes[i] >= 36, start[i] + bytes[i] <= rfx_text_bytes(t), and the little-endian word at start[i] (any residue) equals
+ * bytes[i] - 4.  One failure: RFX_E_FORMAT, rfx_last_error() = "rfx_bam_fetch: entry <the lowest failing index> ...",
+ * nothing written.  *out_bytes = the sum of bytes[]; cap too small: RFX_E_RANGE with *out_bytes set, nothing written.
+ * n == 0 is valid.  One wait for the device between the upload of the lists and the copy of the result.
+ *
+ * rfx_nameset_mark: rfx_bam_mark_names with the hashes from host memory instead of from records: bit i % 64 of
+ * mask_out[i / 64] = hashes[i] is in the set (ceil(n / 64) words, the bits at and above n clear), *n_marked (may be
+ * NULL) = the set bits.  The hashes cross in pieces of 2^22 (RFX_NAMESET_PIECE, a multiple of 64: a test knob that
+ * changes no result), so device memory does not grow with n.
+ * ------------------------------------------------------------------------------------------- */
+int rfx_bam_locate(rfx_text* t, uint32_t exclude_flags, uint64_t n_kept, uint32_t* start_out, uint32_t* bytes_out);
+int rfx_bam_fetch(rfx_text* t, const uint32_t* start, const uint32_t* bytes, uint64_t n, void* host_out, uint64_t cap,
+                  uint64_t* out_bytes);
+int rfx_nameset_mark(const rfx_nameset*, const uint64_t* hashes, uint64_t n, uint64_t* mask_out, uint64_t* n_marked);
+
 /* Synthetic trio workload (BASELINE.json configs[1]-[4]) -- benchmark and scale-test input,
  * not a replacement of any reference code.  Every base is a pure function of (parameters, pair, mate, base
  * index) -- see rufus_amd/csrc/rfx_synth.h -- so a 30x WGS sample (6.2e8 reads) is generated straight into

@@ -115,6 +115,9 @@ SIGNATURES = {
     "rfx_nameset_free": (None, [C.c_void_p]),
     "rfx_bam_mark_names": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u64p, u64p]),
     "rfx_bam_gather": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]),
+    "rfx_bam_locate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p]),
+    "rfx_bam_fetch": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
+    "rfx_nameset_mark": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p, u64p]),
     "rfx_reads_of_length": (C.c_uint64, [C.c_void_p, C.c_uint32]),
     "rfx_synth_text": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rfx_synth_snv": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_char_p, C.c_char_p]),
@@ -571,6 +574,33 @@ class TextArena:
         _check(rc, "rfx_bam_gather")
         return out[:nb].tobytes()
 
+    def bam_locate(self, n_kept: int, exclude_flags: int = 3328):
+        """(start, bytes), uint32 each: the arena offset of every kept record's block_size field and 4 + block_size, in file
+        order (rfx_bam_locate)."""
+        start, nbytes = np.zeros(max(n_kept, 1), np.uint32), np.zeros(max(n_kept, 1), np.uint32)
+        _check(lib().rfx_bam_locate(self._h, exclude_flags, n_kept, _p(start, u32p), _p(nbytes, u32p)), "rfx_bam_locate")
+        return start[:n_kept], nbytes[:n_kept]
+
+    def bam_fetch_into(self, start: np.ndarray, nbytes: np.ndarray, out: np.ndarray, cap: "int | None" = None):
+        """rfx_bam_fetch into `out` (uint8; cap: what the call is told the buffer holds, default all of it): (return code,
+        bytes).  E_RANGE: bytes = the need, nothing written."""
+        start = np.ascontiguousarray(start, dtype=np.uint32)
+        nbytes = np.ascontiguousarray(nbytes, dtype=np.uint32)
+        if len(start) != len(nbytes):
+            raise ValueError("start and bytes differ in length")
+        nb = C.c_uint64(0)
+        rc = lib().rfx_bam_fetch(self._h, _p(start, u32p) if len(start) else None, _p(nbytes, u32p) if len(start) else None,
+                                 len(start), out.ctypes.data_as(C.c_void_p), len(out) if cap is None else cap, C.byref(nb))
+        return int(rc), int(nb.value)
+
+    def bam_fetch(self, start: np.ndarray, nbytes: np.ndarray) -> bytes:
+        """The arena's bytes [start[i], start[i] + bytes[i]), one behind the other in list order; every entry must be a
+        record that begins with its own length (rfx_bam_fetch).  The arena need not be settled."""
+        out = np.zeros(max(int(np.asarray(nbytes, dtype=np.uint64).sum()), 1), np.uint8)
+        rc, nb = self.bam_fetch_into(start, nbytes, out)
+        _check(rc, "rfx_bam_fetch")
+        return out[:nb].tobytes()
+
     def records(self) -> int:
         """Whole records (groups of four lines) the arena holds (rfx_text_records)."""
         n = C.c_uint64(0)
@@ -648,6 +678,15 @@ class NameSet:
 
     def __len__(self) -> int:
         return int(lib().rfx_nameset_size(self._h))
+
+    def mark(self, hashes: np.ndarray):
+        """(mask, marked): bit i of the uint64 mask = hashes[i] is in the set (rfx_nameset_mark)."""
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        mask = np.zeros((len(hashes) + 63) // 64, np.uint64)
+        n_marked = C.c_uint64(0)
+        _check(lib().rfx_nameset_mark(self._h, _p(hashes, u64p) if len(hashes) else None, len(hashes),
+                                      _p(mask, u64p) if len(mask) else None, C.byref(n_marked)), "rfx_nameset_mark")
+        return mask, int(n_marked.value)
 
     def free(self):
         if self._h:

@@ -67,12 +67,17 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // records as RUFUS.Filter would see them -- printed orientation, packed for MinQ Q (default 15), name hash, place in
   // the stream -- in FILE (rfx_packed_cache.hpp; put it in /dev/shm): `RUFUS.Filter --packed FILE CHR HashList SPOOL ...`
   // scans that instead of parsing the stream a second time.
+  // With --bam (ONE input): the BAM-kind cache of rfx_bam_cache.hpp -- per arena the filter's view of the kept records as
+  // the device packs it, their name hashes and their addresses in the inflated stream, and an index of the file's BGZF
+  // blocks -- so that `RUFUS.Filter --packed FILE CHR HashList X.bam ...` inflates only the blocks of the hit names'
+  // records instead of the whole file twice (runRufus.sh:964-967 after scripts/RunJellyForRUFUS.sh:28-29).
   const char* keep_path = nullptr;
   int keep_minq = 15;
   // --bam CHR_FILE [--bam-exclude N] (not in jellyfish): the input is a BAM file and this process does what
   // `samtools view -F N X.bam | PassThroughSamCheck CHR_FILE | jellyfish count` does (runRufus.sh:599,
   // scripts/RunJellyForRUFUS.sh:28-29; N defaults to 3328) -- BGZF inflated, the records found and their sequences packed
-  // on the device (rfx_ingest.hpp BamIngest; csrc/rfx_bam.hip), the chromosome log written.
+  // on the device (rfx_ingest.hpp BamIngest; csrc/rfx_bam.hip), the chromosome log written.  Goes with --keep-packed
+  // (above), not with --sam or --spool.
   const char* bam_chr = nullptr;
   uint32_t bam_exclude = 3328;
   enum { OPT_DISK = 1000, OPT_OCL, OPT_TIMING, OPT_TEXT, OPT_SAM, OPT_SPOOL, OPT_KEEP, OPT_KEEPQ, OPT_BAM, OPT_BAMX };
@@ -114,7 +119,7 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   static const char* const bam_alone =
       "rufus_amd jellyfish count: --bam finds and packs the records on the device, which needs one device and none of --sam, "
       "--spool, --keep-packed";
-  if (bam_chr && (sam_chr || spool_path || keep_path)) die(bam_alone);
+  if (bam_chr && (sam_chr || spool_path)) die(bam_alone);
   int lsize = 0;
   while ((1ull << lsize) < size) ++lsize;
   if (lsize < 1) lsize = 1;
@@ -208,7 +213,9 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
     prealloc_frac = frac;
     prealloc_min = min_bytes;
   }
-  if (keep_path && (!sam_chr || inputs.size() != 1))
+  if (keep_path && bam_chr && inputs.size() != 1)
+    die("rufus_amd jellyfish count: --bam --keep-packed goes with ONE input: the cache describes one file's records");
+  if (keep_path && !bam_chr && (!sam_chr || inputs.size() != 1))
     die("rufus_amd jellyfish count: --keep-packed goes with --sam and ONE input (a pipe with --spool, or a SAM file)");
   if (keep_path && any_stream && !spool_path)  // (the cache points into the stream: without a copy of it there is nothing to point into)
     die("rufus_amd jellyfish count: --keep-packed of a piped input needs --spool FILE (the cache refers to lines of the stream)");
@@ -312,8 +319,8 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // bytes per read over PCIe and the host only reads the file.  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160).
   // Plain gzip (no `BC` subfield) is not BGZF and goes where it went before.
   std::unique_ptr<BgzfIngest> bgzf_ingest;
-  // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, none of --sam, --spool,
-  // --keep-packed, as the bgzf route.
+  // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, neither --sam nor --spool;
+  // --keep-packed with one input leaves the BAM-kind cache (rfx_bam_cache.hpp).
   std::unique_ptr<BamIngest> bam_ingest;
   if (bam_chr && n_gpu != 1) die(bam_alone);
   {
@@ -329,6 +336,11 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
           bam_ingest.reset(new BamIngest(
               ctx, [&](rfx_reads* r) { sink_to(0, r); }, bam_exclude, arena_bytes,
               getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20));
+          if (keep_path) {
+            const int kfd = ::open(keep_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (kfd < 0) die(std::string("Can't open the packed-read cache '") + keep_path + "'");
+            bam_ingest->set_keep_packed(kfd, keep_minq);
+          }
           trace("count: bam route, arenas open");
         }
         void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
@@ -337,6 +349,10 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
         bam_ingest->feed_mapped((const char*)m, in.size);
         munmap(m, in.size);
         trace(("count: " + bam_ingest->counts()).c_str());
+        if (keep_path) {  // (one input: checked above) the file is a cache only from here on
+          bam_ingest->finish_keep_packed();
+          trace(("count: " + bam_ingest->keep_counts()).c_str());
+        }
         if (in.fd > 0) ::close(in.fd);
         continue;
       }

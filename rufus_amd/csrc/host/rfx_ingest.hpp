@@ -34,6 +34,7 @@
 #include "rfx_sam.hpp"
 #include "rfx_bam_pairs.hpp"
 #include "rfx_packed_cache.hpp"
+#include "rfx_bam_cache.hpp"
 
 namespace rfxcli {
 
@@ -1254,6 +1255,11 @@ class BgzfIngest {
 #pragma weak rfx_bam_header
 #pragma weak rfx_bam_settle
 #pragma weak rfx_bam_parse
+#pragma weak rfx_bam_parse_filter
+#pragma weak rfx_bam_name_hashes
+#pragma weak rfx_bam_locate
+#pragma weak rfx_reads_get
+#pragma weak rfx_reads_words
 class BamIngest {
   rfx_ctx* ctx_;
   std::function<void(rfx_reads*)> sink_;
@@ -1273,6 +1279,60 @@ class BamIngest {
   // for every settled arena instead of rfx_bam_parse + sink, and reports the arena's kept records
   std::function<uint64_t(rfx_text*, uint64_t)> per_arena_;
   std::string tool_ = "rufus_amd jellyfish count";
+  // set_keep_packed (`jellyfish count --bam CHR --keep-packed FILE`; rfx_bam_cache.hpp): every settled arena with kept
+  // records also leaves a chunk of FILE -- the filter's view of the records (rfx_bam_parse_filter for MinQ), their name
+  // hashes and their addresses -- so that `RUFUS.Filter --packed FILE` need not inflate the file twice more
+  // (runRufus.sh:964-967 after scripts/RunJellyForRUFUS.sh:28-29)
+  int cache_fd_ = -1, cache_minq_ = 0;
+  rfxbamcache::Writer cache_;
+  struct KeepBufs {
+    std::vector<uint64_t> hash, codes;
+    std::vector<uint32_t> start, bytes, len, word_off, good, runs;
+  } keep_;
+
+  [[noreturn]] void cache_write_error() { die(tool_ + ": write error on the packed-read cache: " + strerror(errno)); }
+  // base: the stream offset of the arena's byte 0
+  void keep_chunk(rfx_text* t, uint64_t n_records, uint64_t base) {
+    keep_.runs.resize((size_t)2 * n_records);
+    uint64_t n_runs = 0;
+    rfx_reads* rd = rfx_bam_parse_filter(t, exclude_, cache_minq_, keep_.runs.data(), n_records, &n_runs);
+    if (!rd) die(tool_ + ": --keep-packed: " + rfx_last_error());
+    const uint32_t n = rfx_reads_count(rd);
+    const uint64_t words = rfx_reads_words(rd);
+    if (n == 0) {  // (an arena none of whose records is kept leaves no chunk)
+      rfx_reads_free(rd);
+      return;
+    }
+    keep_.codes.resize((size_t)words + 1);
+    keep_.good.resize((size_t)words + 1);
+    keep_.word_off.resize((size_t)n + 1);
+    keep_.len.resize(n);
+    keep_.hash.resize(n);
+    keep_.start.resize(n);
+    keep_.bytes.resize(n);
+    int rc = rfx_reads_get(rd, keep_.codes.data(), nullptr, keep_.good.data(), keep_.word_off.data(), keep_.len.data());
+    rfx_reads_free(rd);
+    if (rc != RFX_OK) die(tool_ + ": --keep-packed: rfx_reads_get: " + rfx_last_error());
+    uint64_t got = 0;
+    rc = rfx_bam_name_hashes(t, exclude_, nullptr, n, keep_.hash.data(), n, &got);
+    if (rc != RFX_OK || got != n) die(tool_ + ": --keep-packed: rfx_bam_name_hashes: " + rfx_last_error());
+    rc = rfx_bam_locate(t, exclude_, n, keep_.start.data(), keep_.bytes.data());
+    if (rc != RFX_OK) die(tool_ + ": --keep-packed: rfx_bam_locate: " + rfx_last_error());
+    rfxbamcache::Chunk c;
+    c.stream_off = base;
+    c.n = n;
+    c.n_words = (uint32_t)words;
+    c.n_runs = (uint32_t)n_runs;
+    c.hash = keep_.hash.data();
+    c.start = keep_.start.data();
+    c.rbytes = keep_.bytes.data();
+    c.len = keep_.len.data();
+    c.word_off = keep_.word_off.data();
+    c.codes = keep_.codes.data();
+    c.good = keep_.good.data();
+    c.runs = keep_.runs.data();
+    if (!cache_.add_chunk(c)) cache_write_error();
+  }
 
   void settle_buf(Buf& b) {
     if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
@@ -1282,7 +1342,8 @@ class BamIngest {
     for (Buf& b : ring_)
       if (b.t == t) settle_buf(b);
   }
-  void parse_and_sink(rfx_text* t, uint64_t n_records) {
+  void parse_and_sink(rfx_text* t, uint64_t n_records, uint64_t base) {
+    if (n_records && cache_fd_ >= 0) keep_chunk(t, n_records, base);
     if (n_records && per_arena_) {
       reads_ += per_arena_(t, n_records);
       records_ += n_records;
@@ -1348,6 +1409,25 @@ class BamIngest {
       if (chr_runs_.empty() || chr_runs_.back() != ref) chr_runs_.push_back(ref);
     }
   }
+  // before feed_mapped, with ONE input: fd is the cache file, open for writing and empty
+  void set_keep_packed(int fd, int min_q) {
+    if (!rfx_bam_parse_filter || !rfx_bam_name_hashes || !rfx_bam_locate) die(tool_ + ": this library cannot keep a BAM's packed reads");
+    cache_fd_ = fd;
+    cache_minq_ = min_q;
+  }
+  // after feed_mapped: the block index and the header that makes the file a cache
+  void finish_keep_packed() {
+    if (cache_fd_ < 0) return;
+    const bool ok = cache_.finish();
+    if (::close(cache_fd_) != 0 || !ok) cache_write_error();
+    cache_fd_ = -1;
+  }
+  std::string keep_counts() const {
+    char b[200];
+    snprintf(b, sizeof b, "bam cache: %llu records, %llu bytes, stream %llu bytes", (unsigned long long)cache_.records(),
+             (unsigned long long)cache_.file_bytes(), (unsigned long long)cache_.stream_bytes());
+    return b;
+  }
   uint64_t reads() const { return reads_; }
   uint64_t records() const { return records_; }
   uint64_t arenas() const { return arenas_; }
@@ -1379,6 +1459,28 @@ class BamIngest {
       for (size_t at = 0; at < (size_t)names_bytes; at += strlen(names.data() + at) + 1) ref_names_.emplace_back(names.data() + at);
     }
     if (rc != RFX_OK || !complete) die(tool_ + ": --bam: the input does not begin with a whole BAM header");
+    // the cache's block index: EVERY block of the file from byte 0, the header's too (the stream is all of them); `base`:
+    // the stream offset of the first arena's byte 0 = of the block the records begin in
+    uint64_t base = 0;
+    if (cache_fd_ >= 0) {
+      std::string names;
+      for (const std::string& n : ref_names_) names.append(n).push_back('\0');
+      if (!cache_.open(cache_fd_, cache_minq_, exclude_, (uint32_t)n_ref_, names.data(), names.size())) cache_write_error();
+      for (size_t at = 0; at < size;) {
+        uint32_t nb = 0;
+        uint64_t used = 0, inf = 0;
+        rc = rfx_bgzf_scan(m + at, std::min<size_t>(size - at, 1u << 16), 1, &nb, &used, &inf);
+        if (nb != 1) {
+          char msg[128];
+          snprintf(msg, sizeof msg, "%s BGZF block at byte %llu of the compressed input", rc == RFX_OK ? "truncated" : "no",
+                   (unsigned long long)at);
+          die(tool_ + ": " + msg);
+        }
+        if (at == (size_t)first_block) base = cache_.stream_bytes();
+        cache_.add_block((uint32_t)used, (uint32_t)inf);
+        at += (size_t)used;
+      }
+    }
     // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of inflated bytes
     struct Run { size_t at, n; uint64_t inflated; };
     std::vector<Run> runs;
@@ -1425,13 +1527,15 @@ class BamIngest {
       const uint64_t n_records = settle(t, nx, skip, &carried);
       if (n_records == 0) die(tool_ + ": --bam: a record that is longer than an arena");
       skip = 0;
+      const uint64_t cut = rfx_text_bytes(t);  // (the next arena begins with what lay behind it: its byte 0 is stream byte base + cut)
       more = fill(nx);  // queued, not waited for: the device inflates it beside this arena's count
-      parse_and_sink(t, n_records);
+      parse_and_sink(t, n_records, base);
+      base += cut;
       cur ^= 1;
     }
     uint64_t carried = 0;
     const uint64_t n_records = settle(arena_[cur], nullptr, skip, &carried);  // (a tail: the file ends inside a record)
-    parse_and_sink(arena_[cur], n_records);
+    parse_and_sink(arena_[cur], n_records, base);
   }
 };
 
@@ -1818,6 +1922,183 @@ class BamPairFilter {
     snprintf(b, sizeof b, "bam filter route: arenas %llu records %llu reads %llu hits %llu names %llu gathered %llu pairs %llu",
              (unsigned long long)arenas_, (unsigned long long)records_, (unsigned long long)reads_,
              (unsigned long long)hit_index_.size(), (unsigned long long)names_, (unsigned long long)tail_.records,
+             (unsigned long long)tail_.walk.n_found);
+    return b;
+  }
+};
+
+// ---- the subject's hit pairs from its BAM and the count's cache: no pass over the file ----------------------------------
+// Replaces BamPairFilter's two passes (and with them the second and third inflate of the subject's file, runRufus.sh:964-967
+// after scripts/RunJellyForRUFUS.sh:28-29) when `jellyfish count --bam .. --keep-packed CACHE` has left rfx_bam_cache.hpp's
+// file:
+//   scan    per chunk rfx_reads_upload -> rfx_filter (every record by itself, last base skipped): scan_arena's masks, from
+//           the arrays the same rfx_bam_parse_filter made.  Kept: the hit records' global kept indices and name hashes
+//   mark    rfx_nameset_build of the hit hashes; the chunks' hash arrays through rfx_nameset_mark -> the selected records
+//           (global index, stream offset, bytes), ascending
+//   fetch   rfxbamcache::plan_fetch -> per batch the listed BGZF blocks, copied one behind the other into a page-locked
+//           ring, rfx_text_append_bgzf, rfx_bam_fetch of the batch's records
+//   verify  every fetched record: whole, bam_valid, and its QNAME's hash the cached one -- else the cache does not
+//           describe this file (false: the caller takes the two-pass route; nothing has been written)
+//   tail    BamPairTail::add in stream order, the hit bit by global index: BamPairFilter's tail
+// Exact for BamPairFilter's reason: what becomes of a name depends only on the records of that name, in stream order, and
+// the selection is every kept record whose name hash is in the hit set.
+// (weak, as above)
+#pragma weak rfx_bam_fetch
+#pragma weak rfx_nameset_mark
+class BamCachePull {
+  rfx_ctx* ctx_;
+  rfx_set* set_;
+  int thresh_;
+  size_t arena_bytes_, piece_;
+  std::vector<uint64_t> hit_index_, hit_hash_, mask_;
+  std::vector<std::string> chr_log_;
+  rfxsam::BamPairTail tail_;
+  uint64_t chunks_ = 0, records_ = 0, names_ = 0, selected_ = 0, blocks_ = 0, index_blocks_ = 0, batches_ = 0;
+  static constexpr const char* TOOL = "rufus_amd RUFUS.Filter";
+
+  [[noreturn]] static void fail(const char* what) { die(std::string(TOOL) + ": --packed: " + what + ": " + rfx_last_error()); }
+
+ public:
+  BamCachePull(rfx_ctx* ctx, rfx_set* set, int thresh, size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20)
+      : ctx_(ctx), set_(set), thresh_(thresh), arena_bytes_(arena_bytes), piece_(std::max<size_t>(piece, 1u << 16)) {
+    if (!rfx_bam_fetch || !rfx_nameset_mark || !rfx_nameset_build || !rfx_nameset_free || !rfx_text_append_bgzf)
+      die(std::string(TOOL) + ": this library cannot fetch BAM records");
+  }
+  // the scan, from the cache alone.  Afterwards hits() says whether pull() has anything to do
+  void scan(const rfxbamcache::Cache& cache) {
+    uint64_t base = 0;
+    std::vector<int32_t> runs;
+    for (const rfxbamcache::Chunk& v : cache.chunks) {
+      rfx_reads* rd = rfx_reads_upload(ctx_, v.codes, nullptr, v.good, v.word_off, v.len, v.n);
+      if (!rd) fail("rfx_reads_upload");
+      mask_.assign(((size_t)v.n + 63) / 64 + 1, 0);
+      uint64_t nh = 0;
+      // every record by itself; paired tool: `i < length()-1`, the last base is never examined (src/RUFUS.Filter.cpp:203)
+      const int rc = rfx_filter(set_, rd, thresh_, 1, nullptr, mask_.data(), &nh);
+      rfx_reads_free(rd);
+      if (rc) fail("rfx_filter");
+      for (uint32_t i = 0; i < v.n && nh; ++i)
+        if ((mask_[i >> 6] >> (i & 63)) & 1) {
+          hit_index_.push_back(base + i);
+          hit_hash_.push_back(v.hash[i]);
+        }
+      for (uint32_t r = 0; r < v.n_runs; ++r) {  // BamIngest::add_runs' rule: a chunk that begins with the refID the one
+        const int32_t ref = (int32_t)v.runs[2 * r + 1];  // before ended with is no change
+        if (runs.empty() || runs.back() != ref) runs.push_back(ref);
+      }
+      base += v.n;
+      ++chunks_;
+    }
+    records_ = base;
+    index_blocks_ = cache.h.n_blocks;
+    chr_log_.assign(1, "notachr");
+    for (const int32_t ref : runs) chr_log_.push_back(ref < 0 || (size_t)ref >= cache.names.size() ? std::string("*") : cache.names[(size_t)ref]);
+  }
+  bool hits() const { return !hit_index_.empty(); }
+  // m[0, size): the mapped BAM the cache was made from.  false: it is not -- a fetched record is not the record the cache
+  // describes.  Dies on a block that does not inflate.
+  bool pull(const rfxbamcache::Cache& cache, const char* m, size_t size) {
+    rfx_nameset* names = rfx_nameset_build(ctx_, hit_hash_.data(), hit_hash_.size());
+    if (!names) fail("rfx_nameset_build");
+    names_ = rfx_nameset_size(names);
+    std::vector<rfxbamcache::Selected> sel;
+    std::vector<uint64_t> sel_index, sel_hash;
+    uint64_t base = 0;
+    for (const rfxbamcache::Chunk& v : cache.chunks) {
+      mask_.assign(((size_t)v.n + 63) / 64 + 1, 0);
+      uint64_t marked = 0;
+      if (rfx_nameset_mark(names, v.hash, v.n, mask_.data(), &marked) != RFX_OK) fail("rfx_nameset_mark");
+      for (uint32_t i = 0; i < v.n && marked; ++i)
+        if ((mask_[i >> 6] >> (i & 63)) & 1) {
+          rfxbamcache::Selected s;
+          s.stream_off = v.stream_off + v.start[i];
+          s.bytes = v.rbytes[i];
+          sel.push_back(s);
+          sel_index.push_back(base + i);
+          sel_hash.push_back(v.hash[i]);
+        }
+      base += v.n;
+    }
+    rfx_nameset_free(names);
+    selected_ = sel.size();
+    std::vector<rfxbamcache::Batch> plan;
+    std::string err;
+    if (!rfxbamcache::plan_fetch(cache.index, cache.h.n_blocks, cache.h.stream_bytes, sel, arena_bytes_, plan, &err))
+      die(std::string(TOOL) + ": --packed: " + err + " (RFX_BAM_ARENA)");
+    rfx_text* arena = rfx_text_open(ctx_, arena_bytes_);
+    if (!arena) fail("rfx_text_open");
+    struct Buf { char* p = nullptr; long ticket = -1; };
+    std::vector<Buf> ring(4);
+    for (Buf& b : ring) {
+      b.p = (char*)rfx_host_alloc(piece_);
+      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
+    }
+    auto settle_buf = [&](Buf& b) {
+      if (b.ticket >= 0 && rfx_text_wait(arena, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
+      b.ticket = -1;
+    };
+    std::vector<uint8_t> out;
+    std::vector<uint32_t> nbytes;
+    bool same = true;
+    size_t next_buf = 0;
+    for (const rfxbamcache::Batch& b : plan) {
+      // the batch's blocks, one behind the other (blocks that are not neighbours in the file are each self-contained)
+      size_t k = 0;
+      while (k < b.block.size()) {
+        Buf& buf = ring[next_buf];
+        next_buf = (next_buf + 1) % ring.size();
+        settle_buf(buf);
+        size_t used = 0;
+        for (; k < b.block.size(); ++k) {
+          const rfxbamcache::IndexEntry& e = cache.index[b.block[k]];
+          if (e.file_off + e.csize > size) die(std::string(TOOL) + ": --packed: the block index lies outside the file");  // (sizes agree: checked)
+          if (used + e.csize > piece_) break;
+          memcpy(buf.p + used, m + e.file_off, e.csize);
+          used += e.csize;
+        }
+        const long tk = rfx_text_append_bgzf(arena, buf.p, used);
+        if (tk == RFX_E_FORMAT) { same = false; break; }  // (not whole BGZF blocks where the index says blocks are)
+        if (tk < 0) die(std::string("rufus_amd: rfx_text_append_bgzf: ") + rfx_strerror((int)tk) + " " + rfx_last_error());
+        buf.ticket = tk;
+      }
+      blocks_ += b.block.size();
+      ++batches_;
+      uint64_t total = 0, got = 0;
+      nbytes.resize(b.n);
+      for (size_t i = 0; i < b.n; ++i) total += (nbytes[i] = sel[b.first + i].bytes);
+      out.resize((size_t)total + 8);
+      if (same) {
+        const int rc = rfx_bam_fetch(arena, b.arena_off.data(), nbytes.data(), b.n, out.data(), total, &got);
+        if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string(TOOL) + ": --packed: " + rfx_last_error());
+        if (rc == RFX_E_FORMAT) same = false;  // (an entry is no record: not the file the cache was made from)
+        else if (rc != RFX_OK || got != total) fail("rfx_bam_fetch");
+      }
+      uint64_t p = 0;
+      for (size_t i = 0; i < b.n && same; ++i) {
+        if (bam_next(out.data(), p, total) != p + nbytes[i] || bam_valid(out.data(), p, 0x7FFFFFFF) != BAM_OK ||
+            bam_name_hash(out.data(), p) != sel_hash[b.first + i]) {
+          same = false;
+          break;
+        }
+        tail_.add(out.data(), p, std::binary_search(hit_index_.begin(), hit_index_.end(), sel_index[b.first + i]));
+        p += nbytes[i];
+      }
+      for (Buf& x : ring) settle_buf(x);  // (an arena's tickets die with its reset)
+      rfx_text_reset(arena);
+      if (!same) break;
+    }
+    for (Buf& x : ring) rfx_host_free(x.p);
+    rfx_text_close(arena);
+    return same;
+  }
+  const std::string& mate1() const { return tail_.walk.o1; }
+  const std::string& mate2() const { return tail_.walk.o2; }
+  const std::vector<std::string>& chr_log() const { return chr_log_; }
+  std::string counts() const {
+    char b[320];
+    snprintf(b, sizeof b, "bam cache route: chunks %llu records %llu hits %llu names %llu selected %llu blocks %llu of %llu batches %llu pairs %llu",
+             (unsigned long long)chunks_, (unsigned long long)records_, (unsigned long long)hit_index_.size(), (unsigned long long)names_,
+             (unsigned long long)selected_, (unsigned long long)blocks_, (unsigned long long)index_blocks_, (unsigned long long)batches_,
              (unsigned long long)tail_.walk.n_found);
     return b;
   }

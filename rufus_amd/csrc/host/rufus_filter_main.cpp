@@ -28,6 +28,7 @@ using namespace rfxcli;
 
 #include "rfx_sam.hpp"
 #include "rfx_packed_cache.hpp"
+#include "rfx_bam_cache.hpp"
 #include "rfx_ingest.hpp"
 // ---- RUFUS.Filter HashList A.fastq.gz B.fastq.gz STUB K MinQ HashCountThreshold Threads --------------------------------
 // Both mate files bgzip'd (regular files whose first block rfx_bgzf_scan accepts): replaces runRufus.sh:974-977's
@@ -97,6 +98,9 @@ static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<u
 // order the pairs complete.  The same bytes as the two-process route; no FASTQ text exists for the other pairs.
 // A waiting record is a pointer into its piece (no copy); a piece is recycled LAG pieces later, and only the few
 // records that still wait then (mates far apart, unpaired reads) are copied out.
+namespace bamf {
+static int run_cached(int argc, char** argv);  // --packed with a BAM-kind cache (below)
+}
 namespace samf {
 using namespace rfxsam;
 
@@ -493,11 +497,20 @@ static int run(int argc, char** argv) {
 // (rfx_packed_cache.hpp): the subject's records were packed once, by `jellyfish count --sam ..
 // --keep-packed CACHE`.  Here they are uploaded as they lie in CACHE and scanned; only the lines of the names with a hit
 // are gathered from SPOOL (the stream's bytes: `--spool`, or the SAM file itself) and go through the text route above.
+// A CACHE that begins with rfx_bam_cache.hpp's magic is `jellyfish count --bam .. --keep-packed`'s: SPOOL is then the BAM
+// file itself and the route is bamf::run_cached.
 static int run_packed(int argc, char** argv) {
   printf("Call is --packed CACHE CHRFILE PreBuiltMutHash SPOOL firstpassfile hashsize MinQ HashCountThreshold threads\n");
   if (argc < 11) {
     printf("ERROR: expected 10 arguments\n");
     return 0;
+  }
+  {
+    uint64_t magic = 0;
+    const int cfd = ::open(argv[2], O_RDONLY);
+    const bool bam_kind = cfd >= 0 && ::pread(cfd, &magic, 8, 0) == 8 && magic == rfxbamcache::FILE_MAGIC;
+    if (cfd >= 0) ::close(cfd);
+    if (bam_kind) return bamf::run_cached(argc, argv);
   }
   const char *cache_path = argv[2], *chr_path = argv[3], *hashlist = argv[4], *spool = argv[5];
   const int k = atoi(argv[7]), min_q = atoi(argv[8]), thresh = atoi(argv[9]);
@@ -749,6 +762,107 @@ static int run(int argc, char** argv) {
   rfx_set_free(set);
   rfx_close(ctx);
   return 0;
+}
+
+// `RUFUS.Filter --packed CACHE CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads` with the
+// BAM-kind cache `jellyfish count --bam CHR --keep-packed CACHE X.bam` left (rfx_bam_cache.hpp): what `--bam` writes, byte
+// for byte, without a pass over the file -- the cache is scanned, and only the BGZF blocks that hold the hit names' records
+// are read and inflated (rfx_ingest.hpp BamCachePull).  Replaces the two inflates of runRufus.sh:964-967's generator that
+// `--bam` still does.  A cache that read_cache refuses, one made for another MinQ or other exclude flags than `--bam`'s
+// 3328, an X.bam that is not a regular BGZF file of the recorded size, or a fetched record that is not the record the cache
+// describes: one line on stderr and the two-pass `--bam` route in this process, with the same arguments.  One device.
+static int run_cached(int argc, char** argv) {
+  const char *cache_path = argv[2], *chr_path = argv[3], *hashlist = argv[4], *bam = argv[5];
+  const std::string stub = argv[6];
+  const int k = atoi(argv[7]), min_q = atoi(argv[8]), thresh = atoi(argv[9]);
+  const std::vector<int> gpus = gpu_list();
+  if (gpus.size() != 1)
+    die("rufus_amd RUFUS.Filter: --packed with a BAM's cache scans and fetches on the device, which needs one device (RUFUS_GPUS "
+        "names more)");
+  auto two_pass = [&]() {
+    fprintf(stderr, "rufus_amd RUFUS.Filter: %s is not a usable packed-read cache of %s for MinQ %d: reading the BAM twice\n", cache_path,
+            bam, min_q);
+    std::vector<std::string> a{argv[0], "--bam", chr_path, hashlist, bam, argv[6], argv[7], argv[8], argv[9], argv[10]};
+    std::vector<char*> av;
+    for (std::string& x : a) av.push_back(&x[0]);
+    return run((int)av.size(), av.data());
+  };
+  // the cache, mapped and checked
+  rfxbamcache::Cache cache;
+  {
+    const int fd = ::open(cache_path, O_RDONLY);
+    struct stat sb;
+    void* m = MAP_FAILED;
+    if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (fd >= 0) ::close(fd);
+    if (m == MAP_FAILED || !rfxbamcache::read_cache((const char*)m, (size_t)sb.st_size, cache) || cache.h.min_q != min_q ||
+        cache.h.exclude_flags != 3328u)
+      return two_pass();
+  }
+  struct stat bs;
+  if (stat(bam, &bs) != 0 || !S_ISREG(bs.st_mode) || (uint64_t)bs.st_size != cache.h.bam_bytes) return two_pass();
+  std::string text;
+  {
+    std::ifstream f(hashlist, std::ios::binary);
+    if (!f.is_open()) {
+      printf("Error, ParentHashFile could not be opened");
+      return 0;
+    }
+    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+  }
+  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
+  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, 0, nullptr, 0);
+  if (nk < 0) die("rufus_amd: cannot parse the hash list");
+  std::vector<uint64_t> keys((size_t)nk + 1);
+  rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
+  printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
+  size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
+  if (const char* ev = getenv("RFX_BAM_ARENA")) arena = (size_t)std::max(1ll << 20, atoll(ev));
+  if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+  rfx_ctx* ctx = open_ctxs(gpus)[0];
+  rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
+  if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
+  trace("filter --packed: device open, set built");
+  bool same = true;
+  {
+    // (the fetch arena is a quarter of RFX_BAM_ARENA, the size of BamIngest's runs: it holds the few blocks of the selection,
+    // not a stretch of the file)
+    BamCachePull route(ctx, set, thresh, arena / 4, piece);
+    route.scan(cache);
+    trace("filter --packed: cache scanned");
+    if (route.hits()) {  // (no hit: the BAM is not opened)
+      const int fd = ::open(bam, O_RDONLY);
+      struct stat sb;
+      void* m = MAP_FAILED;
+      same = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && (uint64_t)sb.st_size == cache.h.bam_bytes &&
+             is_bgzf(fd, true, (uint64_t)sb.st_size);
+      if (same) m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (fd >= 0) ::close(fd);
+      same = same && m != MAP_FAILED && route.pull(cache, (const char*)m, (size_t)sb.st_size);
+      if (m != MAP_FAILED) munmap(m, (size_t)sb.st_size);
+    }
+    if (same) {
+      FILE* chr = fopen(chr_path, "w");
+      std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
+      std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
+      if (!chr || !out1.is_open() || !out2.is_open()) {
+        printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
+        return 0;
+      }
+      for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
+      fclose(chr);
+      out1.write(route.mate1().data(), (std::streamsize)route.mate1().size());
+      out2.write(route.mate2().data(), (std::streamsize)route.mate2().size());
+      out1.close();
+      out2.close();
+      trace(route.counts().c_str());
+      printf("\nDone running RUFUS.Filter.cpp\n");
+      leave(0);  // (outputs closed: see the text route's end)
+    }
+  }
+  rfx_set_free(set);
+  rfx_close(ctx);
+  return same ? 0 : two_pass();  // (a fetched record was not the cache's: nothing has been written)
 }
 }  // namespace bamf
 #endif

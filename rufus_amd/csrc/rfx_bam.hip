@@ -665,6 +665,70 @@ __global__ __launch_bounds__(256) void k_bamg_table(const uint8_t* __restrict__ 
   }
 }
 
+// a kept record's address: where its block_size field lies in the arena, and the bytes from there to its end
+__global__ __launch_bounds__(256) void k_bam_locate(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at, uint64_t n_kept,
+                                                     uint32_t* __restrict__ start_out, uint32_t* __restrict__ bytes_out) {
+  for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n_kept; o += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t p = kept_at[o];
+    start_out[o] = p;
+    bytes_out[o] = record_bytes(b, p);
+  }
+}
+
+// Entry i of a fetch list names a record when it holds the fixed fields, lies inside the arena's `used` bytes and begins
+// with its own length (read bytewise: any residue).  *first_bad = the lowest i that does not; sizes[i] = bytes[i] for the scan.
+__global__ __launch_bounds__(256) void k_fetch_check(const uint8_t* __restrict__ b, uint64_t used, const uint32_t* __restrict__ start,
+                                                      const uint32_t* __restrict__ bytes, uint64_t n, uint32_t* __restrict__ first_bad,
+                                                      uint64_t* __restrict__ sizes) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t s = start[i], nb = bytes[i];
+    sizes[i] = nb;
+    bool ok = nb >= BAM_FIXED && (uint64_t)s + nb <= used;
+    if (ok) ok = bam_block_size(b, s) == nb - 4u;  // (s + 4 <= s + nb <= used)
+    if (!ok) atomicMin(first_bad, (uint32_t)i);
+  }
+}
+
+// off: the scanned sizes from the run's first entry on (n + 1 of them); destinations count from the run's first byte
+__global__ __launch_bounds__(256) void k_fetch_table(const uint32_t* __restrict__ start, const uint64_t* __restrict__ off, uint32_t n,
+                                                      uint32_t* __restrict__ src_off, uint32_t* __restrict__ dst_off) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    src_off[i] = start[i];
+    dst_off[i] = (uint32_t)(off[i] - off[0]);  // (a run is at most 1 GiB, or one record of an arena below 4 GiB)
+    if (i == n - 1u) dst_off[n] = (uint32_t)(off[n] - off[0]);
+  }
+}
+
+// k_bam_mark's shape over an array of hashes: wave w of the grid takes mask words w, w + waves, ...; a piece holds fewer
+// than 2^32 hashes, so its set bits are counted with a 32-bit atomic
+__global__ __launch_bounds__(256) void k_nameset_mark(const uint64_t* __restrict__ hashes, uint64_t n, const uint64_t* __restrict__ table,
+                                                       uint64_t slots, int has_zero, uint64_t* __restrict__ mask_out,
+                                                       uint32_t* __restrict__ n_marked) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6), nw = (n + 63) / 64;
+  for (uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < nw; w += waves) {  // (wave-uniform)
+    const uint64_t o = w * 64 + lane;
+    bool in = false;
+    if (o < n) {
+      const uint64_t h = hashes[o];
+      if (h == 0) {
+        in = has_zero != 0;
+      } else {
+        for (uint64_t s = nameset_slot(h, slots);; s = (s + 1) & (slots - 1ull)) {  // (ends: the table is at most half full)
+          const uint64_t key = table[s];
+          if (key == h) in = true;
+          if (key == h || key == 0) break;
+        }
+      }
+    }
+    const unsigned long long vote = __ballot(in);
+    if (lane == 0) {
+      mask_out[w] = vote;
+      if (vote) atomicAdd(n_marked, (uint32_t)__popcll(vote));
+    }
+  }
+}
+
 // What the three pull calls begin with: the arena settled and ready, kept_at[o] = the offset of kept record o (device,
 // dmalloc: the caller frees it; nullptr for 0 kept records), *n_kept.  One wait.
 struct kept_view {
@@ -1060,6 +1124,183 @@ int rfx_bam_gather(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, ui
   if (e == hipSuccess) e = hipMemcpyAsync(host_out, out, (size_t)n_bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = rfxi::sync(c);
   if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  return done(RFX_OK, hipSuccess, "");
+}
+
+
+// ---- a record's address, and records fetched by address (count --bam --keep-packed, RUFUS.Filter --packed) ---------------
+// Replaces the second and third inflate of the subject's BAM (scripts/RunJellyForRUFUS.sh:28-29, then the two passes of
+// runRufus.sh:964-967): the count notes where every kept record lies, the filter asks for the hit names' records alone.
+//
+//   k_bam_locate     a thread per kept record (kept_of's rank): its arena offset and 4 + block_size
+//   k_fetch_check    a thread per list entry: the three checks, the lowest failing index (atomicMin), bytes[] widened -> a scan
+//   k_fetch_table    a thread per entry of a run: source offset, destination offset inside the run   -> k_gather_copy
+//   k_nameset_mark   k_bam_mark with the hash taken from an array: a lane per hash, the ballot = the mask word
+int rfx_bam_locate(rfx_text* t, uint32_t exclude_flags, uint64_t n_kept, uint32_t* start_out, uint32_t* bytes_out) {
+  static const char* const who = "rfx_bam_locate";
+  if (!t || (n_kept && (!start_out || !bytes_out))) return RFX_E_INVAL;
+  kept_view v;
+  if (const int rc = kept_of(t, exclude_flags, who, &v)) return rc;
+  rfx_ctx* c = v.c;
+  if (v.n_kept != n_kept) {
+    dfree(c, v.kept_at);
+    return pull_fail(c, who, RFX_E_INVAL, hipSuccess, "n_kept is not the number of kept records of the arena");
+  }
+  if (n_kept == 0) return RFX_OK;
+  uint32_t* d_out = (uint32_t*)dmalloc(c, (size_t)n_kept * 8);  // the starts, then the sizes
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);
+    dfree(c, v.kept_at); dfree(c, d_out);
+    return rc;
+  };
+  if (!d_out) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  {
+    rfx_span sp(c, "k_bam_locate");
+    const dim3 grid((unsigned)std::min<uint64_t>((n_kept + 255) / 256, (uint64_t)c->n_cu * 16));
+    hipLaunchKernelGGL(k_bam_locate, grid, dim3(256), 0, c->stream, v.arena, (const uint32_t*)v.kept_at, n_kept, d_out, d_out + n_kept);
+  }
+  hipError_t e = hipMemcpyAsync(start_out, d_out, (size_t)n_kept * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(bytes_out, d_out + n_kept, (size_t)n_kept * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  return done(RFX_OK, hipSuccess, "");
+}
+
+int rfx_bam_fetch(rfx_text* t, const uint32_t* start, const uint32_t* bytes, uint64_t n, void* host_out, uint64_t cap,
+                  uint64_t* out_bytes) {
+  static const char* const who = "rfx_bam_fetch";
+  if (out_bytes) *out_bytes = 0;
+  if (!t || !out_bytes || (n && (!start || !bytes)) || (cap && !host_out)) return RFX_E_INVAL;
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t used = 0;
+  if (const int rc = rfxi::text_ready(t, &c, &arena, &used)) return rc;  // waits for the appends; a block that did not inflate
+  if (n == 0) return RFX_OK;
+  if (n >= BAM_NONE) return pull_fail(c, who, RFX_E_RANGE, hipSuccess, "2^32 - 1 entries or more");
+  uint32_t* d_list = (uint32_t*)dmalloc(c, (size_t)n * 8 + 4);  // start, bytes, the lowest failing index
+  uint64_t* sizes = (uint64_t*)dmalloc(c, ((size_t)n + 1) * 8);
+  uint32_t *src_off = nullptr, *dst_off = nullptr, *out = nullptr;
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);
+    dfree(c, d_list); dfree(c, sizes); dfree(c, src_off); dfree(c, dst_off); dfree(c, out);
+    return rc;
+  };
+  if (!d_list || !sizes) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  uint32_t *d_start = d_list, *d_bytes = d_list + n, *d_bad = d_list + 2 * n;
+  const dim3 per_entry((unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->n_cu * 16));
+  // (pageable host memory: the runtime has copied it out of the lists when the call returns)
+  hipError_t e = hipMemcpyAsync(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_bytes, bytes, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0xFF, 4, c->stream);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  {
+    rfx_span sp(c, "k_fetch_check");
+    hipLaunchKernelGGL(k_fetch_check, per_entry, dim3(256), 0, c->stream, arena, used, (const uint32_t*)d_start,
+                       (const uint32_t*)d_bytes, n, d_bad, sizes);
+  }
+  rfxk::scan_tail(c, sizes, n);
+  uint32_t bad = BAM_NONE;
+  uint64_t total = 0;
+  e = queue_read(c, &bad, d_bad, 4);
+  if (e == hipSuccess) e = queue_read(c, &total, sizes + n, 8);
+  if (e == hipSuccess) e = rfxi::sync(c);  // the one wait between the lists and the copy: the verdict and the size
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  if (bad != BAM_NONE) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "entry %u (start %u, bytes %u) is not a record inside the arena's %llu bytes", bad, start[bad], bytes[bad],
+             (unsigned long long)used);
+    return done(RFX_E_FORMAT, hipSuccess, msg);
+  }
+  *out_bytes = total;
+  if (total > cap) return done(RFX_E_RANGE, hipSuccess, "the output buffer is too small");
+  // Runs of the list, each one k_gather_copy: a run ends in front of an entry that starts in the arena's first four bytes
+  // (the kernel reads the dword a record shares with its predecessor from `have` bytes in front of the record: a record
+  // that follows another must not lie there) and where it would pass 1 GiB (the kernel's offsets are 32 bits).  A list the
+  // tool makes -- ascending, out of blocks that begin with other bytes -- is one run.
+  constexpr uint64_t RUN_MAX = 1ull << 30;
+  std::vector<uint64_t> run_first, run_at;  // the run's first entry, its first byte in the result
+  uint64_t at = 0, run_bytes = 0, longest = 0, most = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (i == 0 || start[i] < 4u || run_bytes + bytes[i] > RUN_MAX) {
+      run_first.push_back(i);
+      run_at.push_back(at);
+      run_bytes = 0;
+    }
+    run_bytes += bytes[i];
+    at += bytes[i];
+    longest = std::max(longest, run_bytes);
+    most = std::max(most, i + 1 - run_first.back());
+  }
+  if (at != total) return done(RFX_E_HIP, hipSuccess, "the device's total differs from the host's");  // (cannot be)
+  src_off = (uint32_t*)dmalloc(c, (size_t)most * 4);
+  dst_off = (uint32_t*)dmalloc(c, ((size_t)most + 1) * 4);
+  out = (uint32_t*)dmalloc(c, ((size_t)longest + 3) / 4 * 4);
+  if (!src_off || !dst_off || !out) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  run_first.push_back(n);
+  run_at.push_back(total);
+  for (size_t r = 0; r + 1 < run_first.size(); ++r) {  // (the buffers are reused in stream order)
+    const uint64_t first = run_first[r], m = run_first[r + 1] - first, nb = run_at[r + 1] - run_at[r];
+    {
+      rfx_span sp(c, "k_fetch_table");
+      const dim3 grid((unsigned)std::min<uint64_t>((m + 255) / 256, (uint64_t)c->n_cu * 16));
+      hipLaunchKernelGGL(k_fetch_table, grid, dim3(256), 0, c->stream, (const uint32_t*)d_start + first, (const uint64_t*)sizes + first,
+                         (uint32_t)m, src_off, dst_off);
+    }
+    // (every source dword lies inside the arena or in the 8 KiB behind its capacity: k_gather_copy reads at most 7 bytes
+    // behind a record's last byte, and the check has put every record in front of the arena's end)
+    rfxi::gather_copy(c, arena, src_off, dst_off, (uint32_t)m, (uint32_t)nb, out);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)host_out + run_at[r], out, (size_t)nb, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  }
+  e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  return done(RFX_OK, hipSuccess, "");
+}
+
+int rfx_nameset_mark(const rfx_nameset* set, const uint64_t* hashes, uint64_t n, uint64_t* mask_out, uint64_t* n_marked) {
+  static const char* const who = "rfx_nameset_mark";
+  if (n_marked) *n_marked = 0;
+  if (!set || (n && (!hashes || !mask_out))) return RFX_E_INVAL;
+  if (n == 0) return RFX_OK;
+  rfx_ctx* c = set->ctx;
+  (void)hipSetDevice(c->device);
+  uint64_t piece = 1ull << 22;  // hashes per upload: 32 MiB, whatever n is (RFX_NAMESET_PIECE: a test knob, changes no result)
+  if (const char* env = getenv("RFX_NAMESET_PIECE")) {
+    const long long want = atoll(env);
+    if (want >= 64 && want <= (1ll << 26)) piece = (uint64_t)want & ~63ull;
+  }
+  piece = std::min<uint64_t>(piece, (n + 63) & ~63ull);
+  const uint64_t n_pieces = (n + piece - 1) / piece;
+  uint64_t* d_hash = (uint64_t*)dmalloc(c, (size_t)piece * 8);
+  uint64_t* d_mask = (uint64_t*)dmalloc(c, (size_t)piece / 8);
+  uint32_t* d_cnt = (uint32_t*)dmalloc(c, (size_t)n_pieces * 4);  // a piece's set bits: below 2^32, a 32-bit atomic each
+  std::vector<uint32_t> cnt((size_t)n_pieces, 0);
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);
+    dfree(c, d_hash); dfree(c, d_mask); dfree(c, d_cnt);
+    return rc;
+  };
+  if (!d_hash || !d_mask || !d_cnt) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  hipError_t e = hipMemsetAsync(d_cnt, 0, (size_t)n_pieces * 4, c->stream);
+  for (uint64_t p = 0; p < n_pieces && e == hipSuccess; ++p) {  // (the two buffers are reused in stream order)
+    const uint64_t first = p * piece, m = std::min(piece, n - first), nw = (m + 63) / 64;
+    e = hipMemcpyAsync(d_hash, hashes + first, (size_t)m * 8, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) break;
+    {
+      rfx_span sp(c, "k_nameset_mark");
+      const dim3 grid((unsigned)std::min<uint64_t>((nw + 3) / 4, (uint64_t)c->n_cu * 16));
+      hipLaunchKernelGGL(k_nameset_mark, grid, dim3(256), 0, c->stream, (const uint64_t*)d_hash, m, (const uint64_t*)set->table,
+                         set->slots, set->has_zero, d_mask, d_cnt + p);
+    }
+    e = hipMemcpyAsync(mask_out + first / 64, d_mask, (size_t)nw * 8, hipMemcpyDeviceToHost, c->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  uint64_t marked = 0;
+  for (const uint32_t x : cnt) marked += x;
+  if (n_marked) *n_marked = marked;
   return done(RFX_OK, hipSuccess, "");
 }
 
