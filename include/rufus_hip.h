@@ -510,6 +510,11 @@ uint64_t rfx_runmaps_bytes(const rfx_runmaps*);
 int rfx_runmaps_blocks(const rfx_runmaps*);
 int rfx_runmaps_drop(rfx_runmaps*, const rfx_reads*);
 int rfx_runmaps_clear(rfx_runmaps*); /* every map of the store */
+/* A block's map as it lies in the store, for tests and tools: 32 bytes per read of `reads` to out_bytes (host memory,
+ * 32 * the block's reads) and the indices of the reads that went without a map (count 31: more than 27 entries), in no
+ * particular order, to out_ovf[0, cap).  Returns their number (>= 0); RFX_E_INVAL when the store holds no map of the
+ * block, RFX_E_RANGE (the 32-byte rows are written) when there are more of them than cap.  Waits for the device. */
+int rfx_runmaps_read(rfx_runmaps*, const rfx_reads* reads, void* out_bytes, uint32_t* out_ovf, uint32_t cap);
 int rfx_count_set_runmaps(rfx_table*, rfx_runmaps*);
 /* the maps of several blocks the table is about to add, made with ONE wait for the device (a map made by rfx_count_add
  * waits for its own launch); blocks that have a map, or are no blocks for one, are skipped; no store: nothing happens */

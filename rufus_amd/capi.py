@@ -142,6 +142,7 @@ SIGNATURES = {
     "rfx_runmaps_blocks": (C.c_int, [C.c_void_p]),
     "rfx_runmaps_drop": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rfx_runmaps_clear": (C.c_int, [C.c_void_p]),
+    "rfx_runmaps_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
     "rfx_count_set_runmaps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rfx_count_prepare_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "rfx_count_prefetch_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
@@ -878,6 +879,15 @@ class RunMaps:
 
     def clear(self):
         _check(lib().rfx_runmaps_clear(self._h), "rfx_runmaps_clear")
+
+    def read(self, reads: "ReadBlock"):
+        """(map, overflow): the block's map as a uint8 array of shape (reads, 32) and the sorted indices of the reads that
+        went without one (``rfx_runmaps_read``)."""
+        rows = np.zeros((max(reads.n, 1), 32), np.uint8)
+        ovf = np.zeros(max(reads.n, 1), np.uint32)
+        n = lib().rfx_runmaps_read(self._h, reads._h, rows.ctypes.data, _p(ovf, u32p), len(ovf))
+        _check(min(n, 0), "rfx_runmaps_read")
+        return rows[:reads.n], np.sort(ovf[:n])
 
     def free(self):
         if self._h:

@@ -3606,6 +3606,23 @@ int rfx_runmaps_drop(rfx_runmaps* s, const rfx_reads* r) {
   return RFX_OK;
 }
 
+int rfx_runmaps_read(rfx_runmaps* s, const rfx_reads* r, void* out_bytes, uint32_t* out_ovf, uint32_t cap) {
+  if (!s || !r || !out_bytes) return RFX_E_INVAL;
+  (void)hipSetDevice(s->ctx->device);
+  if (r->twin) return rfx_runmaps_read(s, r->twin, out_bytes, out_ovf, cap);  // (long sequences: the tiled twin's map)
+  const int rc = runmaps_collect(s);
+  if (rc) return rc;
+  auto it = s->m.find(r);
+  if (it == s->m.end() || !it->second.map || it->second.n_reads != r->n || it->second.gen != r->gen) return RFX_E_INVAL;
+  const rfx_runmap_entry& en = it->second;
+  if (ctx_sync(s->ctx) != hipSuccess) return RFX_E_HIP;
+  if (hipMemcpy(out_bytes, en.map, (size_t)en.n_reads * 32, hipMemcpyDeviceToHost) != hipSuccess) return RFX_E_HIP;
+  if (en.n_ovf > cap) return RFX_E_RANGE;
+  if (en.n_ovf && (!out_ovf || hipMemcpy(out_ovf, en.ovf + 1, (size_t)en.n_ovf * 4, hipMemcpyDeviceToHost) != hipSuccess))
+    return out_ovf ? RFX_E_HIP : RFX_E_INVAL;
+  return (int)en.n_ovf;
+}
+
 int rfx_runmaps_clear(rfx_runmaps* s) {
   if (!s) return RFX_E_INVAL;
   (void)hipSetDevice(s->ctx->device);
@@ -3614,7 +3631,7 @@ int rfx_runmaps_clear(rfx_runmaps* s) {
   return RFX_OK;
 }
 
-// Run maps made AHEAD (round 6).  The hashing launch over a block (k_msp_map: 95 ms per W sample, bound by the
+// Run maps made AHEAD (round 6).  The hashing launch over a block (k_msp_map: 80 ms per W sample, bound by the
 // instructions it issues, 54 KB of LDS per CU) and the partition levels of ANOTHER sample's count (bound by the memory,
 // one 96 KB workgroup per CU) want different things of a CU and fit it side by side: the maps of the sample that is
 // counted NEXT are queued on the ctx's second stream while this sample's records are partitioned, refined and sorted on

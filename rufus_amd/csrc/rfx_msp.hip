@@ -108,6 +108,9 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_part1(rfx_reads_view rv, int 
   // (HMODE 4: the lane's 32 map bytes are staged here, stride 9 dwords: no two lanes of a wave on a bank)
   __shared__ uint32_t s_fine[HMODE == 0 ? 4096 : HMODE == 1 ? 8192 : HMODE == 3 ? 16384 : HMODE == 4 ? MP1_BLOCK * 9 : 1];
   uint8_t* const mapb = MAPONLY ? (uint8_t*)(s_fine + threadIdx.x * 9u) : nullptr;
+  // (HMODE 4: six bits of the minimizer's hash per run end, a byte per base, for the four phases of a batch; same stride)
+  __shared__ uint32_t s_mapq[MAPONLY ? MP1_BLOCK * 9 : 1];
+  uint32_t* const mapq = MAPONLY ? s_mapq + threadIdx.x * 9u : nullptr;
   __shared__ uint32_t s_maxlen;
   // SLABS (round 4): CLOSE QUEUE.  With whole super-k-mers one lane in six closes a run at any base, so the ~60
   // instructions that turn a closed run into a record (word + plane, bin, slab slot, two stores, fine histogram) ran at
@@ -207,7 +210,8 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_part1(rfx_reads_view rv, int 
     const uint64_t* cw = rv.codes + roff;
     const uint32_t* cm = live ? rv_acgt(rv, r, roff) : nullptr;  // nullptr: all of the read is A/C/G/T (compact blocks)
     // HMODE 4: entries so far, the k-mer end position the next entry begins at, the entries' shard-half flags
-    uint32_t mcnt = 0, mpos = (uint32_t)k - 1u, mflags = 0;
+    // (and the run ends / starts of up to four phases, bit 8 * (ph & 3) + b, until their batch is walked)
+    uint32_t mcnt = 0, mpos = (uint32_t)k - 1u, mflags = 0, ends32 = 0, starts32 = 0, run_c = 0;
     if (threadIdx.x == 0) s_maxlen = 0;
     __syncthreads();
     atomicMax(&s_maxlen, lenp);
@@ -325,7 +329,8 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_part1(rfx_reads_view rv, int 
         uint32_t ends = KV & ~cont & 0xFFu, starts = kvmask & ~cont;
         if (nmax < WL) {  // k >= 26: a record holds fewer k-mers than a window has m-mers -- the run is cut at the cap
           // (at most once per phase: nmax > 8; and only if the run in progress did not begin in this phase)
-          const uint32_t cb = run_s + (uint32_t)nmax - p0;  // (wraps to a big number when the cap lies behind)
+          // (HMODE 4 keeps `run_s` as it was before the batch of four phases: `run_c` follows the phases there)
+          const uint32_t cb = (MAPONLY ? run_c : run_s) + (uint32_t)nmax - p0;  // (wraps to a big number when the cap lies behind)
           if (cb < 8u && ((cont >> cb) & 1u) && (starts & ((2u << cb) - 1u)) == 0) {
             ends |= 1u << cb;
             starts |= 1u << cb;
@@ -336,43 +341,63 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_part1(rfx_reads_view rv, int 
         // turn needs of the minimizer (its position mod 32, for `back`; its bin, for "is this run the table's") is laid
         // out per phase: five bits per base in `qpack`, one in `minemask`.
         if constexpr (MAPONLY) {
-          // every run that ends in this phase becomes an entry of the map: a lane walks the set bits of its `ends`.  Per
-          // run end six bits of the minimizer's hash are laid out ahead: its position (mod 32) and MSP_HALF_BIT, the
-          // half of the bin space the run's bin lies in (bases 0 .. 4 in one word, 5 .. 7 in another: 32-bit shifts).
-          uint32_t qa = prev_mh & 63u, qb = 0;
-  #pragma unroll
-          for (int b = 1; b < 5; ++b) qa |= (mhv[b - 1] & 63u) << (6 * b);
-  #pragma unroll
-          for (int b = 5; b < P1_S; ++b) qb |= (mhv[b - 1] & 63u) << (6 * (b - 5));
-          uint32_t pend = ends;
-          while (__ballot(pend != 0)) {
-            if (pend) {
-              const uint32_t b = (uint32_t)__ffs((int)pend) - 1u;
-              pend &= pend - 1u;
-              const uint32_t ms = starts & ((1u << b) - 1u);
-              const uint32_t rs = ms ? p0 + 31u - (uint32_t)__clz((int)ms) : run_s;
-              const uint32_t e = p0 + b - 1u;
-              const uint32_t q6 = b < 5u ? qa >> (6u * b) : qb >> (6u * b - 30u);
-              const uint32_t back = (e - q6) & 31u;
-              // entry: low nibble n - 1 (15: a gap), high nibble `back` (a gap: its length - 1).  K-mer end positions no run
-              // covers (invalid bases) are gaps.  A run longer than a record holds (k >= 26) goes in pieces, as the records do.
-              // (Entries beyond the map's 27 land on bytes that the flags overwrite: no test on the way.)
-              if (rs != mpos) {
-                for (uint32_t g = rs - mpos; g != 0;) {
-                  const uint32_t l = min(g, 16u);
-                  mapb[min(mcnt, 31u)] = (uint8_t)(0xFu | ((l - 1u) << 4));
-                  ++mcnt;
-                  g -= l;
-                }
-              }
-              const uint32_t at = min(mcnt, 31u);
-              mapb[at] = (uint8_t)((e - rs) | (back << 4));
-              mflags |= ((q6 >> 5) & 1u) << at;
-              ++mcnt;
-              mpos = e + 1u;
-            }
+          // every run that ends becomes an entry of the map: a lane walks the set bits of its `ends`.  Per run end six
+          // bits of the minimizer's hash are laid out ahead: its position (mod 32) and MSP_HALF_BIT, the half of the bin
+          // space the run's bin lies in (a byte per base, the low bytes of the hashes put together with v_perm; bits 6
+          // and 7 are never looked at).  The walk itself waits for FOUR phases: the wave makes as many turns as its busiest
+          // lane has run ends, and over 32 bases the busiest lane is much nearer the mean than over 8 (61 turns per
+          // 150-base read phase by phase, 37 in batches of four).  Until then a phase shifts its `ends` and `starts` into
+          // 32-bit masks and leaves its eight bytes in LDS.  (The loop's form matters: as `while (ballot) { if (pend) .. }`
+          // with the gap loop under a lane's own test it compiled to 36 VALU instructions per turn, 12 of them copies of
+          // mcnt / mflags / mpos / pend; as written here, 26.)
+          const uint32_t pq = ph & 3u;
+          {
+            constexpr uint32_t LO2 = 0x0C0C0400u, LOHI = 0x05040100u;  // v_perm: byte 0 of either; the low halves of both
+            const uint32_t t0 = __builtin_amdgcn_perm(mhv[0], prev_mh, LO2), t1 = __builtin_amdgcn_perm(mhv[2], mhv[1], LO2);
+            const uint32_t t2 = __builtin_amdgcn_perm(mhv[4], mhv[3], LO2), t3 = __builtin_amdgcn_perm(mhv[6], mhv[5], LO2);
+            static_assert(P1_S == 8, "eight bytes per phase");
+            mapq[2u * pq] = __builtin_amdgcn_perm(t1, t0, LOHI);
+            mapq[2u * pq + 1u] = __builtin_amdgcn_perm(t3, t2, LOHI);
           }
-          if (starts) run_s = p0 + 31u - (uint32_t)__clz((int)starts);
+          ends32 |= ends << (8u * pq);
+          starts32 |= starts << (8u * pq);
+          if (nmax < WL && starts) run_c = p0 + 31u - (uint32_t)__clz((int)starts);  // (only the cap above looks at it)
+          if (pq == 3u || ph + 1u == n_phase) {  // (uniform; the last batch of a read may be short)
+            const uint32_t P0 = p0 - 8u * pq;  // the batch's first base
+            uint32_t pend = ends32;
+            if (__ballot(pend != 0)) do {
+              if (pend) {
+                const uint32_t b = (uint32_t)__ffs((int)pend) - 1u;  // 0 .. 31
+                pend &= pend - 1u;
+                const uint32_t ms = __builtin_amdgcn_ubfe(starts32, 0u, b);  // the starts before b
+                const uint32_t rs = ms ? P0 + 31u - (uint32_t)__clz((int)ms) : run_s;
+                const uint32_t e = P0 + b - 1u;
+                const uint32_t q6 = ((const uint8_t*)mapq)[b];
+                const uint32_t back = (e - q6) & 31u;
+                // entry: low nibble n - 1 (15: a gap), high nibble `back` (a gap: its length - 1).  K-mer end positions no run
+                // covers (invalid bases) are gaps.  A run longer than a record holds (k >= 26) goes in pieces, as the records do.
+                // (Entries beyond the map's 27 land on bytes that the flags overwrite: no test on the way.)
+                // Gaps are rare (invalid bases only): their loop sits behind a test the whole wave makes.
+                const uint32_t g0 = rs - mpos;
+                if (__ballot(g0 != 0)) {
+                  for (uint32_t g = g0; g != 0;) {
+                    const uint32_t l = min(g, 16u);
+                    mapb[min(mcnt, 31u)] = (uint8_t)(0xFu | ((l - 1u) << 4));
+                    ++mcnt;
+                    g -= l;
+                  }
+                }
+                const uint32_t at = min(mcnt, 31u);
+                mapb[at] = (uint8_t)((e - rs) | (back << 4));
+                mflags |= __builtin_amdgcn_ubfe(q6, 5u, 1u) << at;
+                ++mcnt;
+                mpos = e + 1u;
+              }
+            } while (__ballot(pend != 0));
+            if (starts32) run_s = P0 + 31u - (uint32_t)__clz((int)starts32);
+            run_c = run_s;
+            ends32 = starts32 = 0;
+          }
         } else if constexpr (SLABS) {
           uint64_t qpack = prev_mh & 31u;  // 5 bits per run end: position (mod 32) of the minimizer of the run ending at p0 + b - 1
   #pragma unroll
@@ -2192,7 +2217,7 @@ void msp_part1(rfx_ctx* c, const rfx_reads_view& rv, int k, int canonical, int b
 #undef RFX_MSP_P1
 }
 
-int msp_map_grid(rfx_ctx* c, uint32_t n_reads) {  // (k_msp_part1 HMODE 4: 69 VGPRs, 18 KB of LDS: three workgroups per CU)
+int msp_map_grid(rfx_ctx* c, uint32_t n_reads) {  // (k_msp_part1 HMODE 4: 74 VGPRs, 36 KB of LDS: three workgroups per CU)
   const uint32_t chunks = (n_reads + MP1_BLOCK - 1) / MP1_BLOCK;
   return (int)std::max<uint32_t>(8, std::min<uint32_t>((uint32_t)c->n_cu * 3, (chunks + 7) & ~7u));
 }
