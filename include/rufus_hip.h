@@ -698,6 +698,11 @@ rfx_candidates* rfx_binned_strike(rfx_ctx*, rfx_binned* subject, const rfx_binne
  * sides), out[1] = how many of them went through the workgroup-per-unit kernel -- the units beyond the capacities of the
  * wave-per-unit kernel that takes the plain ones, or all of them under RFX_STRIKE_WG=1.  For tests and measurements. */
 int rfx_binned_strike_stats(const rfx_ctx*, uint64_t out[2]);
+/* The kernel the context's last minimizer-bin count launch (k_msp_leaf) took: out[0] = the k it was compiled for, 0 for
+ * the kernel that takes k as an argument, -1 when the context has launched none; out[1] = 1 when it was the single-segment
+ * form.  k = 25 and 31 with one segment take the compiled ones unless RFX_LEAF_GENERIC or RFX_LEAF_FORCE_MIXED is set.
+ * Host-side bookkeeping, for tests and measurements. */
+int rfx_leaf_variant(const rfx_ctx*, int out[2]);
 /* rfx_records_subtract(candidates, {control}, 0, ~0) for every further control: its keys are struck off the list */
 int rfx_candidates_strike(rfx_candidates*, const rfx_binned* control);
 /* entries of the list (struck ones included); _get: all of them, a struck one as ~0 -- canonical keys, no order */

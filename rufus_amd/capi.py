@@ -63,6 +63,7 @@ SIGNATURES = {
     "rfx_binned_free": (None, [C.c_void_p]),
     "rfx_binned_strike": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rfx_binned_strike_stats": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_leaf_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rfx_candidates_strike": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rfx_candidates_size": (C.c_uint64, [C.c_void_p]),
     "rfx_candidates_get": (C.c_int, [C.c_void_p, u64p]),
@@ -1204,6 +1205,14 @@ def binned_strike_stats(ctx: Context) -> dict:
     o = np.zeros(2, dtype=np.uint64)
     _check(lib().rfx_binned_strike_stats(ctx._h, _p(o, u64p)), "rfx_binned_strike_stats")
     return {"units": int(o[0]), "deferred": int(o[1])}
+
+
+def leaf_variant(ctx: Context) -> dict:
+    """The k_msp_leaf the context's last minimizer-bin count launched: "kc" the k it was compiled for (0: the kernel with k
+    as an argument, -1: no launch yet), "one" whether it was the single-segment form -- rfx_leaf_variant."""
+    o = np.zeros(2, dtype=np.int32)
+    _check(lib().rfx_leaf_variant(ctx._h, o.ctypes.data_as(C.POINTER(C.c_int))), "rfx_leaf_variant")
+    return {"kc": int(o[0]), "one": bool(o[1])}
 
 
 OVL_SAM, OVL_CONTIG, OVL_REGION = 0, 1, 2

@@ -3226,6 +3226,13 @@ int rfx_binned_strike_stats(const rfx_ctx* c, uint64_t out[2]) {
   return RFX_OK;
 }
 
+int rfx_leaf_variant(const rfx_ctx* c, int out[2]) {
+  if (!c || !out) return RFX_E_INVAL;
+  out[0] = c->leaf_kc;
+  out[1] = c->leaf_kc > 0;
+  return RFX_OK;
+}
+
 int rfx_candidates_strike(rfx_candidates* a, const rfx_binned* control) {
   if (!a || !control || a->ctx != control->ctx || a->k != control->k) return RFX_E_INVAL;
   rfx_ctx* c = a->ctx;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/rufus_hip.h"
+#include "rfx_leaf_variant.h"
 
 #define RFX_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define RFX_TILE 1024u          // table slots per finish tile
@@ -68,6 +69,8 @@ struct rfx_ctx {
   // (all of them when k_strike_wave did not run), and whether it ran
   uint64_t strike_units = 0, strike_deferred = 0;
   bool strike_by_wave = false;
+  // the last k_msp_leaf launch (rfx_leaf_variant): the k it was compiled for, 0 the generic kernel, -1 none yet
+  int leaf_kc = -1;
   // the last rfx_bam_settle (rfx_bam_stats): tiles, guesses that repair had to change, repair rounds, records
   uint64_t bam_stats[4] = {0, 0, 0, 0};
   // ... and by the last emit of a table of (about) the same number of k-mer instances: a driver that counts samples of

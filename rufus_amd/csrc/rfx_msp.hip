@@ -991,7 +991,10 @@ constexpr uint32_t MSP_RC_UNLISTED = 0x80000000u;  // record cache count: the re
 // GEO 0: one 1024-thread workgroup per CU (8192-slot table); GEO 1: half of everything, two workgroups per CU.
 // (waves_per_eu: two 768-thread workgroups per CU are six waves per SIMD = 80 registers; left to itself the compiler takes 84
 // since the flush sorts its chunk, and only ONE workgroup fits)
-template <bool CANON, int GEO>
+// KC: 0 -- k is the argument; else k is KC, and every shift, mask and the record layout's k <= 28 branch are constants.
+// ONE: one segment (inst0 / bs0 / ext0: what the trio route hands over), no segment loop, no pointer tables, and the
+// test knob force_mixed taken as 0.  <.., 0, false> is the kernel as it was; msp_leaf_kc (rfx_leaf_variant.h) picks.
+template <bool CANON, int GEO, int KC, bool ONE>
 __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_eu(MSP_LEAF_WPE(GEO), MSP_LEAF_WPE(GEO)))) void k_msp_leaf(
     const uint64_t* const* __restrict__ seg_inst, const uint64_t* const* __restrict__ seg_bs, int nseg,
     const uint64_t* __restrict__ inst0, const uint64_t* __restrict__ bs0, const uint32_t* const* __restrict__ seg_ext,
@@ -999,6 +1002,10 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
     uint64_t* __restrict__ stage_k, uint32_t* __restrict__ stage_c, uint32_t CH, uint32_t* __restrict__ stage_fill,
     uint32_t* __restrict__ stage_more, uint32_t n_chunks, unsigned int* __restrict__ flag, unsigned int* __restrict__ err,
     unsigned int* __restrict__ stage_short, int force_mixed, uint2* __restrict__ bin_at) {
+  // (what a launch fixes, as the compiler sees it)
+  const int kk = KC ? KC : k;
+  const int nsegs = ONE ? 1 : nseg;
+  const bool fmixed = ONE ? false : force_mixed != 0;
   constexpr int TBL_LOG2 = GEO ? 12 : 13, TBL = 1 << TBL_LOG2, BLK = (int)MSP_LEAF_BLK(GEO), FILL = TBL * 3 / 4;
   static_assert(MSP_LEAF_PASS_MAX(GEO) >= (uint32_t)(FILL + BLK) && FILL + BLK <= TBL, "what a pass can leave behind fits the chunk and the table");
   constexpr int RC_LOG2 = TBL_LOG2 - (GEO ? RFX_RC_SHRINK : 2), RC = 1 << RC_LOG2, KMAP = TBL;
@@ -1096,7 +1103,7 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
       auto insert_fwd = [&](uint64_t fwd, uint32_t mult) {
         uint64_t key = fwd;
         if (CANON) {
-          const uint64_t rc = revcomp_bases(fwd, k);
+          const uint64_t rc = revcomp_bases(fwd, kk);
           key = rc < fwd ? rc : fwd;
         }
         if (r > 0 && (split_hash(key) >> (32 - r)) != j) return;
@@ -1128,12 +1135,12 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
       };
       auto insert_record = [&](uint64_t x, uint32_t xe, uint32_t mult) {  // all k-mers of a record, one after the other
         uint64_t lo, hi;
-        msp_record_run(x, xe, k, lo, hi);
+        msp_record_run(x, xe, kk, lo, hi);
         const int n = msp_record_n(x);
-        for (int q = 0; q < n; ++q) insert_fwd(msp_run_kmer(lo, hi, k, n, q), mult);
+        for (int q = 0; q < n; ++q) insert_fwd(msp_run_kmer(lo, hi, kk, n, q), mult);
       };
       // ---- A: records -> cache (+ k-mer map) ----
-      for (int sg = 0; sg < nseg; ++sg) {
+      for (int sg = 0; sg < nsegs; ++sg) {
         const uint64_t a = sg == 0 ? a0 : seg_bs[sg][bin], e = sg == 0 ? e0 : seg_bs[sg][bin + 1];
         const uint64_t* __restrict__ src = sg == 0 ? inst0 : seg_inst[sg];
         const uint32_t* __restrict__ srcx = sg == 0 ? ext0 : seg_ext[sg];
@@ -1157,7 +1164,7 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
 #pragma unroll
           for (int u = 0; u < MSP_ILP; ++u) {
             const uint64_t x = rec[u];
-            const uint32_t xe = msp_plane_bits(recx[u], k);
+            const uint32_t xe = msp_plane_bits(recx[u], kk);
             if (x == MSP_EMPTY) continue;
             uint32_t h = (uint32_t)x ^ (uint32_t)(x >> 23) ^ (uint32_t)(x >> 41) ^ (xe * 0x85EBCA6Bu);
             h *= 0x9E3779B1u;
@@ -1218,11 +1225,11 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
         const uint64_t x = s_rk[slot] ^ ((uint64_t)xe * MSP_RK_MUL);
         if (q == 0 && s_rmin[slot] != xe) s_mixed[X] = 1;  // two different records met in this slot
         uint64_t lo, hi;
-        msp_record_run(x, xe, k, lo, hi);
+        msp_record_run(x, xe, kk, lo, hi);
         const int n = msp_record_n(x);
         const uint32_t mult = s_rc[slot];
-        insert_fwd(msp_run_kmer(lo, hi, k, n, (int)q), mult);
-        if ((int)q + 1 < n) insert_fwd(msp_run_kmer(lo, hi, k, n, (int)q + 1), mult);
+        insert_fwd(msp_run_kmer(lo, hi, kk, n, (int)q), mult);
+        if ((int)q + 1 < n) insert_fwd(msp_run_kmer(lo, hi, kk, n, (int)q + 1), mult);
       }
       if (nk_all > (uint32_t)KMAP) {  // (rare) records that found no room in the map
         for (int i = threadIdx.x; i < RC; i += BLK) {
@@ -1239,7 +1246,7 @@ __global__ __launch_bounds__(MSP_LEAF_BLK(GEO)) __attribute__((amdgpu_waves_per_
       TM(11);
       // (the pass is void: once more, without the cache.  force_mixed -- RFX_LEAF_FORCE_MIXED, a test knob: the recount
       // route is taken by every third bin, a 64-bit coincidence of two records being too rare to wait for)
-      const bool mixed = s_mixed[X] != 0 || (force_mixed && !nocache && bin % 3u == 1u);
+      const bool mixed = s_mixed[X] != 0 || (fmixed && !nocache && bin % 3u == 1u);
       const bool ovf = s_ovf[X] != 0 || mixed;  // from here on: "nothing of this pass leaves"
       const bool split = s_ovf[X] != 0 && !mixed;
       TMC(20, split);
@@ -2272,20 +2279,30 @@ void msp_leaf(rfx_ctx* c, const uint64_t* const* seg_inst, const uint64_t* const
               unsigned int* stage_short, int geo, const uint32_t* const* seg_ext, const uint32_t* ext0, const msp_stage& st,
               uint32_t launch, uint32_t grid, uint2* bin_at) {
   const int force_mixed = getenv("RFX_LEAF_FORCE_MIXED") != nullptr;
+  // (RFX_LEAF_GENERIC: the kernel with k and the segments as arguments whatever the launch, for A/B and bisecting)
+  const int kc = msp_leaf_kc(k, nseg, force_mixed != 0, getenv("RFX_LEAF_GENERIC") != nullptr);
+  c->leaf_kc = kc;  // (rfx_leaf_variant)
   uint32_t* const more = st.more + (bin_at ? 0u : launch);  // (binned: one counter hands out the chunks of all launches)
   {
     rfx_span sp(c, "k_msp_leaf");
-#define RFX_MSP_LEAF(CANON, GEO)                                                                                        \
-  hipLaunchKernelGGL((k_msp_leaf<CANON, GEO>), dim3(grid), dim3(MSP_LEAF_BLK(GEO)), 0, c->stream, seg_inst, seg_bs, nseg, \
-                     inst0, bs0, seg_ext, ext0, P, k, lower, upper, st.keys, st.counts, st.chunk, st.fill, more,           \
+#define RFX_MSP_LEAF(CANON, GEO, KC, ONE)                                                                                  \
+  hipLaunchKernelGGL((k_msp_leaf<CANON, GEO, KC, ONE>), dim3(grid), dim3(MSP_LEAF_BLK(GEO)), 0, c->stream, seg_inst, seg_bs, \
+                     nseg, inst0, bs0, seg_ext, ext0, P, k, lower, upper, st.keys, st.counts, st.chunk, st.fill, more,       \
                      st.n_chunks, flag, err, stage_short, force_mixed, bin_at)
+#define RFX_MSP_LEAF_K(CANON, GEO)                 \
+  do {                                             \
+    if (kc == 25) RFX_MSP_LEAF(CANON, GEO, 25, true); \
+    else if (kc == 31) RFX_MSP_LEAF(CANON, GEO, 31, true); \
+    else RFX_MSP_LEAF(CANON, GEO, 0, false);       \
+  } while (0)
     if (canonical) {
-      if (geo) RFX_MSP_LEAF(true, 1);
-      else RFX_MSP_LEAF(true, 0);
+      if (geo) RFX_MSP_LEAF_K(true, 1);
+      else RFX_MSP_LEAF_K(true, 0);
     } else {
-      if (geo) RFX_MSP_LEAF(false, 1);
-      else RFX_MSP_LEAF(false, 0);
+      if (geo) RFX_MSP_LEAF_K(false, 1);
+      else RFX_MSP_LEAF_K(false, 0);
     }
+#undef RFX_MSP_LEAF_K
 #undef RFX_MSP_LEAF
   }
   if (!bin_at) {  // (binned: the survivors stay in the staging pool, minimizer bin after minimizer bin)
