@@ -703,6 +703,12 @@ int rfx_binned_strike_stats(const rfx_ctx*, uint64_t out[2]);
  * form.  k = 25 and 31 with one segment take the compiled ones unless RFX_LEAF_GENERIC or RFX_LEAF_FORCE_MIXED is set.
  * Host-side bookkeeping, for tests and measurements. */
 int rfx_leaf_variant(const rfx_ctx*, int out[2]);
+/* The form the context's last k_msp_replay launch (a shard pass's records from reads + run map) took: 0 a lane cuts the
+ * runs of its own read (RFX_REPLAY_OLD=1), 1 the per-wave queue with one scattered store per record (RFX_REPLAY_SCATTER=1,
+ * or a pass whose bins span more than 64 coarse bins), 2 the per-wave queue with a wave's records sorted by coarse bin in
+ * LDS and written in bin order (the default), -1 when the context has launched none.  Both knobs are read at every launch.
+ * Host-side bookkeeping, for tests and measurements. */
+int rfx_replay_variant(const rfx_ctx*, int* out);
 /* rfx_records_subtract(candidates, {control}, 0, ~0) for every further control: its keys are struck off the list */
 int rfx_candidates_strike(rfx_candidates*, const rfx_binned* control);
 /* entries of the list (struck ones included); _get: all of them, a struck one as ~0 -- canonical keys, no order */

@@ -64,6 +64,7 @@ SIGNATURES = {
     "rfx_binned_strike": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rfx_binned_strike_stats": (C.c_int, [C.c_void_p, u64p]),
     "rfx_leaf_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rfx_replay_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rfx_candidates_strike": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rfx_candidates_size": (C.c_uint64, [C.c_void_p]),
     "rfx_candidates_get": (C.c_int, [C.c_void_p, u64p]),
@@ -1213,6 +1214,18 @@ def leaf_variant(ctx: Context) -> dict:
     o = np.zeros(2, dtype=np.int32)
     _check(lib().rfx_leaf_variant(ctx._h, o.ctypes.data_as(C.POINTER(C.c_int))), "rfx_leaf_variant")
     return {"kc": int(o[0]), "one": bool(o[1])}
+
+
+REPLAY_OLD, REPLAY_SCATTER, REPLAY_COMBINE = 0, 1, 2
+
+
+def replay_variant(ctx: Context) -> int:
+    """The form the context's last k_msp_replay launch took: REPLAY_OLD (a lane per read, RFX_REPLAY_OLD=1), REPLAY_SCATTER
+    (per-wave queue, one scattered store per record: RFX_REPLAY_SCATTER=1), REPLAY_COMBINE (per-wave queue, records
+    written in bin order: the default), -1: no launch yet -- rfx_replay_variant."""
+    o = C.c_int(-1)
+    _check(lib().rfx_replay_variant(ctx._h, C.byref(o)), "rfx_replay_variant")
+    return int(o.value)
 
 
 OVL_SAM, OVL_CONTIG, OVL_REGION = 0, 1, 2

@@ -3233,6 +3233,12 @@ int rfx_leaf_variant(const rfx_ctx* c, int out[2]) {
   return RFX_OK;
 }
 
+int rfx_replay_variant(const rfx_ctx* c, int* out) {
+  if (!c || !out) return RFX_E_INVAL;
+  *out = c->replay_form;
+  return RFX_OK;
+}
+
 int rfx_candidates_strike(rfx_candidates* a, const rfx_binned* control) {
   if (!a || !control || a->ctx != control->ctx || a->k != control->k) return RFX_E_INVAL;
   rfx_ctx* c = a->ctx;

@@ -71,6 +71,9 @@ struct rfx_ctx {
   bool strike_by_wave = false;
   // the last k_msp_leaf launch (rfx_leaf_variant): the k it was compiled for, 0 the generic kernel, -1 none yet
   int leaf_kc = -1;
+  // the last k_msp_replay launch (rfx_replay_variant): 0 a lane per read, 1 queued + scattered stores, 2 queued + records
+  // written in bin order, -1 none yet
+  int replay_form = -1;
   // the last rfx_bam_settle (rfx_bam_stats): tiles, guesses that repair had to change, repair rounds, records
   uint64_t bam_stats[4] = {0, 0, 0, 0};
   // ... and by the last emit of a table of (about) the same number of k-mer instances: a driver that counts samples of

@@ -618,14 +618,25 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_part1(rfx_reads_view rv, int 
 // takes the next set bit.  (The first version stepped over gaps and the other half's runs one by one: 36 wave-
 // instructions per 64 bases and pass, 30 of them scalar loop control -- more than half of what the hashing costs.)
 constexpr int RP_STRIDE = 25;  // dwords per lane: 10 of read, 7 of entries, 7 of end positions, 1 that keeps the stride odd
+constexpr int RC_KEEP = 12, RC_ROUND = 384;  // COMBINE: records a lane keeps per chunk; records a wave sorts per round
+// (COMBINE: four waves per SIMD is what two workgroups per CU need -- 128 VGPRs; the other forms are left to the compiler)
+constexpr int RP_WPE_MIN(bool combine) { return combine ? 4 : 1; }
+constexpr int RP_WPE_MAX(bool combine) { return combine ? 4 : 8; }
 // QUEUED (round 6): the runs of a wave's 64 reads go through a per-wave queue and are cut 64 at a time, one per lane.
 // With a lane cutting the runs of ITS read, a turn of the loop lasted as long as the read with the most runs of this pass
 // had any: 16 - 17 of them where the mean is 11 (half of ~22, binomially), so two lanes in five idled through ~85
 // instructions per run.  Now every lane writes its runs' descriptors -- lane | entry index << 6, at most 8 per batch:
 // 512 per wave -- to the wave's queue (one LDS add to one address = a wave scan: -amdgpu-atomic-optimizer-strategy=DPP) and
 // lane t cuts run t, t + 64, ..: the entry, its end position and the read's dwords come out of the OWNER's staging area.
-template <bool CANON, bool QUEUED>
-__global__ __launch_bounds__(MP1_BLOCK) void k_msp_replay(rfx_reads_view rv, const uint4* __restrict__ map, int k, int bin_bits,
+// COMBINE (a form of QUEUED; <.., true, false> and <.., false, false> are the kernels as they were, instruction for
+// instruction): a record no longer leaves as one 12-byte store to a cache line of its own -- 64 lanes, 64 slabs; those
+// stores were a third of the kernel's time (profiles/replay_combine.txt).  A lane keeps what it cuts in the first six
+// trips of a chunk in registers; when the wave has cut its chunk it sorts them by coarse bin in its own, then dead,
+// staging areas and queue, reserves a bin's slots with one s_fill add, and lane x writes record x: a bin's records of
+// the round lie side by side.  Wave barriers only; the slot -> slab mapping, s_fine, n_emit and the hand-over behind the
+// chunk's two __syncthreads() are untouched.  The launch needs the pass's bins within 64 coarse bins (msp_replay checks).
+template <bool CANON, bool QUEUED, bool COMBINE = false>
+__global__ __launch_bounds__(MP1_BLOCK) __attribute__((amdgpu_waves_per_eu(RP_WPE_MIN(COMBINE), RP_WPE_MAX(COMBINE)))) void k_msp_replay(rfx_reads_view rv, const uint4* __restrict__ map, int k, int bin_bits,
                                                           uint32_t bin_lo, uint32_t bin_hi, msp_rec12* __restrict__ rec_a,
                                                           uint32_t* __restrict__ coarse_cur, uint32_t cap_a,
                                                           uint32_t* __restrict__ cnt_rows, unsigned int* __restrict__ flag,
@@ -634,10 +645,10 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_replay(rfx_reads_view rv, con
   __shared__ uint32_t s_fill[P1_BINS];
   __shared__ uint64_t s_slab[3][P1_BINS];
   __shared__ uint32_t s_fine[4096];  // 8-bit counters of bins bin_lo .. bin_lo + 16383 (a shard pass holds at most half of 32768)
-  __shared__ uint32_t s_rd[MP1_BLOCK * RP_STRIDE + 4];
+  __shared__ __attribute__((aligned(16))) uint32_t s_rd[MP1_BLOCK * RP_STRIDE + 4];  // (16: COMBINE's sort moves 16-byte records)
   __shared__ uint32_t s_sum, s_emit;
   constexpr int RQ_BATCH = 8, RQ_CAP = 64 * RQ_BATCH;  // runs a lane queues per batch; descriptors per wave
-  __shared__ uint16_t s_q[QUEUED ? MP1_BLOCK / 64 : 1][QUEUED ? RQ_CAP : 1];
+  __shared__ __attribute__((aligned(8))) uint16_t s_q[QUEUED ? MP1_BLOCK / 64 : 1][QUEUED ? RQ_CAP : 1];  // (8: COMBINE keeps uint2 there)
   __shared__ uint32_t s_qn[QUEUED ? MP1_BLOCK / 64 : 1];
   const uint32_t P = 1u << bin_bits;
   const int sub_bits = bin_bits - 7;
@@ -721,7 +732,7 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_replay(rfx_reads_view rv, con
     // (a lane reads only what it wrote itself: no barrier)
     uint32_t mine = ~gaps & ((1u << cnt) - 1u);
     if (half_sel != 2u) mine &= half_sel ? flags : ~flags;
-    if constexpr (QUEUED) {
+    if constexpr (QUEUED && !COMBINE) {
       const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
       uint16_t* const wq = s_q[wv];
       const uint32_t* const wrd = s_rd + (size_t)(wv * 64u) * RP_STRIDE;  // the wave's 64 staging areas
@@ -814,6 +825,210 @@ __global__ __launch_bounds__(MP1_BLOCK) void k_msp_replay(rfx_reads_view rv, con
               atomicAdd(&s_fine[fb >> 2], 1u << ((fb & 3u) * 8));
             }
           }
+        }
+      }
+    } else if constexpr (COMBINE) {
+      static_assert(QUEUED, "COMBINE is a form of the queued kernel");
+      const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
+      uint16_t* const wq = s_q[wv];
+      const uint32_t* const wrd = s_rd + (size_t)(wv * 64u) * RP_STRIDE;  // the wave's 64 staging areas
+      // What a lane cuts in the first six trips of a chunk -- the first batch's four, the second's first two -- stays in
+      // registers: slot 8 * batch + 2 * trip + u, with the run's coarse bin (counted from the pass's first) in a 16-bit field
+      // of km, 0xFFFF: no record.  (16 slots, both batches whole: 128 VGPRs and 24 bytes of scratch per lane.)
+      uint64_t kw[RC_KEEP];
+      uint32_t kx[RC_KEEP], km[RC_KEEP / 2];
+#pragma unroll
+      for (int j = 0; j < RC_KEEP / 2; ++j) km[j] = 0xFFFFFFFFu;
+      // ---- a batch: every lane queues its next <= RQ_BATCH runs; returns how many the wave queued ----
+      auto queue_batch = [&]() -> uint32_t {
+        if (ln == 0) s_qn[wv] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t take = mine;
+#pragma unroll
+        for (int t = 0; t < RQ_BATCH; ++t) take &= take - 1u;  // `mine` without its RQ_BATCH lowest set bits ...
+        take = mine & ~take;                                    // ... = those bits
+        mine &= ~take;
+        uint32_t at = atomicAdd(&s_qn[wv], (uint32_t)__popc(take));  // (one address: a wave scan)
+        while (__ballot(take != 0)) {
+          if (take) {
+            const uint32_t i = (uint32_t)__ffs((int)take) - 1u;
+            take &= take - 1u;
+            wq[at++] = (uint16_t)(ln | (i << 6));
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        return s_qn[wv];
+      };
+      // ---- lane t cuts runs t0 + t and t0 + t + 64 of the T queued: two per trip, stage by stage, so that their LDS round
+      // trips (descriptor, entry, read words, slab slot) overlap instead of queueing up.  J < 0: the records go to their
+      // slab slots, one scattered store each; else into register slots J and J + 1 ----
+      auto cut2 = [&](uint32_t t0, uint32_t T, auto JC) {
+        constexpr int J = decltype(JC)::value;
+        bool on[2], put[2];
+        uint32_t dsc[2], en[2], pe[2], sh[2], d[2][4], run_bin[2], slot[2], bh[2];
+        const uint32_t* ord[2];
+        uint64_t lo[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          on[u] = t0 + (uint32_t)u * 64u + ln < T;
+          dsc[u] = on[u] ? wq[t0 + (uint32_t)u * 64u + ln] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          ord[u] = wrd + (size_t)(dsc[u] & 63u) * RP_STRIDE;  // the owner's area
+          const uint32_t i = dsc[u] >> 6;
+          en[u] = ((const uint8_t*)(ord[u] + 10))[i];
+          pe[u] = ((const uint8_t*)(ord[u] + 17))[i];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const uint32_t e = (uint32_t)k - 2u + pe[u];  // the run's last k-mer ends at base e
+          const uint32_t o = 2u * (159u - e), dw = o >> 5;
+          sh[u] = o & 31u;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) d[u][j] = ord[u][dw + j];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const uint32_t back = en[u] >> 4;
+          lo[u] = (uint64_t)__builtin_amdgcn_alignbit(d[u][1], d[u][0], sh[u]) |
+                  ((uint64_t)__builtin_amdgcn_alignbit(d[u][2], d[u][1], sh[u]) << 32);
+          const uint32_t f = (uint32_t)(lo[u] >> (2u * back)) & mmask;
+          uint32_t c = f;
+          if (CANON) {
+            uint32_t y = __brev(~f);
+            y = ((y & 0xAAAAAAAAu) >> 1) | ((y & 0x55555555u) << 1);
+            c = min(f, y >> (32 - 2 * m));
+          }
+          bh[u] = msp_binhash(mmer_hash(c));
+          run_bin[u] = bh[u] >> (32 - bin_bits);
+          put[u] = on[u] && run_bin[u] - bin_lo < bin_hi - bin_lo;
+          if constexpr (J < 0) slot[u] = put[u] ? atomicAdd(&s_fill[run_bin[u] >> sub_bits], 1u) : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          if (put[u]) {
+            const int n = (int)(en[u] & 15u) + 1;
+            const uint32_t back = en[u] >> 4;
+            const uint32_t hi = __builtin_amdgcn_alignbit(d[u][3], d[u][2], sh[u]) & 0x3FFFFFu;
+            uint64_t w;
+            uint32_t x;
+            msp_record_make(lo[u], hi, k, n, (uint32_t)(k + n - 1 - m) - back, w, x);
+            x |= msp_stamp(bh[u], k);
+            const uint32_t coarse = run_bin[u] >> sub_bits;
+            if constexpr (J < 0) {
+              if (slot[u] < 2 * SLAB) {
+                const uint64_t sb = s_slab[slot[u] >> slab_log2][coarse];
+                msp_rec12_store(rec_a, sb + (slot[u] & (SLAB - 1)), w, x);
+              } else {  // more than two slabs' worth in one chunk: one reservation per record
+                const uint32_t at2 = atomicAdd(&coarse_cur[coarse * P1_CUR_STRIDE], 1u);
+                if (at2 < cap_a) msp_rec12_store(rec_a, (uint64_t)coarse * cap_a + at2, w, x);
+                else atomicExch(flag, 1u);
+              }
+            } else {
+              const int S = J + u, SH = (S & 1) * 16;  // (the loop over u is unrolled: constants)
+              kw[S] = w;
+              kx[S] = x;
+              km[S >> 1] = (km[S >> 1] & ~(0xFFFFu << SH)) | ((coarse - (bin_lo >> sub_bits)) << SH);
+            }
+            ++n_emit;
+            const uint32_t fb = run_bin[u] - bin_lo;
+            atomicAdd(&s_fine[fb >> 2], 1u << ((fb & 3u) * 8));
+          }
+        }
+      };
+      {
+        // the first two batches with every index a constant: a batch is at most 512 runs = four trips
+        auto kept_batch = [&](auto BC) {
+          constexpr int B = decltype(BC)::value;
+          const uint32_t T = queue_batch();
+          cut2(0u, T, std::integral_constant<int, 8 * B>());
+          if (T > 128u) cut2(128u, T, std::integral_constant<int, 8 * B + 2>());
+          if constexpr (8 * B + 4 < RC_KEEP) {
+            if (T > 256u) cut2(256u, T, std::integral_constant<int, 8 * B + 4>());
+            if (T > 384u) cut2(384u, T, std::integral_constant<int, 8 * B + 6>());
+          } else {
+            for (uint32_t t0 = 256u; t0 < T; t0 += 128u) cut2(t0, T, std::integral_constant<int, -1>());
+          }
+        };
+        if (__ballot(mine != 0)) kept_batch(std::integral_constant<int, 0>());
+        if (__ballot(mine != 0)) kept_batch(std::integral_constant<int, 1>());
+      }
+      while (__ballot(mine != 0)) {  // (a lane with more than 16 runs of this pass: a few records per wave at S = 2)
+        const uint32_t T = queue_batch();
+        for (uint32_t t0 = 0; t0 < T; t0 += 128u) cut2(t0, T, std::integral_constant<int, -1>());
+      }
+      {
+        // The wave has cut its runs: its 64 staging areas and its queue are dead until the next chunk is staged, and no
+        // other wave ever read them.  In them the kept records are sorted by coarse bin, in two rounds of at most 384
+        // (round r: slots 6 r .. 6 r + 5), and leave with consecutive lanes at consecutive addresses, as k_part2's tile
+        // does.  One s_fill add per bin and round instead of one per record.  Wave barriers only.
+        // A record travels through LDS as 16 bytes: word, plane, and bin << 16 | slot in its coarse bin's slabs.
+        uint4* const area = (uint4*)(s_rd + (size_t)(wv * 64u) * RP_STRIDE);  // RC_ROUND records, then 64 bin counters
+        uint32_t* const cntw = (uint32_t*)(area + RC_ROUND);
+        uint2* const binw = (uint2*)wq;  // per bin: where its records start in the round, its first slot
+        static_assert(4 * RC_ROUND + 64 <= 64 * RP_STRIDE && (64 * RP_STRIDE) % 4 == 0 && 64 * 8 <= 2 * RQ_CAP,
+                      "the sort area is the wave's own");
+        const uint32_t coarse0 = bin_lo >> sub_bits;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          bool any = false;
+#pragma unroll
+          for (int jj = 0; jj < RC_KEEP / 2; ++jj) {
+            const int S = RC_KEEP / 2 * r + jj;
+            any |= ((km[S >> 1] >> ((S & 1) * 16)) & 0xFFFFu) != 0xFFFFu;
+          }
+          if (!__ballot(any)) continue;
+          cntw[ln] = 0;
+          if (ln == 0) s_qn[wv] = 0;
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int jj = 0; jj < RC_KEEP / 2; ++jj) {  // a record's rank in its bin, into bits 7 .. 15 of its field
+            const int S = RC_KEEP / 2 * r + jj, SH = (S & 1) * 16;
+            const uint32_t h = (km[S >> 1] >> SH) & 0xFFFFu;
+            if (h != 0xFFFFu) km[S >> 1] |= atomicAdd(&cntw[h], 1u) << (SH + 7);
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          {
+            const uint32_t cn = cntw[ln];
+            const uint32_t st = atomicAdd(&s_qn[wv], cn);  // (one address: a wave scan)
+            const uint32_t base = cn ? atomicAdd(&s_fill[coarse0 + ln], cn) : 0u;
+            binw[ln] = make_uint2(st, base);
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          const uint32_t N = s_qn[wv];
+#pragma unroll
+          for (int jj = 0; jj < RC_KEEP / 2; ++jj) {
+            const int S = RC_KEEP / 2 * r + jj, SH = (S & 1) * 16;
+            const uint32_t h = (km[S >> 1] >> SH) & 0xFFFFu;
+            if (h != 0xFFFFu) {
+              const uint32_t lb = h & 127u;
+              const uint2 sb = binw[lb];
+              area[sb.x + (h >> 7)] = make_uint4((uint32_t)kw[S], (uint32_t)(kw[S] >> 32), kx[S], lb << 16 | min(sb.y + (h >> 7), 0xFFFFu));
+            }
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          for (uint32_t i = ln; i < N; i += 64u) {
+            const uint4 rc = area[i];
+            const uint32_t slot = rc.w & 0xFFFFu, coarse = coarse0 + (rc.w >> 16);
+            const uint64_t w = (uint64_t)rc.x | ((uint64_t)rc.y << 32);
+            if (slot < 2 * SLAB) {
+              const uint64_t sb = s_slab[slot >> slab_log2][coarse];
+              msp_rec12_store(rec_a, sb + (slot & (SLAB - 1)), w, rc.z);
+            } else {  // more than two slabs' worth in one chunk: one reservation per record
+              const uint32_t at2 = atomicAdd(&coarse_cur[coarse * P1_CUR_STRIDE], 1u);
+              if (at2 < cap_a) msp_rec12_store(rec_a, (uint64_t)coarse * cap_a + at2, w, rc.z);
+              else atomicExch(flag, 1u);
+            }
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
         }
       }
     } else {
@@ -2238,15 +2453,25 @@ void msp_replay(rfx_ctx* c, const rfx_reads_view& rv, const void* map, int k, in
                 uint32_t bin_hi, int grid, void* rec_a, uint32_t* coarse_cur, uint32_t cap_a, uint32_t* cnt_rows,
                 unsigned int* flag, int slab_log2) {
   rfx_span sp(c, "k_msp_replay");
-  static const bool queued = getenv("RFX_REPLAY_OLD") == nullptr;  // (A/B: a lane cuts the runs of its own read, as in round 5)
-#define RFX_REPLAY(CANON, Q)                                                                                                  \
-  hipLaunchKernelGGL((k_msp_replay<CANON, Q>), dim3(grid), dim3(MP1_BLOCK), 0, c->stream, rv, (const uint4*)map, k, bin_bits, \
-                     bin_lo, bin_hi, (msp_rec12*)rec_a, coarse_cur, cap_a, cnt_rows, flag, slab_log2)
+  // Which form (rfx_replay_variant).  Read per launch, so that a test can switch within one process.
+  //   RFX_REPLAY_OLD      0: a lane cuts the runs of its own read, as in round 5
+  //   RFX_REPLAY_SCATTER  1: the per-wave queue, every record one scattered store
+  //   neither             2: the per-wave queue, a wave's records sorted by coarse bin in LDS and written in bin order --
+  //                          when the pass's bins lie in at most 64 coarse bins (the wave's bin counters); else 1
+  const int sub_bits = bin_bits - 7;
+  const bool fits = bin_hi > bin_lo && sub_bits >= 0 && ((bin_hi - 1) >> sub_bits) - (bin_lo >> sub_bits) < 64u;
+  const int form = getenv("RFX_REPLAY_OLD") ? 0 : getenv("RFX_REPLAY_SCATTER") || !fits ? 1 : 2;
+  c->replay_form = form;
+#define RFX_REPLAY(CANON, ...)                                                                                               \
+  hipLaunchKernelGGL((k_msp_replay<CANON, __VA_ARGS__>), dim3(grid), dim3(MP1_BLOCK), 0, c->stream, rv, (const uint4*)map, k, \
+                     bin_bits, bin_lo, bin_hi, (msp_rec12*)rec_a, coarse_cur, cap_a, cnt_rows, flag, slab_log2)
   if (canonical) {
-    if (queued) RFX_REPLAY(true, true);
+    if (form == 2) RFX_REPLAY(true, true, true);
+    else if (form == 1) RFX_REPLAY(true, true);
     else RFX_REPLAY(true, false);
   } else {
-    if (queued) RFX_REPLAY(false, true);
+    if (form == 2) RFX_REPLAY(false, true, true);
+    else if (form == 1) RFX_REPLAY(false, true);
     else RFX_REPLAY(false, false);
   }
 #undef RFX_REPLAY
