@@ -321,6 +321,22 @@ int rfx_text_gather(rfx_text* t, const uint64_t* hitmask, uint64_t n_records, vo
  * record's refID differs from the kept record before it; *n_runs = their number (more than cap: NULL, "RFX_E_RANGE" in the
  * error text, *n_runs set; cap = the arena's records always suffices).  NULL on failure, rfx_last_error() says why.
  *
+ * rfx_bam_set_region (replaces the REGION argument of `samtools view -F 3328 X.bam REGION`, what runRufus.sh -R puts into
+ * the generators of :599, :639 and :964-967): on an arena settled by rfx_bam_settle (else RFX_E_INVAL), one keep byte per
+ * record -- refID == tid, pos < end and pos + rlen > beg (0-based, half open; rlen = the reference bases the CIGAR consumes,
+ * 1 for flag 4, no CIGAR or none consumed: rfx_bam_core.h bam_in_region, 64-bit) -- that lives with the arena until
+ * rfx_text_reset or the next rfx_bam_settle.  While it is set, "kept" means the flag test AND that byte in rfx_bam_parse
+ * and in the five functions of the next section and rfx_bam_locate; without it they are what they were.  *n_in = the
+ * records inside the region, before any flag filter.  A second call replaces the first.
+ *
+ * rfx_bam_region_parse, rfx_bai_query (pure host code, need no device; rufus_amd/csrc/host/rfx_bai.hpp): the region's text
+ * -- a reference's name as a whole, else NAME:BEG[-END] cut at the LAST colon, 1-based inclusive, commas dropped -- to
+ * (tid, [beg, end)), names as rfx_bam_header gives them; and the ONE range of virtual offsets [start, stop) of a .bai
+ * (section 5.2 of the SAM specification) in which every record of the region starts, or *empty.  A superset is exact,
+ * because rfx_bam_set_region decides every record.  RFX_E_FORMAT with the reason in why[0, why_cap) for a text or an index
+ * that is refused (unknown name, BEG < 1, END < BEG, trailing characters; wrong magic, n_ref that is not the BAM's, counts
+ * or offsets beyond the file's bytes, a chunk with beg >= end or beyond bam_size).
+ *
  * rfx_bam_stats: of the last rfx_bam_settle on this ctx -- out[0] tiles, out[1] guesses that repair had to change, out[2]
  * repair rounds, out[3] records.  For tests and measurements, like rfx_binned_strike_stats.
  * ------------------------------------------------------------------------------------------- */
@@ -328,6 +344,11 @@ int rfx_bam_header(const void* buf, uint64_t n, int* complete, int32_t* n_ref, c
                    uint64_t* names_bytes, uint64_t* first_block, uint32_t* skip);
 int rfx_bam_settle(rfx_text* t, rfx_text* next, uint64_t skip, int32_t n_ref, uint64_t* n_records, uint64_t* carried);
 rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs, uint64_t cap, uint64_t* n_runs);
+int rfx_bam_set_region(rfx_text* t, int32_t tid, int64_t beg, int64_t end, uint64_t* n_in);
+int rfx_bam_region_parse(const char* text, const char* names, uint64_t names_bytes, int32_t* tid, int64_t* beg, int64_t* end,
+                         char* why, uint64_t why_cap);
+int rfx_bai_query(const void* bai, uint64_t n, int32_t n_ref, uint64_t bam_size, int32_t tid, int64_t beg, int64_t end, int* empty,
+                  uint64_t* start, uint64_t* stop, char* why, uint64_t why_cap);
 int rfx_bam_stats(const rfx_ctx*, uint64_t out[4]);
 
 /* -------------------------------------------------------------------------------------------

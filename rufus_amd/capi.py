@@ -110,6 +110,11 @@ SIGNATURES = {
     "rfx_bam_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, u64p, u64p]),
     "rfx_bam_parse": (C.c_void_p, [C.c_void_p, C.c_uint32, u32p, C.c_uint64, u64p]),
     "rfx_bam_stats": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_bam_set_region": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, u64p]),
+    "rfx_bam_region_parse": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.c_char_p, C.c_uint64]),
+    "rfx_bai_query": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int64,
+                                C.POINTER(C.c_int), u64p, u64p, C.c_char_p, C.c_uint64]),
     "rfx_bam_parse_filter": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_int, u32p, C.c_uint64, u64p]),
     "rfx_bam_name_hashes": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_uint64, u64p, C.c_uint64, u64p]),
     "rfx_nameset_build": (C.c_void_p, [C.c_void_p, u64p, C.c_uint64]),
@@ -353,6 +358,33 @@ def bam_header(data: bytes):
     return {"n_ref": int(n_ref.value), "names": names, "first_block": int(first.value), "skip": int(skip.value)}
 
 
+def bam_region_parse(text, ref_names):
+    """``rfx_bam_region_parse``: (tid, beg, end) of a region as `samtools view` reads it -- a reference's name as a whole, else
+    NAME:BEG[-END] cut at the last colon, 1-based inclusive, commas dropped -> 0-based [beg, end).  ref_names: the header's
+    (list of bytes).  RufusError with the reason for a text that is refused.  Pure host code."""
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    names = b"".join(bytes(n) + b"\0" for n in ref_names)
+    tid, beg, end = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    why = C.create_string_buffer(512)
+    rc = lib().rfx_bam_region_parse(text, names, len(names), C.byref(tid), C.byref(beg), C.byref(end), why, len(why))
+    if rc:
+        raise RufusError(f"rfx_bam_region_parse failed ({rc}): " + why.value.decode(errors="replace"))
+    return int(tid.value), int(beg.value), int(end.value)
+
+
+def bai_query(bai: bytes, n_ref: int, bam_size: int, tid: int, beg: int, end: int):
+    """``rfx_bai_query``: the one range (start, stop) of virtual offsets of a .bai in which every record that overlaps
+    [beg, end) of reference tid starts, or None when the index has no chunk for it.  RufusError with the reason for an
+    index that is refused.  Pure host code."""
+    empty, start, stop = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+    why = C.create_string_buffer(512)
+    rc = lib().rfx_bai_query(bai, len(bai), n_ref, bam_size, tid, beg, end, C.byref(empty), C.byref(start), C.byref(stop), why,
+                             len(why))
+    if rc:
+        raise RufusError(f"rfx_bai_query failed ({rc}): " + why.value.decode(errors="replace"))
+    return None if empty.value else (int(start.value), int(stop.value))
+
+
 class PackedReads:
     """Host-side packed block: 32 bases per 64-bit code word, one mask bit per base."""
 
@@ -511,6 +543,13 @@ class TextArena:
                                     C.byref(carried)), "rfx_bam_settle")
         self._bam_records = int(rec.value)
         return int(rec.value), int(carried.value)
+
+    def bam_set_region(self, tid: int, beg: int, end: int) -> int:
+        """From here to the next reset or bam_settle, a KEPT record of this arena also overlaps [beg, end) of reference tid
+        (0-based, half open): the number of records inside the region, before any flag filter (rfx_bam_set_region)."""
+        n_in = C.c_uint64(0)
+        _check(lib().rfx_bam_set_region(self._h, tid, beg, end, C.byref(n_in)), "rfx_bam_set_region")
+        return int(n_in.value)
 
     def bam_parse(self, exclude_flags: int = 3328):
         """(block, runs): the records with flag & exclude_flags == 0 of an arena settled by bam_settle as a count block, and

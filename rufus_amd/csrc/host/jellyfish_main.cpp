@@ -78,15 +78,19 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // scripts/RunJellyForRUFUS.sh:28-29; N defaults to 3328) -- BGZF inflated, the records found and their sequences packed
   // on the device (rfx_ingest.hpp BamIngest; csrc/rfx_bam.hip), the chromosome log written.  Goes with --keep-packed
   // (above), not with --sam or --spool.
+  // --region REG (with --bam, ONE input; not in jellyfish): `samtools view -F N X.bam REG`, what runRufus.sh -R puts into the
+  // generator -- only the records that overlap CHR[:BEG[-END]] are counted and logged; X.bam.bai / X.bai, when there, limits
+  // what is inflated (rfx_bai.hpp, BamIngest::set_region).  Not with --keep-packed: the cache does not record a region.
   const char* bam_chr = nullptr;
+  const char* bam_region = nullptr;
   uint32_t bam_exclude = 3328;
-  enum { OPT_DISK = 1000, OPT_OCL, OPT_TIMING, OPT_TEXT, OPT_SAM, OPT_SPOOL, OPT_KEEP, OPT_KEEPQ, OPT_BAM, OPT_BAMX };
+  enum { OPT_DISK = 1000, OPT_OCL, OPT_TIMING, OPT_TEXT, OPT_SAM, OPT_SPOOL, OPT_KEEP, OPT_KEEPQ, OPT_BAM, OPT_BAMX, OPT_REGION };
   static option lo[] = {{"mer-len", 1, 0, 'm'},      {"size", 1, 0, 's'},        {"threads", 1, 0, 't'},
                         {"output", 1, 0, 'o'},       {"counter-len", 1, 0, 'c'}, {"out-counter-len", 1, 0, OPT_OCL},
                         {"canonical", 0, 0, 'C'},    {"disk", 0, 0, OPT_DISK},   {"lower-count", 1, 0, 'L'},
                         {"upper-count", 1, 0, 'U'},  {"timing", 1, 0, OPT_TIMING}, {"text", 0, 0, OPT_TEXT}, {"sam", 1, 0, OPT_SAM},
                         {"spool", 1, 0, OPT_SPOOL},  {"keep-packed", 1, 0, OPT_KEEP}, {"keep-minq", 1, 0, OPT_KEEPQ},
-                        {"bam", 1, 0, OPT_BAM},      {"bam-exclude", 1, 0, OPT_BAMX},
+                        {"bam", 1, 0, OPT_BAM},      {"bam-exclude", 1, 0, OPT_BAMX}, {"region", 1, 0, OPT_REGION},
                         {"reprobes", 1, 0, 'p'},     {0, 0, 0, 0}};
   optind = 1;
   int ch;
@@ -110,6 +114,10 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
       case OPT_KEEPQ: keep_minq = atoi(optarg); break;
       case OPT_BAM: bam_chr = optarg; break;
       case OPT_BAMX: bam_exclude = (uint32_t)strtoul(optarg, nullptr, 0); break;
+      case OPT_REGION:
+        if (bam_region) die("rufus_amd jellyfish count: --region given twice: one region per run");
+        bam_region = optarg;
+        break;
       case OPT_TEXT: die("rufus_amd jellyfish: --text output is not on the RUFUS path");
       default: die("Usage: jellyfish count -m K -s SIZE [-C] [-L n] [-U n] [-t T] [-o OUT] [--disk] file...");
     }
@@ -120,6 +128,10 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
       "rufus_amd jellyfish count: --bam finds and packs the records on the device, which needs one device and none of --sam, "
       "--spool, --keep-packed";
   if (bam_chr && (sam_chr || spool_path)) die(bam_alone);
+  if (bam_region && !bam_chr) die("rufus_amd jellyfish count: --region goes with --bam CHR_FILE: only a BAM's records carry a position");
+  if (bam_region && keep_path)
+    die("rufus_amd jellyfish count: --region does not go with --keep-packed: the cache does not record a region");
+  if (bam_region && argc - optind != 1) die("rufus_amd jellyfish count: --region goes with ONE input: the region names one file's references");
   int lsize = 0;
   while ((1ull << lsize) < size) ++lsize;
   if (lsize < 1) lsize = 1;
@@ -341,6 +353,7 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
             if (kfd < 0) die(std::string("Can't open the packed-read cache '") + keep_path + "'");
             bam_ingest->set_keep_packed(kfd, keep_minq);
           }
+          if (bam_region) bam_ingest->set_region(bam_region, in.path);
           trace("count: bam route, arenas open");
         }
         void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);

@@ -35,6 +35,7 @@
 #include "rfx_bam_pairs.hpp"
 #include "rfx_packed_cache.hpp"
 #include "rfx_bam_cache.hpp"
+#include "rfx_bai.hpp"
 
 namespace rfxcli {
 
@@ -1251,10 +1252,18 @@ class BgzfIngest {
 // block rfx_bam_header names; `skip`, the header's bytes in that block, goes to the first arena's settle only.  The
 // chromosome log of PassThroughSamCheck (src/PassThroughSamCheck.cpp:140-155) is stitched on the host from the arenas'
 // run lists: a run that begins an arena with the refID the arena before ended with is no change.
+//
+// set_region (`samtools view -F N X.bam REGION` in front of the feeder, runRufus.sh -R): the header is read as ever; the
+// runs of blocks then begin at the block of the index's START (rfx_bai.hpp: one range per region) with `skip` = START's
+// offset inside it, and end with STOP's block.  Every settled arena gets rfx_bam_set_region before anything looks at its
+// records, so the index decides what is inflated and nothing else.  Without a usable index the whole file is walked.
+// The last arena of a range may end inside a record -- STOP's block holds whatever follows the region -- which is accepted
+// only where that record starts at or behind STOP.
 // (weak, as above: the host harnesses link the executable's source against stand-in libraries without these)
 #pragma weak rfx_bam_header
 #pragma weak rfx_bam_settle
 #pragma weak rfx_bam_parse
+#pragma weak rfx_bam_set_region
 #pragma weak rfx_bam_parse_filter
 #pragma weak rfx_bam_name_hashes
 #pragma weak rfx_bam_locate
@@ -1285,6 +1294,12 @@ class BamIngest {
   // (runRufus.sh:964-967 after scripts/RunJellyForRUFUS.sh:28-29)
   int cache_fd_ = -1, cache_minq_ = 0;
   rfxbamcache::Writer cache_;
+  // set_region
+  bool region_on_ = false, region_quiet_ = false;
+  std::string region_text_, bam_path_;
+  const char* region_index_ = "none";  // none | used | unusable
+  rfxbai::Region region_;
+  uint64_t in_region_ = 0;
   struct KeepBufs {
     std::vector<uint64_t> hash, codes;
     std::vector<uint32_t> start, bytes, len, word_off, good, runs;
@@ -1369,10 +1384,88 @@ class BamIngest {
     if (rc == RFX_E_FORMAT) die(tool_ + ": --bam: " + rfx_last_error());
     if (rc == RFX_E_RANGE) die(tool_ + ": --bam: a record that is longer than an arena");
     if (rc != RFX_OK) die(std::string("rufus_amd: rfx_bam_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
+    if (region_on_) {
+      uint64_t n_in = 0;
+      const int rr = rfx_bam_set_region(t, region_.tid, region_.beg, region_.end, &n_in);
+      if (rr != RFX_OK) die(std::string("rufus_amd: rfx_bam_set_region: ") + rfx_strerror(rr) + " " + rfx_last_error());
+      in_region_ += n_in;
+    }
     return n_records;
   }
 
+  // one whole BGZF block at compressed byte `at` of the file: its compressed and inflated sizes
+  static bool block_at(const char* m, size_t size, uint64_t at, uint64_t* used, uint64_t* inflated) {
+    if (at >= size) return false;
+    uint32_t nb = 0;
+    *used = *inflated = 0;
+    (void)rfx_bgzf_scan(m + at, std::min<size_t>(size - (size_t)at, 1u << 16), 1, &nb, used, inflated);
+    return nb == 1;
+  }
+  // The file range of the region: X.bam.bai, then X.bai.  false: no usable index (one line on stderr), the whole file is
+  // walked.  true: *empty, or the blocks [*start_c, *end_c) with *skip in the first; *stop_in = STOP's offset inside the
+  // last block's inflated data (0: STOP is that block's end), *stop_inf the last block's inflated size.
+  bool region_range(const char* m, size_t size, uint64_t first_block, uint32_t skip0, bool* empty, uint64_t* start_c, uint64_t* skip,
+                    uint64_t* end_c, uint64_t* stop_in, uint64_t* stop_inf) {
+    std::vector<std::string> tries{bam_path_ + ".bai"};
+    if (bam_path_.size() > 4 && bam_path_.compare(bam_path_.size() - 4, 4, ".bam") == 0)
+      tries.push_back(bam_path_.substr(0, bam_path_.size() - 4) + ".bai");
+    std::vector<uint8_t> bytes;
+    std::string found;
+    for (const std::string& path : tries) {
+      FILE* f = fopen(path.c_str(), "rb");
+      if (!f) continue;
+      uint8_t buf[1 << 16];
+      for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) bytes.insert(bytes.end(), buf, buf + n);
+      fclose(f);
+      found = path;
+      break;
+    }
+    if (found.empty()) {
+      if (!region_quiet_) fprintf(stderr, "%s: --region: '%s' has no .bai index: walking the whole file\n", tool_.c_str(), bam_path_.c_str());
+      return false;
+    }
+    auto unusable = [&](const std::string& why) {
+      region_index_ = "unusable";
+      if (!region_quiet_)
+        fprintf(stderr, "%s: --region: '%s' is not a usable BAM index (%s): walking the whole file\n", tool_.c_str(), found.c_str(),
+                why.c_str());
+      return false;
+    };
+    rfxbai::Index ix;
+    std::string why;
+    if (!rfxbai::read_index(bytes.data(), bytes.size(), n_ref_, size, &ix, &why)) return unusable(why);
+    const rfxbai::Range r = rfxbai::query(ix, region_.tid, region_.beg, region_.end);
+    *empty = r.empty;
+    if (!r.empty) {
+      // the two ends name blocks of THIS file, behind its header
+      uint64_t used = 0, inf = 0;
+      *start_c = r.start >> 16;
+      *skip = r.start & 0xFFFFu;
+      if (r.start < ((first_block << 16) | skip0)) return unusable("a chunk in front of the first record");
+      if (!block_at(m, size, *start_c, &used, &inf) || *skip > inf) return unusable("a chunk that starts at no BGZF block");
+      *stop_in = r.stop & 0xFFFFu;
+      *stop_inf = 0;
+      *end_c = r.stop >> 16;
+      if (*stop_in) {
+        if (!block_at(m, size, *end_c, &used, &inf) || *stop_in > inf) return unusable("a chunk that ends at no BGZF block");
+        *end_c += used;
+        *stop_inf = inf;
+      }
+    }
+    region_index_ = "used";
+    return true;
+  }
+
  public:
+  // before feed_mapped: only the records that overlap `text` (rfx_bai.hpp parse_region) are kept; bam_path: the file
+  // feed_mapped is given, whose index is looked for beside it.  quiet: the stderr line about the index is not repeated.
+  void set_region(const std::string& text, const std::string& bam_path, bool quiet = false) {
+    if (!rfx_bam_set_region) die(tool_ + ": this library cannot restrict BAM input to a region");
+    region_on_ = true;
+    region_quiet_ = quiet;
+    region_text_ = text;
+    bam_path_ = bam_path;
+  }
   BamIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, uint32_t exclude_flags, size_t arena_bytes = (size_t)1 << 30,
             size_t piece = 8u << 20)
       : ctx_(ctx), sink_(std::move(sink)), piece_(piece), exclude_(exclude_flags), arena_bytes_(arena_bytes) {
@@ -1435,7 +1528,11 @@ class BamIngest {
     char b[200];
     snprintf(b, sizeof b, "bam route: %llu blocks in %llu appends, %llu arenas, %llu records, %llu reads", (unsigned long long)blocks_,
              (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)records_, (unsigned long long)reads_);
-    return b;
+    if (!region_on_) return b;
+    char r[200];
+    snprintf(r, sizeof r, "; region tid %d [%lld, %lld) index %s: %llu blocks inflated, %llu records in the region", (int)region_.tid,
+             (long long)region_.beg, (long long)region_.end, region_index_, (unsigned long long)blocks_, (unsigned long long)in_region_);
+    return std::string(b) + r;
   }
   // PassThroughSamCheck's side file (src/PassThroughSamCheck.cpp:140-155): its initial `current`, then the RNAME of every
   // run of kept records in file order; refID -1 prints as `*`
@@ -1481,14 +1578,30 @@ class BamIngest {
         at += (size_t)used;
       }
     }
+    // --region: the index's one range of blocks instead of all of them (region_range)
+    bool ranged = false;
+    uint64_t walk_from = first_block, walk_to = size, skip_first = skip0, stop_in = 0, stop_inf = 0;
+    if (region_on_) {
+      std::string why;
+      if (!rfxbai::parse_region(region_text_, ref_names_, &region_, &why)) die(tool_ + ": --region: " + why);
+      bool empty = false;
+      ranged = region_range(m, size, first_block, skip0, &empty, &walk_from, &skip_first, &walk_to, &stop_in, &stop_inf);
+      if (ranged && empty) return;  // no chunk: no arena, the outputs of an empty input
+      if (!ranged) {
+        walk_from = first_block;
+        walk_to = size;
+        skip_first = skip0;
+      }
+    }
     // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of inflated bytes
     struct Run { size_t at, n; uint64_t inflated; };
     std::vector<Run> runs;
     const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
-    for (size_t at = (size_t)first_block; at < size;) {
+    uint64_t range_inflated = 0;
+    for (size_t at = (size_t)walk_from; at < (size_t)walk_to;) {
       uint32_t nb = 0;
       uint64_t used = 0, inf = 0;
-      rc = rfx_bgzf_scan(m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
+      rc = rfx_bgzf_scan(m + at, std::min((size_t)walk_to - at, buf_cap_), max_blocks, &nb, &used, &inf);
       if (nb == 0) {
         char msg[128];
         snprintf(msg, sizeof msg, "%s BGZF block at byte %llu of the compressed input", rc == RFX_OK ? "truncated" : "no",
@@ -1497,8 +1610,12 @@ class BamIngest {
       }
       runs.push_back({at, (size_t)used, inf});
       blocks_ += nb;
+      range_inflated += inf;
       at += (size_t)used;
     }
+    if (ranged && runs.empty()) return;
+    // STOP as an offset in the inflated bytes of the range (the first arena's byte 0 = the first block's)
+    const uint64_t stop_stream = stop_in ? range_inflated - stop_inf + stop_in : range_inflated;
     int cur = 0;
     size_t i = 0;
     // queues runs into arena `a` until the next does not fit (false: the file is at its end)
@@ -1518,7 +1635,7 @@ class BamIngest {
       }
       return false;
     };
-    uint64_t skip = skip0;
+    uint64_t skip = skip_first;
     bool more = fill(arena_[cur]);
     while (more) {
       rfx_text* t = arena_[cur];
@@ -1534,6 +1651,16 @@ class BamIngest {
       cur ^= 1;
     }
     uint64_t carried = 0;
+    if (ranged) {  // the tail goes to the other arena (empty: reset behind its last parse) and is dropped with it
+      rfx_text* t = arena_[cur];
+      rfx_text* nx = arena_[cur ^ 1];
+      const uint64_t n_records = settle(t, nx, skip, &carried);
+      if (carried && base + rfx_text_bytes(t) < stop_stream)
+        die(tool_ + ": --bam: --region: the index's range ends inside a record that starts in front of its end");
+      parse_and_sink(t, n_records, base);
+      rfx_text_reset(nx);
+      return;
+    }
     const uint64_t n_records = settle(arena_[cur], nullptr, skip, &carried);  // (a tail: the file ends inside a record)
     parse_and_sink(arena_[cur], n_records, base);
   }
@@ -1818,6 +1945,7 @@ class BamPairFilter {
   std::vector<uint8_t> out_;
   rfxsam::BamPairTail tail_;
   uint64_t arenas_ = 0, records_ = 0, reads_ = 0, names_ = 0, passes_ = 0;
+  std::string region_, bam_path_, ingest_counts_;  // set_region: both passes are BamIngest's ranged walk
   static constexpr const char* TOOL = "rufus_amd RUFUS.Filter";
 
   [[noreturn]] static void fail(const char* what) { die(std::string(TOOL) + ": --bam: " + what + ": " + rfx_last_error()); }
@@ -1873,6 +2001,7 @@ class BamPairFilter {
   void pass(const char* m, size_t size, rfx_nameset* names) {
     BamIngest in(ctx_, nullptr, exclude_, arena_bytes_, piece_);
     uint64_t base = 0;
+    if (!region_.empty()) in.set_region(region_, bam_path_, /*quiet=*/names != nullptr);
     in.set_per_arena(
         [&](rfx_text* t, uint64_t n_records) {
           const uint64_t n = names ? pull_arena(t, n_records, base, names) : scan_arena(in, t, n_records, base);
@@ -1886,6 +2015,7 @@ class BamPairFilter {
       records_ = in.records();
       reads_ = in.reads();
       chr_log_ = in.chr_log();
+      ingest_counts_ = in.counts();
     } else if (in.records() != records_ || in.reads() != reads_) {
       die(std::string(TOOL) + ": --bam: the two passes saw different records");
     }
@@ -1899,6 +2029,12 @@ class BamPairFilter {
     if (!rfx_bam_parse_filter || !rfx_bam_name_hashes || !rfx_nameset_build || !rfx_nameset_size || !rfx_nameset_free ||
         !rfx_bam_mark_names || !rfx_bam_gather)
       die(std::string(TOOL) + ": this library cannot read BAM input");
+  }
+  // before run(): only the records that overlap the region take part -- in the scan, in the log and in the pairing by name,
+  // as behind `samtools view X.bam REG`, where a mate outside the region never reaches the filter
+  void set_region(const std::string& text, const std::string& bam_path) {
+    region_ = text;
+    bam_path_ = bam_path;
   }
   // A whole mapped BAM file.  Dies where BamIngest does.  Afterwards mate1() / mate2() hold the two output files' bytes and
   // chr_log() the chromosome log's lines.
@@ -1923,7 +2059,7 @@ class BamPairFilter {
              (unsigned long long)arenas_, (unsigned long long)records_, (unsigned long long)reads_,
              (unsigned long long)hit_index_.size(), (unsigned long long)names_, (unsigned long long)tail_.records,
              (unsigned long long)tail_.walk.n_found);
-    return b;
+    return region_.empty() ? std::string(b) : std::string(b) + " | " + ingest_counts_;
   }
 };
 

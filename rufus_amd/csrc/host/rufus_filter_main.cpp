@@ -505,6 +505,9 @@ static int run_packed(int argc, char** argv) {
     printf("ERROR: expected 10 arguments\n");
     return 0;
   }
+  for (int a = 11; a < argc; ++a)
+    if (strcmp(argv[a], "--region") == 0)
+      die("rufus_amd RUFUS.Filter: --region does not go with --packed: the cache does not record a region (use --bam)");
   {
     uint64_t magic = 0;
     const int cfd = ::open(argv[2], O_RDONLY);
@@ -688,7 +691,7 @@ static int run_packed(int argc, char** argv) {
 // not used: no host thread parses anything.
 namespace bamf {
 static int run(int argc, char** argv) {
-  printf("Call is --bam CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads [--bam-exclude N]\n");
+  printf("Call is --bam CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads [--bam-exclude N] [--region REG]\n");
   if (argc < 10) {
     printf("ERROR: expected 9 arguments\n");
     return 0;
@@ -697,9 +700,13 @@ static int run(int argc, char** argv) {
   const std::string stub = argv[5];
   const int k = atoi(argv[6]), min_q = atoi(argv[7]), thresh = atoi(argv[8]);
   uint32_t exclude = 3328;
+  const char* region = nullptr;  // --region REG: `samtools view -F N X.bam REG` in front of both passes (BamIngest::set_region)
   for (int a = 10; a < argc; ++a) {
     if (strcmp(argv[a], "--bam-exclude") == 0 && a + 1 < argc) exclude = (uint32_t)strtoul(argv[++a], nullptr, 0);
-    else die(std::string("rufus_amd RUFUS.Filter: --bam: unknown argument ") + argv[a]);
+    else if (strcmp(argv[a], "--region") == 0 && a + 1 < argc) {
+      if (region) die("rufus_amd RUFUS.Filter: --bam: --region given twice: one region per run");
+      region = argv[++a];
+    } else die(std::string("rufus_amd RUFUS.Filter: --bam: unknown argument ") + argv[a]);
   }
   std::string text;
   {
@@ -748,6 +755,7 @@ static int run(int argc, char** argv) {
   if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
   {
     BamPairFilter route(ctx, set, min_q, thresh, exclude, arena, piece);
+    if (region) route.set_region(region, bam);
     route.run((const char*)m, (size_t)sb.st_size);
     for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
     fclose(chr);

@@ -21,6 +21,10 @@
 //   k_bam_starts   a lane per tile walks once more and writes rec_start[]; every record on the chain is checked with
 //                  bam_valid, the lowest failing offset kept (atomicMin)
 //
+// rfx_bam_set_region (`samtools view X.bam CHR:BEG-END`, runRufus.sh -R):
+//   k_bam_region   a thread per record: bam_in_region -> a byte per record that lives with rec_start[]; every kernel below
+//                  that asks "kept?" asks bam_kept (rfx_bam_core.h): the flag test, and that byte while it is set
+//
 // rfx_bam_parse, shaped as rfx_select.hip:
 //   k_bam_fields   a thread per record: flag, l_seq -> keep, code words, bases  -> three scans
 //                  (+ the longest kept read and the histogram of lengths < 32: atomics on 33 counters)
@@ -137,14 +141,34 @@ __global__ __launch_bounds__(256) void k_bam_starts(const uint8_t* __restrict__ 
   if (guess[t] != in[t]) atomicAdd(&info[1], 1u);
 }
 
+// ---- rfx_bam_set_region -------------------------------------------------------------------------------------------------
+// A thread per record: keep[r] = bam_in_region (a byte each; r < n_rec, the array's size).  *n_in: a ballot per wave, one
+// 32-bit add of its population by lane 0 (an arena holds fewer than 2^30 records).  The loop's trip count is wave-uniform
+// (it runs over the wave's first record), so every lane of a wave reaches the ballot.
+__global__ __launch_bounds__(256) void k_bam_region(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
+                                                     uint64_t n_rec, int32_t tid, int64_t beg, int64_t end,
+                                                     uint8_t* __restrict__ keep, uint32_t* __restrict__ n_in) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t r0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); r0 < n_rec; r0 += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = r0 + lane;
+    bool in = false;
+    if (r < n_rec) {
+      in = bam_in_region(b, rec_start[r], tid, beg, end);
+      keep[r] = in;
+    }
+    const unsigned long long vote = __ballot(in);
+    if (lane == 0 && vote) atomicAdd(n_in, (uint32_t)__popcll(vote));
+  }
+}
+
 // ---- rfx_bam_parse ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_bam_fields(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
-                                                     uint64_t n_rec, uint32_t exclude, uint64_t* __restrict__ cnt,
+                                                     uint64_t n_rec, uint32_t exclude, const uint8_t* __restrict__ region, uint64_t* __restrict__ cnt,
                                                      uint64_t* __restrict__ words, uint64_t* __restrict__ bases,
                                                      unsigned int* __restrict__ d_stat) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t p = rec_start[r];
-    const bool keep = (bam_flag(b, p) & exclude) == 0;
+    const bool keep = bam_kept(b, p, exclude, region, r);
     const uint32_t len = max((uint32_t)bam_l_seq(b, p), 1u);  // (>= 0: rfx_bam_settle has checked every record; 0: SEQ is `*`)
     cnt[r] = keep;
     words[r] = keep ? (len + 31u) / 32u : 0u;
@@ -157,13 +181,13 @@ __global__ __launch_bounds__(256) void k_bam_fields(const uint8_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(256) void k_bam_table(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
-                                                    uint64_t n_rec, uint32_t exclude, const uint64_t* __restrict__ cnt,
+                                                    uint64_t n_rec, uint32_t exclude, const uint8_t* __restrict__ region, const uint64_t* __restrict__ cnt,
                                                     const uint64_t* __restrict__ words, uint32_t* __restrict__ out_len,
                                                     uint32_t* __restrict__ out_word_off, uint32_t* __restrict__ seq_at,
                                                     int32_t* __restrict__ ref_id) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t p = rec_start[r];
-    if (bam_flag(b, p) & exclude) continue;
+    if (!bam_kept(b, p, exclude, region, r)) continue;
     const uint32_t o = (uint32_t)cnt[r];  // (both totals are below 2^32: checked before this launch)
     const uint32_t l_seq = (uint32_t)bam_l_seq(b, p);
     out_len[o] = max(l_seq, 1u);  // (no sequence: samtools view prints `*`, one base that is none of ACGT)
@@ -252,6 +276,7 @@ int rfx_bam_settle(rfx_text* t, rfx_text* next, uint64_t skip, int32_t n_ref, ui
   if (skip > n) return RFX_E_INVAL;
   rfxi::text_bam& slot = rfxi::text_bam_of(t);
   if (slot.rec_start) dfree(c, slot.rec_start);
+  if (slot.region) dfree(c, slot.region);
   slot = rfxi::text_bam();
   memset(c->bam_stats, 0, sizeof c->bam_stats);
   if (n == 0) {
@@ -366,6 +391,55 @@ int rfx_bam_stats(const rfx_ctx* c, uint64_t out[4]) {
   return RFX_OK;
 }
 
+int rfx_bam_set_region(rfx_text* t, int32_t tid, int64_t beg, int64_t end, uint64_t* n_in) {
+  static const char* const who = "rfx_bam_set_region";
+  if (n_in) *n_in = 0;
+  if (!t || !n_in) return RFX_E_INVAL;
+  rfxi::text_bam& slot = rfxi::text_bam_of(t);
+  if (!slot.settled) {
+    rfxi::set_error("rfx_bam_set_region: the arena has not been settled with rfx_bam_settle since its last reset");
+    return RFX_E_INVAL;
+  }
+  rfx_ctx* c = nullptr;
+  const uint8_t* arena = nullptr;
+  uint64_t n = 0;
+  if (const int rc = rfxi::text_ready(t, &c, &arena, &n)) return rc;
+  const uint64_t R = slot.n_records;
+  if (slot.region) dfree(c, slot.region);
+  slot.region = nullptr;
+  uint8_t* keep = (uint8_t*)dmalloc(c, std::max<uint64_t>(R, 1));
+  uint32_t* d_in = (uint32_t*)dmalloc(c, 4);
+  if (!keep || !d_in) {
+    dfree(c, keep);
+    dfree(c, d_in);
+    rfxi::set_error("rfx_bam_set_region: out of device memory");
+    return RFX_E_NOMEM;
+  }
+  if (R == 0) {
+    dfree(c, d_in);
+    slot.region = keep;
+    return RFX_OK;
+  }
+  uint32_t h_in = 0;
+  hipError_t e = hipMemsetAsync(d_in, 0, 4, c->stream);
+  if (e == hipSuccess) {
+    rfx_span sp(c, "k_bam_region");
+    const dim3 grid((unsigned)std::min<uint64_t>((R + 255) / 256, (uint64_t)c->n_cu * 16));
+    hipLaunchKernelGGL(k_bam_region, grid, dim3(256), 0, c->stream, arena, (const uint32_t*)slot.rec_start, R, tid, beg, end, keep, d_in);
+    e = queue_read(c, &h_in, d_in, 4);
+  }
+  if (e == hipSuccess) e = rfxi::sync(c);
+  else (void)rfxi::sync(c);  // (a queued read-back points at h_in: deliver it now)
+  dfree(c, d_in);
+  if (e != hipSuccess) {
+    dfree(c, keep);
+    return hip_fail(e, who);
+  }
+  slot.region = keep;
+  *n_in = h_in;
+  return RFX_OK;
+}
+
 rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs, uint64_t cap, uint64_t* n_runs) {
   static const char* const who = "rfx_bam_parse";
   char msg[256];
@@ -415,7 +489,7 @@ rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs
     if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
     {
       rfx_span sp(c, "k_bam_fields");
-      hipLaunchKernelGGL(k_bam_fields, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+      hipLaunchKernelGGL(k_bam_fields, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, (const uint8_t*)slot.region, cnt, words,
                          bases, d_stat);
     }
     rfxk::scan_tail(c, cnt, R);
@@ -451,7 +525,7 @@ rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs
   if (S) {
     {
       rfx_span sp(c, "k_bam_table");
-      hipLaunchKernelGGL(k_bam_table, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+      hipLaunchKernelGGL(k_bam_table, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, (const uint8_t*)slot.region, cnt, words,
                          r->len, r->word_off, seq_at, ref_id);
     }
     {
@@ -507,12 +581,12 @@ rfx_reads* rfx_bam_parse(rfx_text* t, uint32_t exclude_flags, uint32_t* ref_runs
 namespace {
 
 __global__ __launch_bounds__(256) void k_bamf_fields(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
-                                                      uint64_t n_rec, uint32_t exclude, uint64_t* __restrict__ cnt,
+                                                      uint64_t n_rec, uint32_t exclude, const uint8_t* __restrict__ region, uint64_t* __restrict__ cnt,
                                                       uint64_t* __restrict__ words, uint64_t* __restrict__ bases,
                                                       unsigned int* __restrict__ d_stat) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t p = rec_start[r];
-    const bool keep = (bam_flag(b, p) & exclude) == 0;
+    const bool keep = bam_kept(b, p, exclude, region, r);
     const uint32_t len = keep ? bam_filter_len(b, p) : 0u;
     cnt[r] = keep;
     words[r] = (len + 31u) / 32u;
@@ -526,13 +600,13 @@ __global__ __launch_bounds__(256) void k_bamf_fields(const uint8_t* __restrict__
 
 // (cnt, words: scanned; bases: scanned too, so a record's length is the difference of two entries)
 __global__ __launch_bounds__(256) void k_bamf_table(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
-                                                     uint64_t n_rec, uint32_t exclude, const uint64_t* __restrict__ cnt,
+                                                     uint64_t n_rec, uint32_t exclude, const uint8_t* __restrict__ region, const uint64_t* __restrict__ cnt,
                                                      const uint64_t* __restrict__ words, const uint64_t* __restrict__ bases,
                                                      uint32_t* __restrict__ out_len, uint32_t* __restrict__ out_word_off,
                                                      uint32_t* __restrict__ rec_at, int32_t* __restrict__ ref_id) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t p = rec_start[r];
-    if (bam_flag(b, p) & exclude) continue;
+    if (!bam_kept(b, p, exclude, region, r)) continue;
     const uint32_t o = (uint32_t)cnt[r];  // (both totals are below 2^32: checked before this launch)
     out_len[o] = (uint32_t)(bases[r + 1] - bases[r]);
     out_word_off[o] = (uint32_t)words[r];
@@ -556,9 +630,9 @@ __global__ __launch_bounds__(256) void k_bamf_pack(const uint8_t* __restrict__ b
 }
 
 __global__ __launch_bounds__(256) void k_bam_keep(const uint8_t* __restrict__ b, const uint32_t* __restrict__ rec_start,
-                                                   uint64_t n_rec, uint32_t exclude, uint64_t* __restrict__ cnt) {
+                                                   uint64_t n_rec, uint32_t exclude, const uint8_t* __restrict__ region, uint64_t* __restrict__ cnt) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * blockDim.x)
-    cnt[r] = (bam_flag(b, rec_start[r]) & exclude) == 0;
+    cnt[r] = bam_kept(b, rec_start[r], exclude, region, r);
 }
 
 __global__ __launch_bounds__(256) void k_bam_kept_at(const uint32_t* __restrict__ rec_start, uint64_t n_rec,
@@ -763,7 +837,7 @@ int kept_of(rfx_text* t, uint32_t exclude, const char* who, kept_view* v) {
   const dim3 grid((unsigned)std::min<uint64_t>((R + 255) / 256, (uint64_t)c->n_cu * 16));
   {
     rfx_span sp(c, "k_bam_keep");
-    hipLaunchKernelGGL(k_bam_keep, grid, dim3(256), 0, c->stream, v->arena, slot.rec_start, R, exclude, cnt);
+    hipLaunchKernelGGL(k_bam_keep, grid, dim3(256), 0, c->stream, v->arena, slot.rec_start, R, exclude, (const uint8_t*)slot.region, cnt);
   }
   rfxk::scan_tail(c, cnt, R);
   hipError_t e = queue_read(c, &v->n_kept, cnt + R, 8);
@@ -849,7 +923,7 @@ rfx_reads* rfx_bam_parse_filter(rfx_text* t, uint32_t exclude_flags, int min_q, 
     if (e != hipSuccess) return fail(e, "RFX_E_HIP", "");
     {
       rfx_span sp(c, "k_bamf_fields");
-      hipLaunchKernelGGL(k_bamf_fields, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+      hipLaunchKernelGGL(k_bamf_fields, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, (const uint8_t*)slot.region, cnt, words,
                          bases, d_stat);
     }
     rfxk::scan_tail(c, cnt, R);
@@ -885,7 +959,7 @@ rfx_reads* rfx_bam_parse_filter(rfx_text* t, uint32_t exclude_flags, int min_q, 
   if (S) {
     {
       rfx_span sp(c, "k_bamf_table");
-      hipLaunchKernelGGL(k_bamf_table, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, cnt, words,
+      hipLaunchKernelGGL(k_bamf_table, grid_of(R, 16), dim3(256), 0, c->stream, arena, slot.rec_start, R, exclude_flags, (const uint8_t*)slot.region, cnt, words,
                          bases, r->len, r->word_off, rec_at, ref_id);
     }
     {

@@ -128,6 +128,34 @@ RFX_BAM_HD bool bam_guess_ok(const uint8_t* b, uint64_t c, uint64_t end, int32_t
   return true;
 }
 
+// ---- the region test of `samtools view X.bam CHR:BEG-END` (rfx_bam_set_region) ----------------------------------------
+// Both run on a record bam_valid accepts: its cigar lies inside the record, and every byte is read through bam_u8.
+// bam_end_pos: pos + rlen in 64 bits, rlen = the lengths of the M, D, N, = and X operations (codes 0, 2, 3, 7, 8: the mask
+// 0x18D) added up; 1 for an unmapped record (flag 4), one without an operation and one whose operations consume nothing.
+// n_cigar_op <= 65535 and a length < 2^28, so the sum stays below 2^44.
+RFX_BAM_HD int64_t bam_end_pos(const uint8_t* b, uint64_t p) {
+  const int64_t pos = bam_pos(b, p);
+  const uint32_t n_op = bam_n_cigar_op(b, p);
+  if ((bam_flag(b, p) & 4u) || n_op == 0) return pos + 1;
+  const uint64_t cigar = p + BAM_FIXED + bam_l_read_name(b, p);
+  int64_t rlen = 0;
+  for (uint32_t i = 0; i < n_op; ++i) {
+    const uint32_t v = bam_u32(b, cigar + 4ull * i);
+    if ((0x18Du >> (v & 15u)) & 1u) rlen += (int64_t)(v >> 4);
+  }
+  return pos + (rlen ? rlen : 1);
+}
+// the record overlaps [beg, end) of reference tid
+RFX_BAM_HD bool bam_in_region(const uint8_t* b, uint64_t p, int32_t tid, int64_t beg, int64_t end) {
+  if (bam_ref_id(b, p) != tid || (int64_t)bam_pos(b, p) >= end) return false;
+  return bam_end_pos(b, p) > beg;
+}
+// What every kernel of rfx_bam.hip calls a KEPT record r (at offset p): none of the excluded flags, and -- while the arena
+// has a region (region != NULL: rfx_bam_set_region's byte per record) -- inside it.
+RFX_BAM_HD bool bam_kept(const uint8_t* b, uint64_t p, uint32_t exclude, const uint8_t* region, uint64_t r) {
+  return (bam_flag(b, p) & exclude) == 0 && (!region || region[r] != 0);
+}
+
 // One tile's walk: from `in` along bam_next until the offset is >= limit (the tile's end) or the chain ends.  Returns
 // where it stands and adds the whole records it passed -- they START in [in, limit) -- to *count.  An entry that already
 // lies behind the limit is passed through.  visit(p): called for every record passed (the kernels write and check it).

@@ -19,6 +19,7 @@
 #include "../../include/rufus_hip.h"
 #include "rfx_synth.h"
 #include "rfx_bgzf_core.h"
+#include "host/rfx_bai.hpp"
 
 namespace {
 
@@ -291,6 +292,53 @@ int rfx_bam_header(const void* buf, uint64_t n, int* complete, int32_t* n_ref, c
     text_at.push_back(was);
     at += bsize;
   }
+}
+
+namespace {
+void copy_why(const std::string& why, char* out, uint64_t cap) {
+  if (!out || !cap) return;
+  const size_t n = std::min<size_t>(why.size(), (size_t)cap - 1);
+  memcpy(out, why.data(), n);
+  out[n] = 0;
+}
+}  // namespace
+
+int rfx_bam_region_parse(const char* text, const char* names, uint64_t names_bytes, int32_t* tid, int64_t* beg, int64_t* end,
+                         char* why, uint64_t why_cap) {
+  if (!text || (!names && names_bytes) || !tid || !beg || !end) return RFX_E_INVAL;
+  std::vector<std::string> refs;
+  for (uint64_t at = 0; at < names_bytes;) {  // (each name with its NUL; a last one without: up to the end)
+    const void* nul = memchr(names + at, 0, (size_t)(names_bytes - at));
+    const uint64_t len = nul ? (uint64_t)((const char*)nul - (names + at)) : names_bytes - at;
+    refs.emplace_back(names + at, (size_t)len);
+    at += len + 1;
+  }
+  rfxbai::Region r;
+  std::string msg;
+  if (!rfxbai::parse_region(text, refs, &r, &msg)) {
+    copy_why(msg, why, why_cap);
+    return RFX_E_FORMAT;
+  }
+  *tid = r.tid;
+  *beg = r.beg;
+  *end = r.end;
+  return RFX_OK;
+}
+
+int rfx_bai_query(const void* bai, uint64_t n, int32_t n_ref, uint64_t bam_size, int32_t tid, int64_t beg, int64_t end, int* empty,
+                  uint64_t* start, uint64_t* stop, char* why, uint64_t why_cap) {
+  if ((!bai && n) || !empty || !start || !stop) return RFX_E_INVAL;
+  rfxbai::Index ix;
+  std::string msg;
+  if (!rfxbai::read_index((const uint8_t*)bai, (size_t)n, n_ref, bam_size, &ix, &msg)) {
+    copy_why(msg, why, why_cap);
+    return RFX_E_FORMAT;
+  }
+  const rfxbai::Range r = rfxbai::query(ix, tid, beg, end);
+  *empty = r.empty;
+  *start = r.start;
+  *stop = r.stop;
+  return RFX_OK;
 }
 
 int rfx_jf_matrix(int lsize, int k, uint64_t* cols) {

@@ -581,9 +581,11 @@ hipError_t text_line_starts(rfx_ctx*, const uint8_t* arena, uint64_t n, const ui
 // what lay behind moves, device to device, to the front of `next` (empty, of the same ctx: the caller has checked);
 // next == NULL with a tail is RFX_E_FORMAT "<who>: the text ends inside a record", a tail beyond next's capacity
 // RFX_E_RANGE.  text_bam_of: the record starts rfx_bam_settle found (device, n_records + 1 entries, the last one the
-// cut; allocated with dmalloc), which belong to the arena: rfx_text_reset and rfx_text_close free them.
+// cut; allocated with dmalloc) and the region bytes of rfx_bam_set_region, which belong to the arena: rfx_text_reset and
+// rfx_text_close free them.
 struct text_bam {
   uint32_t* rec_start = nullptr;
+  uint8_t* region = nullptr;  // rfx_bam_set_region: a byte per record, 1 = inside the region (dmalloc); NULL: no region
   uint64_t n_records = 0;
   int32_t n_ref = 0;
   bool settled = false;

@@ -411,6 +411,7 @@ void rfx_text_close(rfx_text* t) {
     (void)hipFree(t->first_bad);
   }
   dfree(t->ctx, t->bam.rec_start);
+  dfree(t->ctx, t->bam.region);
   for (auto& ch : t->stage) (void)hipFree(ch.p);
   for (hipEvent_t e : t->ev) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(t->copy);
@@ -487,6 +488,7 @@ void rfx_text_reset(rfx_text* t) {
   t->n_ev = 0;
   t->used = 0;
   if (t->bam.rec_start) dfree(t->ctx, t->bam.rec_start);
+  if (t->bam.region) dfree(t->ctx, t->bam.region);
   t->bam = rfxi::text_bam();
   if (t->n_bgzf_blocks) {
     if (t->stage.size() > 1) {  // one chunk of the size that was needed, next time

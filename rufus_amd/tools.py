@@ -175,15 +175,32 @@ def is_bam(data: bytes) -> bool:
         return False
 
 
-def _bam_arenas(ctx: capi.Context, data: bytes, arena_bytes: int):
+def _bam_arenas(ctx: capi.Context, data: bytes, arena_bytes: int, region=None, index: bytes | None = None):
     """The settled arenas of a BAM file, one after the other: yields (arena, whole records, header).  The arena is reset
-    when the caller comes back for the next."""
+    when the caller comes back for the next.  region (`samtools view X.bam REGION`): every arena gets bam_set_region before
+    it is handed out; with `index` (the .bai file's bytes) only the blocks of capi.bai_query's range are inflated, without it
+    all of them."""
     hdr = capi.bam_header(data)
     if hdr is None:
         raise ValueError("the BAM header is not whole")
+    at, skip, stop_at, reg = hdr["first_block"], hdr["skip"], len(data), None
+    if region is not None:
+        reg = capi.bam_region_parse(region, hdr["names"])
+        if index is not None:
+            rng = capi.bai_query(index, hdr["n_ref"], len(data), *reg)
+            if rng is None:
+                return
+            at, skip, stop_at = rng[0] >> 16, rng[0] & 0xFFFF, rng[1] >> 16
+            if rng[1] & 0xFFFF:  # STOP lies inside a block: that block is the last
+                nb, used, _ = capi.bgzf_scan(data[stop_at:stop_at + 65536], 1)
+                if nb != 1:
+                    raise ValueError(f"no whole BGZF block at byte {stop_at} of the BAM file")
+                stop_at += used
+    ranged = stop_at != len(data) or at != hdr["first_block"]
+    data = data[:stop_at]
     arenas = [capi.TextArena(ctx, arena_bytes), capi.TextArena(ctx, arena_bytes)]
     try:
-        at, cur, skip = hdr["first_block"], 0, hdr["skip"]
+        cur = 0
         while True:
             a = arenas[cur]
             while at < len(data) and a.bytes + 65536 <= arena_bytes:
@@ -193,11 +210,16 @@ def _bam_arenas(ctx: capi.Context, data: bytes, arena_bytes: int):
                 a.append_bgzf(data[at:at + used])
                 at += used
             last = at >= len(data)
-            n, _ = a.bam_settle(None if last else arenas[cur ^ 1], skip, hdr["n_ref"])
+            # (a range's last block holds whatever follows the region: its cut record goes to the other arena and is dropped)
+            n, _ = a.bam_settle(None if last and not ranged else arenas[cur ^ 1], skip, hdr["n_ref"])
             skip = 0
+            if reg is not None:
+                a.bam_set_region(*reg)
             if n:
                 yield a, n, hdr
             a.reset()
+            if last:
+                arenas[cur ^ 1].reset()
             if last:
                 break
             cur ^= 1
@@ -206,30 +228,37 @@ def _bam_arenas(ctx: capi.Context, data: bytes, arena_bytes: int):
             a.close()
 
 
-def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, arena_bytes: int = 256 << 20):
+def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, arena_bytes: int = 256 << 20, region=None,
+                    index: bytes | None = None):
     """The records of a BAM file with flag & exclude_flags == 0 as count blocks, an arena at a time: yields (block, runs,
     reference names) -- what `samtools view -F 3328 X.bam | PassThroughSamCheck` hands the counter, found and packed on the
-    device (capi.bam_header, TextArena.append_bgzf / bam_settle / bam_parse).  The caller frees the blocks."""
-    for a, _, hdr in _bam_arenas(ctx, data, arena_bytes):
+    device (capi.bam_header, TextArena.append_bgzf / bam_settle / bam_parse).  region, index: `samtools view X.bam REGION`
+    (_bam_arenas).  The caller frees the blocks."""
+    for a, _, hdr in _bam_arenas(ctx, data, arena_bytes, region, index):
         blk, runs = a.bam_parse(exclude_flags)
         yield blk, runs, hdr["names"]
 
 
 def jellyfish_count(ctx: capi.Context, inputs, k: int, size: int, canonical: bool = True, lower: int = 0,
                     upper: int = 2**64 - 1, out: str | None = None, capacity: int = 0, argv=(),
-                    mode: int = capi.COUNT_AUTO) -> JhashFile:
-    """Count the k-mers of FASTA/FASTQ files (paths or bytes); a BAM file is counted as `samtools view -F 3328` of it."""
+                    mode: int = capi.COUNT_AUTO, region=None, index: bytes | None = None) -> JhashFile:
+    """Count the k-mers of FASTA/FASTQ files (paths or bytes); a BAM file is counted as `samtools view -F 3328` of it, with
+    `region` as `samtools view -F 3328 X.bam REGION` (ONE BAM input; index: its .bai's bytes, or None for the whole walk)."""
+    if region is not None and len(inputs) != 1:
+        raise ValueError("region goes with ONE BAM input")
     table = capi.CountTable(ctx, k, size, canonical, capacity, mode=mode)
     try:
         for src in inputs:
             data = src if isinstance(src, (bytes, bytearray)) else open(src, "rb").read()
             if is_bam(bytes(data)):
-                for block, _, _ in bam_read_blocks(ctx, bytes(data)):
+                for block, _, _ in bam_read_blocks(ctx, bytes(data), region=region, index=index):
                     try:
                         table.add(block)
                     finally:
                         block.free()
                 continue
+            if region is not None:
+                raise ValueError("region goes with a BAM input: only a BAM's records carry a position")
             seqs = parse_sequences(bytes(data))
             block = ctx.upload(capi.PackedReads.from_reads(seqs, flags=capi.PACK_COUNT))
             try:
@@ -403,16 +432,16 @@ def _bam_printed(rec: bytes):
 
 
 def filter_bam(ctx: capi.Context, data: bytes, hash_list: bytes, k: int, min_q: int, thresh: int, exclude_flags: int = 3328,
-               arena_bytes: int = 256 << 20):
+               arena_bytes: int = 256 << 20, region=None, index: bytes | None = None):
     """``RUFUS.Filter --bam`` on the bytes of a BAM file: (Mate1 bytes, Mate2 bytes, chromosome log) -- what `samtools view
     -F exclude_flags | PassThroughSamCheck.stranded | RUFUS.Filter` writes.  Two passes, both on the device: the scan of
     every kept record in its stranded form (TextArena.bam_parse_filter, MutantSet.filter, bam_name_hashes of the hits),
     then the pull of every record of a hit name (NameSet, bam_mark_names, bam_gather); the few pulled records are printed
-    and paired by name here."""
+    and paired by name here.  region, index: both passes as `samtools view -F exclude_flags X.bam REGION` (_bam_arenas)."""
     mset = capi.MutantSet(ctx, capi.hashlist_keys(hash_list, k, single_end=False), k)
     hit_index, hit_hash, refs, names, base = [], [], [], [], 0
     try:
-        for a, _, hdr in _bam_arenas(ctx, data, arena_bytes):
+        for a, _, hdr in _bam_arenas(ctx, data, arena_bytes, region, index):
             names = hdr["names"]
             blk, runs = a.bam_parse_filter(min_q, exclude_flags)
             try:
@@ -439,7 +468,7 @@ def filter_bam(ctx: capi.Context, data: bytes, hash_list: bytes, k: int, min_q: 
     hits, waiting, out1, out2, base = set(hit_index), {}, [], [], 0
     nset = capi.NameSet(ctx, np.concatenate(hit_hash))
     try:
-        for a, _, _ in _bam_arenas(ctx, data, arena_bytes):
+        for a, _, _ in _bam_arenas(ctx, data, arena_bytes, region, index):
             mask, n_kept, n_marked = a.bam_mark_names(nset, exclude_flags)
             if n_marked:
                 blob, p = a.bam_gather(mask, n_kept, exclude_flags), 0
