@@ -430,6 +430,32 @@ int rfx_bam_fetch(rfx_text* t, const uint32_t* start, const uint32_t* bytes, uin
                   uint64_t* out_bytes);
 int rfx_nameset_mark(const rfx_nameset*, const uint64_t* hashes, uint64_t n, uint64_t* mask_out, uint64_t* n_marked);
 
+/* -------------------------------------------------------------------------------------------
+ * BAM in, for the single-end filter: the hit records of an arena, with their hit counts, in one call
+ * Replaces the single-end read pull, `samtools view -F 3328 X.bam | PassThroughSamCheck.stranded.se CHR |
+ * RUFUS.Filter.single HashList stdin ...` (runRufus.sh:1031-1032).  Nothing is paired by name there: the feeder prints
+ * a record (src/PassThroughSamCheck.stranded.se.cpp:155-203, the same switch as the paired stranded feeder's), the filter
+ * counts its windows in the set (src/RUFUS.Filter.ss.cpp:164-193; `i < length()`: the last base IS examined, which is
+ * last_base_skipped = 0) and writes the record with ":MH<count>" when the count reaches the threshold (:194-203).  What
+ * becomes of a record depends on that record alone, so one pass over the file is exact.
+ *
+ * rfx_bam_gather_hits: t is an arena settled by rfx_bam_settle, with or without rfx_bam_set_region; block is the filter
+ * block rfx_bam_parse_filter made of that arena in that state with the same exclude_flags -- block->n must be the
+ * arena's number of kept records (RFX_E_INVAL); the arena, the set and the block must belong to one context
+ * (RFX_E_INVAL).  The block is scanned by the filter in its counting mode (every read by itself), and kept record i is
+ * SELECTED when (int)count[i] >= thresh; thresh <= 0 selects every kept record, as the reference's `>=` does.  For the
+ * selected records, ascending: host_out = their bytes from the block_size field to the record's end, concatenated
+ * (rfx_bam_gather's form); hits_out[j] = the count of the j-th selected record; index_out[j] (may be NULL) = its kept
+ * index in this arena.  *bytes and *n_selected are set once the sizes are known; *bytes > cap or *n_selected > sel_cap:
+ * RFX_E_RANGE with both set and nothing written -- the caller grows its buffers and calls again.  An arena without a kept
+ * record and an empty selection are valid.  The error texts begin with the function's name.  Behind the wait that finds
+ * the kept records (as in rfx_bam_gather) there are two waits for the device: for the sizes, and for the copies of the
+ * result.  Neither the per-read counts nor a mask cross to the host.
+ * ------------------------------------------------------------------------------------------- */
+int rfx_bam_gather_hits(rfx_text* t, uint32_t exclude_flags, rfx_set* set, const rfx_reads* block, int thresh, int last_base_skipped,
+                        void* host_out, uint64_t cap, uint64_t* bytes, uint32_t* hits_out, uint32_t* index_out, uint64_t sel_cap,
+                        uint64_t* n_selected);
+
 /* Synthetic trio workload (BASELINE.json configs[1]-[4]) -- benchmark and scale-test input,
  * not a replacement of any reference code.  Every base is a pure function of (parameters, pair, mate, base
  * index) -- see rufus_amd/csrc/rfx_synth.h -- so a 30x WGS sample (6.2e8 reads) is generated straight into

@@ -123,6 +123,8 @@ SIGNATURES = {
     "rfx_bam_mark_names": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u64p, u64p]),
     "rfx_bam_gather": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]),
     "rfx_bam_locate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p]),
+    "rfx_bam_gather_hits": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, u64p,
+                                      u32p, u32p, C.c_uint64, u64p]),
     "rfx_bam_fetch": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     "rfx_nameset_mark": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p, u64p]),
     "rfx_reads_of_length": (C.c_uint64, [C.c_void_p, C.c_uint32]),
@@ -615,6 +617,32 @@ class TextArena:
             rc, nb, _ = self.bam_gather_into(mask, n_kept, out, exclude_flags=exclude_flags)
         _check(rc, "rfx_bam_gather")
         return out[:nb].tobytes()
+
+    def bam_gather_hits_into(self, mset: "MutantSet", block: "ReadBlock", thresh: int, last_base_skipped: bool, out: np.ndarray,
+                             hits: np.ndarray, index: "np.ndarray | None", cap: "int | None" = None, sel_cap: "int | None" = None,
+                             exclude_flags: int = 3328):
+        """rfx_bam_gather_hits into `out` (uint8), `hits` and `index` (uint32; index may be None); cap / sel_cap: what the
+        call is told the buffers hold, default all of them: (return code, bytes, records selected).  E_RANGE: both totals
+        are the need, nothing written."""
+        nb, ns = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().rfx_bam_gather_hits(self._h, exclude_flags, mset._h, block._h, thresh, int(last_base_skipped),
+                                       out.ctypes.data_as(C.c_void_p), len(out) if cap is None else cap, C.byref(nb), _p(hits, u32p),
+                                       _p(index, u32p) if index is not None else None,
+                                       len(hits) if sel_cap is None else sel_cap, C.byref(ns))
+        return int(rc), int(nb.value), int(ns.value)
+
+    def bam_gather_hits(self, mset: "MutantSet", block: "ReadBlock", thresh: int, last_base_skipped: bool = False,
+                        exclude_flags: int = 3328):
+        """(bytes, hits, index): the kept records of this settled arena whose count of windows in `mset` reaches `thresh`,
+        block_size field included, in file order; their counts; their kept indices (uint32 each).  `block` is
+        bam_parse_filter's of this arena in this state.  One retry with the sizes the first call reports."""
+        out, hits, index = np.zeros(1 << 16, np.uint8), np.zeros(256, np.uint32), np.zeros(256, np.uint32)
+        rc, nb, ns = self.bam_gather_hits_into(mset, block, thresh, last_base_skipped, out, hits, index, exclude_flags=exclude_flags)
+        if rc == E_RANGE:
+            out, hits, index = np.zeros(max(nb, 1), np.uint8), np.zeros(max(ns, 1), np.uint32), np.zeros(max(ns, 1), np.uint32)
+            rc, nb, ns = self.bam_gather_hits_into(mset, block, thresh, last_base_skipped, out, hits, index, exclude_flags=exclude_flags)
+        _check(rc, "rfx_bam_gather_hits")
+        return out[:nb].tobytes(), hits[:ns].copy(), index[:ns].copy()
 
     def bam_locate(self, n_kept: int, exclude_flags: int = 3328):
         """(start, bytes), uint32 each: the arena offset of every kept record's block_size field and 4 + block_size, in file

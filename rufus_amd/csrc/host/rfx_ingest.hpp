@@ -33,6 +33,7 @@
 
 #include "rfx_sam.hpp"
 #include "rfx_bam_pairs.hpp"
+#include "rfx_bam_single.hpp"
 #include "rfx_packed_cache.hpp"
 #include "rfx_bam_cache.hpp"
 #include "rfx_bai.hpp"
@@ -2059,6 +2060,108 @@ class BamPairFilter {
              (unsigned long long)arenas_, (unsigned long long)records_, (unsigned long long)reads_,
              (unsigned long long)hit_index_.size(), (unsigned long long)names_, (unsigned long long)tail_.records,
              (unsigned long long)tail_.walk.n_found);
+    return region_.empty() ? std::string(b) : std::string(b) + " | " + ingest_counts_;
+  }
+};
+
+// ---- the subject's hit reads straight from a single-end BAM: one pass, on the device -------------------------------------
+// Replaces `samtools view -F 3328 X.bam [REG] | PassThroughSamCheck.stranded.se CHR | RUFUS.Filter.single HashList stdin ...`
+// (runRufus.sh:1031-1032).  Nothing is paired by name, so what becomes of a record depends on that record alone and ONE
+// pass is exact: BamIngest's walk (the region and its .bai range are BamIngest's, unchanged), and per settled arena
+//   rfx_bam_parse_filter(MinQ)    the stranded filter form; the refID runs stitched by BamIngest::add_runs
+//   rfx_bam_gather_hits(thresh, last_base_skipped = 0)    src/RUFUS.Filter.ss.cpp:176-193 examines the last base; the
+//                                 selected records' bytes and their counts into page-locked memory, which grows on
+//                                 RFX_E_RANGE: one retry with the sizes the call reported
+//   tail    rfx_bam_single.hpp: every gathered record checked, printed as the stranded feeder prints it, `:MH<hits>`
+// The text goes to the sink arena by arena, in stream order; nothing is held for the whole file.
+// (weak, as above)
+#pragma weak rfx_bam_gather_hits
+class BamSingleFilter {
+  rfx_ctx* ctx_;
+  rfx_set* set_;
+  int min_q_, thresh_;
+  uint32_t exclude_;
+  size_t arena_bytes_, piece_;
+  std::function<void(const char*, size_t)> sink_;
+  std::vector<uint32_t> runs_buf_;
+  std::vector<std::string> chr_log_;
+  struct Pinned {
+    void* p = nullptr;
+    size_t cap = 0;
+    void need(size_t bytes) {
+      if (bytes <= cap) return;
+      if (p) rfx_host_free(p);
+      cap = bytes + bytes / 4 + 4096;
+      p = rfx_host_alloc(cap);
+      if (!p) die("rufus_amd: cannot allocate page-locked memory for the pulled records");
+    }
+    ~Pinned() { if (p) rfx_host_free(p); }
+  } out_, hits_;
+  rfxsam::BamSingleTail tail_;
+  uint64_t arenas_ = 0, records_ = 0, reads_ = 0;
+  std::string region_, bam_path_, ingest_counts_;
+  static constexpr const char* TOOL = "rufus_amd RUFUS.Filter.single";
+
+  uint64_t arena_step(BamIngest& in, rfx_text* t, uint64_t n_records) {
+    runs_buf_.resize((size_t)2 * n_records);
+    uint64_t n_runs = 0;
+    rfx_reads* rd = rfx_bam_parse_filter(t, exclude_, min_q_, runs_buf_.data(), n_records, &n_runs);
+    if (!rd) die(std::string(TOOL) + ": --bam: " + rfx_last_error());
+    in.add_runs(runs_buf_.data(), n_runs);
+    const uint64_t n = rfx_reads_count(rd);
+    uint64_t bytes = 0, sel = 0;
+    auto pull = [&] {
+      return rfx_bam_gather_hits(t, exclude_, set_, rd, thresh_, /*last_base_skipped=*/0, out_.p, out_.cap, &bytes, (uint32_t*)hits_.p,
+                                 nullptr, hits_.cap / 4, &sel);
+    };
+    int rc = pull();
+    if (rc == RFX_E_RANGE) {
+      out_.need((size_t)bytes);
+      hits_.need((size_t)sel * 4);
+      rc = pull();
+    }
+    rfx_reads_free(rd);
+    if (rc != RFX_OK) die(std::string(TOOL) + ": --bam: " + rfx_last_error());
+    std::string why;
+    tail_.out.clear();
+    if (!tail_.add((const uint8_t*)out_.p, bytes, (const uint32_t*)hits_.p, sel, &why)) die(std::string(TOOL) + ": --bam: " + why);
+    if (!tail_.out.empty()) sink_(tail_.out.data(), tail_.out.size());
+    return n;
+  }
+
+ public:
+  // sink: the next stretch of STUB.Mutations.fastq, in stream order
+  BamSingleFilter(rfx_ctx* ctx, rfx_set* set, int min_q, int thresh, uint32_t exclude_flags, std::function<void(const char*, size_t)> sink,
+                  size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20)
+      : ctx_(ctx), set_(set), min_q_(min_q), thresh_(thresh), exclude_(exclude_flags), arena_bytes_(arena_bytes), piece_(piece),
+        sink_(std::move(sink)) {
+    if (!rfx_bam_parse_filter || !rfx_bam_gather_hits || !rfx_reads_count) die(std::string(TOOL) + ": this library cannot read BAM input");
+    out_.need((size_t)1 << 20);
+    hits_.need((size_t)1 << 14);
+  }
+  // before run(): only the records that overlap the region take part, as behind `samtools view X.bam REG`
+  void set_region(const std::string& text, const std::string& bam_path) {
+    region_ = text;
+    bam_path_ = bam_path;
+  }
+  // A whole mapped BAM file.  Dies where BamIngest does.  Afterwards chr_log() holds the chromosome log's lines.
+  void run(const char* m, size_t size) {
+    BamIngest in(ctx_, nullptr, exclude_, arena_bytes_, piece_);
+    if (!region_.empty()) in.set_region(region_, bam_path_);
+    in.set_per_arena([&](rfx_text* t, uint64_t n_records) { return arena_step(in, t, n_records); }, TOOL);
+    in.feed_mapped(m, size);
+    arenas_ = in.arenas();
+    records_ = in.records();
+    reads_ = in.reads();
+    chr_log_ = in.chr_log();
+    ingest_counts_ = in.counts();
+    trace("filter --bam: pass 1 done");
+  }
+  const std::vector<std::string>& chr_log() const { return chr_log_; }
+  std::string counts() const {
+    char b[240];
+    snprintf(b, sizeof b, "bam single route: arenas %llu records %llu reads %llu selected %llu windows %llu", (unsigned long long)arenas_,
+             (unsigned long long)records_, (unsigned long long)reads_, (unsigned long long)tail_.records, (unsigned long long)tail_.windows);
     return region_.empty() ? std::string(b) : std::string(b) + " | " + ingest_counts_;
   }
 };

@@ -5,6 +5,8 @@
 //       -> STUB.Mutations.fastq with ":MH<hits>" appended to each header  src/RUFUS.Filter.ss.cpp:27,:43-49,:198
 //   RUFUS.Filter --sam | --packed | --bam ...: the subject's SAM stream, its packed cache or its BAM file as the input
 //       (not in the reference: namespaces samf and bamf below)
+//   RUFUS.Filter.single --sam | --bam ...: the same two inputs for a single-end subject (runRufus.sh -se, :1031-1032):
+//       every record by itself, STUB.Mutations.fastq with ":MH<hits>"; --packed stays paired-only
 // The two mate files may be named pipes written in lock step by PassThroughSamCheck.stranded, so
 // they are read interleaved, 4 lines each (src/RUFUS.Filter.cpp:165-173) -- never one file ahead.
 // Pulled records are written in input order (the reference's order depends on OpenMP scheduling; at
@@ -23,13 +25,23 @@
 
 using namespace rfxcli;
 
-#ifndef RFX_SINGLE_END
 #include <unordered_set>
 
 #include "rfx_sam.hpp"
 #include "rfx_packed_cache.hpp"
 #include "rfx_bam_cache.hpp"
 #include "rfx_ingest.hpp"
+
+// the two executables this source makes: what differs between them in the routes both have (--sam, --bam)
+#ifdef RFX_SINGLE_END
+static constexpr int SINGLE = 1;
+static const char* const TOOL = "rufus_amd RUFUS.Filter.single";
+#else
+static constexpr int SINGLE = 0;
+static const char* const TOOL = "rufus_amd RUFUS.Filter";
+#endif
+
+#ifndef RFX_SINGLE_END
 // ---- RUFUS.Filter HashList A.fastq.gz B.fastq.gz STUB K MinQ HashCountThreshold Threads --------------------------------
 // Both mate files bgzip'd (regular files whose first block rfx_bgzf_scan accepts): replaces runRufus.sh:974-977's
 // `<(zcat A) <(zcat B)`.  The files are mapped and handed to rfx_ingest.hpp's BgzfPairFilter: inflated, parsed, scanned
@@ -101,6 +113,13 @@ static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<u
 namespace bamf {
 static int run_cached(int argc, char** argv);  // --packed with a BAM-kind cache (below)
 }
+#endif
+// RUFUS.Filter.single --sam CHRFILE HashList SAM|stdin STUB K MinQ HashCountThreshold Threads (-DRFX_SINGLE_END): the same
+// pipeline -- reader, helper threads, the stranded form packed per record, the chromosome log -- for what
+// `PassThroughSamCheck.stranded.se CHR | RUFUS.Filter.single HashList stdin ...` does with the stream (runRufus.sh:1031-1032;
+// a CRAM subject, :609, gets one process instead of two).  The scan examines the last base too (`i < length()`,
+// src/RUFUS.Filter.ss.cpp:176) and the counts come back; there is no pairing: the records whose count reaches the threshold
+// are written in stream order to STUB.Mutations.fastq with ":MH<hits>" (:194-203).
 namespace samf {
 using namespace rfxsam;
 
@@ -136,6 +155,7 @@ struct SPiece {
   std::vector<Rec> recs;
   std::vector<std::string> chr_runs;
   std::vector<uint64_t> mask;  // hit bit per record
+  std::vector<uint32_t> hits;  // RUFUS.Filter.single: hit windows per record
   std::vector<uint32_t> waited;  // records of this piece that went into the waiting table
   uint64_t seq = 0;
 };
@@ -167,17 +187,22 @@ static int run(int argc, char** argv) {
     return 0;
   }
   FILE* chr = fopen(chr_path, "w");
+#ifdef RFX_SINGLE_END
+  std::ofstream out1((stub + ".Mutations.fastq").c_str(), std::ios::binary);
+  if (!chr || !out1.is_open()) {
+#else
   std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
   std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
   if (!chr || !out1.is_open() || !out2.is_open()) {
+#endif
     printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
     return 0;
   }
-  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, 0, nullptr, 0);
+  if (k < 1 || k > 32) die(std::string(TOOL) + ": hash size must be 1..32");
+  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, nullptr, 0);
   if (nk < 0) die("rufus_amd: cannot parse the hash list");
   std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
+  rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, keys.data(), keys.size());
   printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
   // RUFUS_GPUS: the pieces are dealt to the devices by helper thread (the filter shards by read block)
   const std::vector<int> gpus = gpu_list();
@@ -372,6 +397,7 @@ static int run(int argc, char** argv) {
       }
       const size_t n = pc.recs.size();
       pc.mask.assign((n + 63) / 64, 0);
+      if (SINGLE) pc.hits.assign(n, 0);
       if (n) {
         so.resize(n); qo.resize(n); sl.resize(n);
         for (size_t i = 0; i < n; ++i) {
@@ -399,7 +425,9 @@ static int run(int argc, char** argv) {
         rfx_reads* rd = rfx_reads_upload(ctx, codes, nullptr, good, woff, lens, (uint32_t)n);
         if (!rd) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
         uint64_t nh = 0;
-        const int rc = rfx_filter(set, rd, thresh, 1, nullptr, pc.mask.data(), &nh);
+        // (the paired tool never examines a read's last base, src/RUFUS.Filter.cpp:203; the single-end tool does and wants
+        // the counts, src/RUFUS.Filter.ss.cpp:176-198)
+        const int rc = rfx_filter(set, rd, thresh, SINGLE ? 0 : 1, SINGLE ? pc.hits.data() : nullptr, pc.mask.data(), &nh);
         rfx_reads_free(rd);
         if (rc) die(std::string("rufus_amd: filter failed: ") + rfx_last_error());
       }
@@ -415,6 +443,7 @@ static int run(int argc, char** argv) {
   PairWalk walk;  // (rfx_sam.hpp: the walk `--bam` runs too)
   WaitTable& waiting = walk.waiting;
   std::string &o1 = walk.o1, &o2 = walk.o2;
+  (void)o2;
   unsigned long long &n_pairs = walk.n_pairs, &n_found = walk.n_found;
   std::deque<SPiece*> live;
   std::string current = "notachr";
@@ -455,6 +484,28 @@ static int run(int argc, char** argv) {
         current = name;
       }
     const size_t n = pc->recs.size();
+#ifdef RFX_SINGLE_END
+    // no pairing: a record whose count reaches the threshold is written, `@QNAME:MH<hits>` (selected by the COUNT, as the
+    // reference's `>=` does: a threshold <= 0 writes every record)
+    for (size_t i = 0; i < n; ++i) {
+      const Rec& r = pc->recs[i];
+      ++n_pairs;
+      if ((int)pc->hits[i] < thresh) continue;
+      ++n_found;
+      o1.push_back('@');
+      o1.append(r.name, r.name_len);
+      o1.append(":MH").append(std::to_string(pc->hits[i])).push_back('\n');
+      o1.append(r.seq, r.seq_len);
+      o1.append("\n+\n", 3);
+      o1.append(r.qual, r.qual_len);
+      o1.push_back('\n');
+    }
+    n_rec += n;
+    if (!o1.empty()) {
+      out1.write(o1.data(), (std::streamsize)o1.size());
+      o1.clear();
+    }
+#else
     for (size_t i = 0; i < n; ++i) {
       const Rec& r = pc->recs[i];
       const uint32_t hit = (uint32_t)((pc->mask[i >> 6] >> (i & 63)) & 1);
@@ -467,6 +518,7 @@ static int run(int argc, char** argv) {
       o1.clear();
       o2.clear();
     }
+#endif
     live.push_back(pc);
     if (live.size() > LAG) {
       retire(live.front());
@@ -485,7 +537,9 @@ static int run(int argc, char** argv) {
   trace("filter --sam: all pieces done");
   printf("\nSAM records %llu, pairs %llu, pulled %llu\n", n_rec, n_pairs, n_found);
   out1.close();
+#ifndef RFX_SINGLE_END
   out2.close();
+#endif
   printf("\nDone running RUFUS.Filter.cpp\n");
   if (!in_process) leave(0);  // (outputs closed: see the FASTQ route's end)
   for (rfx_set* st : sets) rfx_set_free(st);
@@ -493,6 +547,7 @@ static int run(int argc, char** argv) {
   return 0;
 }
 
+#ifndef RFX_SINGLE_END
 // `RUFUS.Filter --packed CACHE CHRFILE PreBuiltMutHash SPOOL firstpassfile hashsize MinQ HashCountThreshold threads`
 // (rfx_packed_cache.hpp): the subject's records were packed once, by `jellyfish count --sam ..
 // --keep-packed CACHE`.  Here they are uploaded as they lie in CACHE and scanned; only the lines of the names with a hit
@@ -680,6 +735,7 @@ static int run_packed(int argc, char** argv) {
   ::unlink(tmp.c_str());
   return rc;
 }
+#endif
 }  // namespace samf
 
 // ---- RUFUS.Filter --bam CHRFILE HashList X.bam STUB K MinQ HashCountThreshold Threads [--bam-exclude N] ---------------
@@ -689,6 +745,11 @@ static int run_packed(int argc, char** argv) {
 // the file and writes the three outputs.  One device: RUFUS_GPUS naming more is refused, as for the bgzip'd mates.
 // RFX_BAM_ARENA (bytes per arena, >= 1 MiB) and RFX_INGEST_PIECE as in `jellyfish count --bam`.  Threads is accepted and
 // not used: no host thread parses anything.
+//
+// RUFUS.Filter.single --bam ... (-DRFX_SINGLE_END): the same arguments, checks and refusals; what `samtools view -F N X.bam
+// [REG] | PassThroughSamCheck.stranded.se CHRFILE | RUFUS.Filter.single HashList stdin STUB K MinQ Threshold 1` writes
+// (runRufus.sh:1031-1032), byte for byte: STUB.Mutations.fastq and CHRFILE.  rfx_ingest.hpp's BamSingleFilter: ONE pass --
+// nothing is paired by name -- and the file's text is written arena by arena, in stream order.
 namespace bamf {
 static int run(int argc, char** argv) {
   printf("Call is --bam CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads [--bam-exclude N] [--region REG]\n");
@@ -704,9 +765,9 @@ static int run(int argc, char** argv) {
   for (int a = 10; a < argc; ++a) {
     if (strcmp(argv[a], "--bam-exclude") == 0 && a + 1 < argc) exclude = (uint32_t)strtoul(argv[++a], nullptr, 0);
     else if (strcmp(argv[a], "--region") == 0 && a + 1 < argc) {
-      if (region) die("rufus_amd RUFUS.Filter: --bam: --region given twice: one region per run");
+      if (region) die(std::string(TOOL) + ": --bam: --region given twice: one region per run");
       region = argv[++a];
-    } else die(std::string("rufus_amd RUFUS.Filter: --bam: unknown argument ") + argv[a]);
+    } else die(std::string(TOOL) + ": --bam: unknown argument " + argv[a]);
   }
   std::string text;
   {
@@ -724,22 +785,27 @@ static int run(int argc, char** argv) {
   }
   struct stat sb;
   if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode))
-    die("rufus_amd RUFUS.Filter: --bam needs a regular file, not a pipe: the BAM is mapped and read twice");
-  if (!is_bgzf(fd, true, (uint64_t)sb.st_size)) die(std::string("rufus_amd RUFUS.Filter: --bam: '") + bam + "' is not BGZF");
-  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, 0, nullptr, 0);
+    die(std::string(TOOL) + ": --bam needs a regular file, not a pipe: the BAM is mapped and read " + (SINGLE ? "once" : "twice"));
+  if (!is_bgzf(fd, true, (uint64_t)sb.st_size)) die(std::string(TOOL) + ": --bam: '" + bam + "' is not BGZF");
+  if (k < 1 || k > 32) die(std::string(TOOL) + ": hash size must be 1..32");
+  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, nullptr, 0);
   if (nk < 0) die("rufus_amd: cannot parse the hash list");
   std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
+  rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, keys.data(), keys.size());
   printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
   const std::vector<int> gpus = gpu_list();
   if (gpus.size() != 1)
-    die("rufus_amd RUFUS.Filter: --bam finds, scans and pulls the records on the device, which needs one device (RUFUS_GPUS names "
+    die(std::string(TOOL) + ": --bam finds, scans and pulls the records on the device, which needs one device (RUFUS_GPUS names "
         "more)");
   FILE* chr = fopen(chr_path, "w");
+#ifdef RFX_SINGLE_END
+  std::ofstream out1((stub + ".Mutations.fastq").c_str(), std::ios::binary);
+  if (!chr || !out1.is_open()) {
+#else
   std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
   std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
   if (!chr || !out1.is_open() || !out2.is_open()) {
+#endif
     printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
     return 0;
   }
@@ -748,11 +814,25 @@ static int run(int argc, char** argv) {
   if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
   trace("filter --bam: device open, set built");
   void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  if (m == MAP_FAILED) die(std::string("rufus_amd RUFUS.Filter: --bam: cannot map the input: ") + strerror(errno));
+  if (m == MAP_FAILED) die(std::string(TOOL) + ": --bam: cannot map the input: " + strerror(errno));
   (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
   size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
   if (const char* ev = getenv("RFX_BAM_ARENA")) arena = (size_t)std::max(1ll << 20, atoll(ev));
   if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+#ifdef RFX_SINGLE_END
+  {
+    BamSingleFilter route(
+        ctx, set, min_q, thresh, exclude, [&](const char* p, size_t n) { out1.write(p, (std::streamsize)n); }, arena, piece);
+    if (region) route.set_region(region, bam);
+    route.run((const char*)m, (size_t)sb.st_size);
+    for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
+    fclose(chr);
+    out1.close();
+    trace(route.counts().c_str());
+    printf("\nDone running RUFUS.Filter.cpp\n");
+    leave(0);  // (outputs closed: see the text route's end)
+  }
+#else
   {
     BamPairFilter route(ctx, set, min_q, thresh, exclude, arena, piece);
     if (region) route.set_region(region, bam);
@@ -767,11 +847,13 @@ static int run(int argc, char** argv) {
     printf("\nDone running RUFUS.Filter.cpp\n");
     leave(0);  // (outputs closed: see the text route's end)
   }
+#endif
   rfx_set_free(set);
   rfx_close(ctx);
   return 0;
 }
 
+#ifndef RFX_SINGLE_END
 // `RUFUS.Filter --packed CACHE CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads` with the
 // BAM-kind cache `jellyfish count --bam CHR --keep-packed CACHE X.bam` left (rfx_bam_cache.hpp): what `--bam` writes, byte
 // for byte, without a pass over the file -- the cache is scanned, and only the BGZF blocks that hold the hit names' records
@@ -872,14 +954,17 @@ static int run_cached(int argc, char** argv) {
   rfx_close(ctx);
   return same ? 0 : two_pass();  // (a fetched record was not the cache's: nothing has been written)
 }
-}  // namespace bamf
 #endif
+}  // namespace bamf
 
 int main(int argc, char** argv) {
-#ifndef RFX_SINGLE_END
   if (argc > 1 && strcmp(argv[1], "--sam") == 0) return samf::run(argc, argv);
-  if (argc > 1 && strcmp(argv[1], "--packed") == 0) return samf::run_packed(argc, argv);
   if (argc > 1 && strcmp(argv[1], "--bam") == 0) return bamf::run(argc, argv);
+#ifndef RFX_SINGLE_END
+  if (argc > 1 && strcmp(argv[1], "--packed") == 0) return samf::run_packed(argc, argv);
+#else
+  if (argc > 1 && strcmp(argv[1], "--packed") == 0)
+    die("rufus_amd RUFUS.Filter.single: --packed is for paired subjects only (RUFUS.Filter --packed): use --bam or --sam");
 #endif
 #ifdef RFX_SINGLE_END
   const int need = 8;

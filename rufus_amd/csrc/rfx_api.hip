@@ -4505,23 +4505,26 @@ void rfx_set_free(rfx_set* s) {
 namespace {
 // One block's filter queued on the ctx stream: launches + read-backs, no wait.  The device buffers go to `held` (freed by
 // the caller after the wait); *nh receives the number of reads over threshold at the next synchronisation.
+// keep_counts: the per-read counts are wanted on the DEVICE (held[first + 0] afterwards, r->n words, never nullptr on
+// RFX_OK) whether or not hits_out asks for them on the host; false leaves every launch as it was.
 int filter_queue(rfx_set* s, const rfx_reads* r, int thresh, int last_base_skipped, uint32_t* hits_out, uint64_t* hitmask_out,
-                 unsigned long long* nh, std::vector<void*>& held) {
+                 unsigned long long* nh, std::vector<void*>& held, bool keep_counts = false) {
   rfx_ctx* c = s->ctx;
+  const bool want_counts = hits_out || keep_counts;
   const uint64_t nmask = ((uint64_t)r->n + 63) / 64;
   // (the queue filter counts into the array whether the caller wants the counts or not)
   const bool use_q = s->bitmap4 && !getenv("RFX_FILTER_GENERIC") && !getenv("RFX_FILTER_OLD");
   // the pair filter (round 6; RFX_FILTER_NO_PAIR at rfx_set_build keeps the set without its table): with thresh = 1 and
   // nobody asking for the counts, the hits set the mask's bits themselves -- no count array, no memset, no second pass
   const bool use_p = s->bitmap5 && use_q && !getenv("RFX_FILTER_NO_PAIR");
-  const bool mask_only = use_p && thresh == 1 && !hits_out;
-  uint32_t* d_hits = (hits_out || use_q) && !mask_only ? (uint32_t*)dmalloc(c, (size_t)r->n * 4) : nullptr;
+  const bool mask_only = use_p && thresh == 1 && !want_counts;
+  uint32_t* d_hits = (want_counts || use_q) && !mask_only ? (uint32_t*)dmalloc(c, (size_t)r->n * 4) : nullptr;
   uint64_t* d_mask = (uint64_t*)dmalloc(c, nmask * 8);
   unsigned long long* d_n = (unsigned long long*)dmalloc(c, 8);
   held.push_back(d_hits);
   held.push_back(d_mask);
   held.push_back(d_n);
-  if (((hits_out || use_q) && !mask_only && !d_hits) || !d_mask || !d_n) return RFX_E_NOMEM;
+  if (((want_counts || use_q) && !mask_only && !d_hits) || !d_mask || !d_n) return RFX_E_NOMEM;
   hipError_t e = hipMemsetAsync(d_n, 0, 8, c->stream);
   if (e == hipSuccess && use_q && !mask_only) e = hipMemsetAsync(d_hits, 0, (size_t)r->n * 4, c->stream);
   if (e == hipSuccess && mask_only) e = hipMemsetAsync(d_mask, 0, nmask * 8, c->stream);
@@ -4549,6 +4552,14 @@ int filter_queue(rfx_set* s, const rfx_reads* r, int thresh, int last_base_skipp
   return e == hipSuccess ? RFX_OK : hip_fail(e, "rfx_filter");
 }
 }  // namespace
+// filter_queue for rfx_bam.hip (rfx_bam_gather_hits): the filter in its counting mode, the counts left on the device
+int rfxi::filter_counts_queue(rfx_set* s, const rfx_reads* r, int thresh, int last_base_skipped, unsigned long long* nh,
+                              std::vector<void*>& held, const uint32_t** d_hits) {
+  const size_t first = held.size();
+  const int rc = filter_queue(s, r, thresh, last_base_skipped, nullptr, nullptr, nh, held, /*keep_counts=*/true);
+  *d_hits = rc == RFX_OK ? (const uint32_t*)held[first] : nullptr;  // (filter_queue holds d_hits, d_mask, d_n in this order)
+  return rc;
+}
 extern "C" {
 
 int rfx_filter(rfx_set* s, const rfx_reads* r, int thresh, int last_base_skipped, uint32_t* hits_out,

@@ -739,6 +739,75 @@ __global__ __launch_bounds__(256) void k_bamg_table(const uint8_t* __restrict__ 
   }
 }
 
+// ---- the hit records of an arena with their hit counts (RUFUS.Filter.single --bam) ----------------------------------------
+// Replaces `samtools view -F 3328 X.bam | PassThroughSamCheck.stranded.se CHR | RUFUS.Filter.single ...` (runRufus.sh:1031-1032).
+// What becomes of a record depends on that record alone (src/PassThroughSamCheck.stranded.se.cpp:155-203 prints it,
+// src/RUFUS.Filter.ss.cpp:164-203 scans it -- `i < length()`: the last base IS examined -- and writes it when its count
+// reaches the threshold, :194), so one pass does it: rfx_bam_parse_filter's block goes through the filter in its counting
+// mode, and the selection is made from the COUNTS (the filter's own mask has undefined bits at and above n, and the pair
+// filter's mask-only mode leaves no counts at all):
+//   k_bamh_pick    k_bam_mark's shape -- a wave per 64 kept records, a lane a record: the ballot of `count >= thresh`, the
+//                  selected records' 4 + block_size summed over the wave by shuffles -> cnt[w], bytes[w]   -> two scans
+//   k_bamh_table   the same ballot again; a selected lane's rank = the votes below it (mbcnt), its offset = an in-wave
+//                  exclusive prefix of the selected sizes (six shuffle steps, every lane taking part): source offset,
+//                  destination offset, count and kept index at cnt[w] + rank                               -> k_gather_copy
+// No LDS, no atomics; the trip count of both loops is wave-uniform, so every lane reaches every ballot and shuffle; lanes
+// at and above n_kept vote 0 and bring 0 bytes.  hits[o] and kept_at[o] are read for o < n_kept only, a record's size only
+// through bam_block_size inside a record the settle has checked.  All totals are below 2^32: an arena is.
+__global__ __launch_bounds__(256) void k_bamh_pick(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at,
+                                                    const uint32_t* __restrict__ hits, uint64_t n_kept, int thresh,
+                                                    uint64_t* __restrict__ cnt, uint64_t* __restrict__ bytes) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6), nw = (n_kept + 63) / 64;
+  for (uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < nw; w += waves) {  // (wave-uniform)
+    const uint64_t o = w * 64 + lane;
+    const bool sel = o < n_kept && (int)hits[o] >= thresh;
+    const unsigned long long vote = __ballot(sel);
+    uint32_t nb = sel ? record_bytes(b, kept_at[o]) : 0u;
+    for (int d = 32; d; d >>= 1) nb += __shfl_xor(nb, d);
+    if (lane == 0) {
+      cnt[w] = (uint32_t)__popcll(vote);
+      bytes[w] = nb;
+    }
+  }
+}
+
+// cnt / bytes: the scanned arrays (positions in the result)
+__global__ __launch_bounds__(256) void k_bamh_table(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at,
+                                                     const uint32_t* __restrict__ hits, uint64_t n_kept, int thresh,
+                                                     const uint64_t* __restrict__ cnt, const uint64_t* __restrict__ bytes,
+                                                     uint32_t* __restrict__ src_off, uint32_t* __restrict__ dst_off,
+                                                     uint32_t* __restrict__ hits_sel, uint32_t* __restrict__ index_sel) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6), nw = (n_kept + 63) / 64;
+  for (uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < nw; w += waves) {  // (wave-uniform)
+    const uint64_t o = w * 64 + lane;
+    uint32_t h = 0, s = 0;
+    bool sel = false;
+    if (o < n_kept) {
+      h = hits[o];
+      sel = (int)h >= thresh;
+      if (sel) s = kept_at[o];
+    }
+    const unsigned long long vote = __ballot(sel);
+    const uint32_t nb = sel ? record_bytes(b, s) : 0u;
+    uint32_t upto = nb;  // the inclusive prefix of the sizes: lane l adds what lies d lanes below it, d = 1, 2, .. 32
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t below = __shfl_up(upto, d);
+      if (lane >= d) upto += below;
+    }
+    const uint32_t first = (uint32_t)cnt[w], at0 = (uint32_t)bytes[w];  // (both totals are below 2^32: the arena is)
+    if (sel) {
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(vote >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vote, 0u));
+      src_off[first + rank] = s;
+      dst_off[first + rank] = at0 + upto - nb;
+      hits_sel[first + rank] = h;
+      index_sel[first + rank] = (uint32_t)o;
+    }
+    if (w == nw - 1 && lane == 63u) dst_off[first + (uint32_t)__popcll(vote)] = at0 + upto;  // dst_off[n_sel] = all bytes
+  }
+}
+
 // a kept record's address: where its block_size field lies in the arena, and the bytes from there to its end
 __global__ __launch_bounds__(256) void k_bam_locate(const uint8_t* __restrict__ b, const uint32_t* __restrict__ kept_at, uint64_t n_kept,
                                                      uint32_t* __restrict__ start_out, uint32_t* __restrict__ bytes_out) {
@@ -1197,6 +1266,82 @@ int rfx_bam_gather(rfx_text* t, uint32_t exclude_flags, const uint64_t* mask, ui
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(host_out, out, (size_t)n_bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = rfxi::sync(c);
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  return done(RFX_OK, hipSuccess, "");
+}
+
+// The single-end read pull (RUFUS.Filter.single --bam): see the section in front of k_bamh_pick.
+int rfx_bam_gather_hits(rfx_text* t, uint32_t exclude_flags, rfx_set* set, const rfx_reads* block, int thresh, int last_base_skipped,
+                        void* host_out, uint64_t cap, uint64_t* bytes_out, uint32_t* hits_out, uint32_t* index_out, uint64_t sel_cap,
+                        uint64_t* n_selected) {
+  static const char* const who = "rfx_bam_gather_hits";
+  if (bytes_out) *bytes_out = 0;
+  if (n_selected) *n_selected = 0;
+  if (!t || !set || !block || !bytes_out || !n_selected || (cap && !host_out) || (sel_cap && !hits_out))
+    return pull_fail(nullptr, who, RFX_E_INVAL, hipSuccess, "a NULL argument");
+  if (rfxi::text_ctx(t) != set->ctx || block->ctx != set->ctx)
+    return pull_fail(nullptr, who, RFX_E_INVAL, hipSuccess, "the arena, the set and the block belong to different contexts");
+  if (!block->good) return pull_fail(nullptr, who, RFX_E_INVAL, hipSuccess, "the block is not a filter block (no quality mask)");
+  kept_view v;
+  if (const int rc = kept_of(t, exclude_flags, who, &v)) return rc;
+  rfx_ctx* c = v.c;
+  if (v.n_kept != block->n) {
+    dfree(c, v.kept_at);
+    return pull_fail(c, who, RFX_E_INVAL, hipSuccess, "the block does not hold the kept records of the arena as it is now");
+  }
+  if (v.n_kept == 0) return RFX_OK;
+  const uint64_t nw = (v.n_kept + 63) / 64;
+  uint64_t* cnt = (uint64_t*)dmalloc(c, ((size_t)nw + 1) * 8);
+  uint64_t* sizes = (uint64_t*)dmalloc(c, ((size_t)nw + 1) * 8);
+  uint32_t *src_off = nullptr, *dst_off = nullptr, *hits_sel = nullptr, *index_sel = nullptr, *out = nullptr;
+  std::vector<void*> held;  // the filter's buffers: the counts among them
+  auto done = [&](int rc, hipError_t e, const char* text) {
+    if (rc) pull_fail(c, who, rc, e, text);  // (waits: a read-back into a local below may be queued)
+    dfree(c, v.kept_at); dfree(c, cnt); dfree(c, sizes); dfree(c, src_off); dfree(c, dst_off); dfree(c, hits_sel); dfree(c, index_sel);
+    dfree(c, out);
+    for (void* p : held) dfree(c, p);
+    return rc;
+  };
+  if (!cnt || !sizes) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  unsigned long long nh = 0;
+  uint64_t n_sel = 0, n_bytes = 0;
+  const uint32_t* d_hits = nullptr;
+  if (const int rc = rfxi::filter_counts_queue(set, block, thresh, last_base_skipped, &nh, held, &d_hits))
+    return done(rc, hipSuccess, rc == RFX_E_NOMEM ? "out of device memory" : "the filter could not be queued");
+  const dim3 per_wave((unsigned)std::min<uint64_t>((nw + 3) / 4, (uint64_t)c->n_cu * 16));
+  {
+    rfx_span sp(c, "k_bamh_pick");
+    hipLaunchKernelGGL(k_bamh_pick, per_wave, dim3(256), 0, c->stream, v.arena, v.kept_at, d_hits, v.n_kept, thresh, cnt, sizes);
+  }
+  rfxk::scan_tail(c, cnt, nw);
+  rfxk::scan_tail(c, sizes, nw);
+  hipError_t e = queue_read(c, &n_sel, cnt + nw, 8);
+  if (e == hipSuccess) e = queue_read(c, &n_bytes, sizes + nw, 8);
+  if (e == hipSuccess) e = rfxi::sync(c);  // the first wait: what the result is sized by
+  if (e != hipSuccess) return done(RFX_E_HIP, e, "");
+  *bytes_out = n_bytes;
+  *n_selected = n_sel;
+  if (n_bytes > cap || n_sel > sel_cap) return done(RFX_E_RANGE, hipSuccess, "an output buffer is too small");
+  if (n_sel == 0) return done(RFX_OK, hipSuccess, "");
+  if (n_bytes > v.n) return done(RFX_E_HIP, hipSuccess, "the selection is larger than the arena");  // (cannot be: a subset)
+  src_off = (uint32_t*)dmalloc(c, (size_t)n_sel * 4);
+  dst_off = (uint32_t*)dmalloc(c, ((size_t)n_sel + 1) * 4);
+  hits_sel = (uint32_t*)dmalloc(c, (size_t)n_sel * 4);
+  index_sel = (uint32_t*)dmalloc(c, (size_t)n_sel * 4);
+  out = (uint32_t*)dmalloc(c, ((size_t)n_bytes + 3) / 4 * 4);
+  if (!src_off || !dst_off || !hits_sel || !index_sel || !out) return done(RFX_E_NOMEM, hipSuccess, "out of device memory");
+  {
+    rfx_span sp(c, "k_bamh_table");
+    hipLaunchKernelGGL(k_bamh_table, per_wave, dim3(256), 0, c->stream, v.arena, v.kept_at, d_hits, v.n_kept, thresh, cnt, sizes, src_off,
+                       dst_off, hits_sel, index_sel);
+  }
+  // (the sources are whole records of the arena, as in rfx_bam_gather)
+  rfxi::gather_copy(c, v.arena, src_off, dst_off, (uint32_t)n_sel, (uint32_t)n_bytes, out);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(host_out, out, (size_t)n_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(hits_out, hits_sel, (size_t)n_sel * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && index_out) e = hipMemcpyAsync(index_out, index_sel, (size_t)n_sel * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = rfxi::sync(c);  // the second wait: the result is in the caller's memory
   if (e != hipSuccess) return done(RFX_E_HIP, e, "");
   return done(RFX_OK, hipSuccess, "");
 }

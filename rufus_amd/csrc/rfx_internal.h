@@ -599,6 +599,13 @@ int text_cut(rfx_text* t, rfx_text* next, uint64_t cut, uint64_t* carried, const
 // follows another in the selection does not start at the arena's first four bytes.
 void gather_copy(rfx_ctx*, const uint8_t* arena, const uint32_t* src_off, const uint32_t* dst_off, uint32_t n_sel, uint32_t n_bytes,
                  uint32_t* out);
+// One block's filter (rfx_api.hip filter_queue) queued on the ctx stream in its COUNTING mode for rfx_bam_gather_hits: the
+// launches and the read-back of *nh (lands at the next sync), no wait.  *d_hits = the per-read counts on the device (r->n
+// words, r->n > 0); they and the filter's other buffers go to `held`, which the caller frees (dfree) behind the work that
+// reads them.  The pair filter's mask-only mode is never taken, and the filter's own mask is not handed out: its bits at
+// and above r->n are undefined.  The caller has checked s->ctx == r->ctx and r->good.
+int filter_counts_queue(rfx_set* s, const rfx_reads* r, int thresh, int last_base_skipped, unsigned long long* nh,
+                        std::vector<void*>& held, const uint32_t** d_hits);
 }  // namespace rfxi
 
 // Launch bracket: records a HIP-event span on the ctx stream (or `stream`: an arena's own, rfx_text.hip) when profiling

@@ -490,3 +490,40 @@ def filter_bam(ctx: capi.Context, data: bytes, hash_list: bytes, k: int, min_q: 
     finally:
         nset.free()
     return b"".join(out1), b"".join(out2), log
+
+
+def filter_bam_single(ctx: capi.Context, data: bytes, hash_list: bytes, k: int, min_q: int, thresh: int, exclude_flags: int = 3328,
+                      arena_bytes: int = 256 << 20, region=None, index: bytes | None = None):
+    """``RUFUS.Filter.single --bam`` on the bytes of a BAM file: (STUB.Mutations.fastq bytes, chromosome log) -- what
+    `samtools view -F exclude_flags | PassThroughSamCheck.stranded.se | RUFUS.Filter.single` writes.  One pass, on the
+    device: per arena the stranded filter form (TextArena.bam_parse_filter) and the records whose count of hit windows --
+    the last base examined -- reaches `thresh`, with that count (TextArena.bam_gather_hits); the few pulled records are
+    printed here with `:MH<hits>`.  region, index: as `samtools view -F exclude_flags X.bam REGION` (_bam_arenas)."""
+    mset = capi.MutantSet(ctx, capi.hashlist_keys(hash_list, k, single_end=True), k)
+    out, refs, names = [], [], []
+    try:
+        for a, _, hdr in _bam_arenas(ctx, data, arena_bytes, region, index):
+            names = hdr["names"]
+            blk, runs = a.bam_parse_filter(min_q, exclude_flags)
+            try:
+                blob, hits, _ = a.bam_gather_hits(mset, blk, thresh, last_base_skipped=False, exclude_flags=exclude_flags)
+            finally:
+                blk.free()
+            refs += [int(r) for r in runs[:, 1]]
+            p = 0
+            for h in hits:
+                size = 4 + int.from_bytes(blob[p:p + 4], "little")
+                name, seq, qual = _bam_printed(blob[p:p + size])
+                p += size
+                out.append(b"@" + name + b":MH%d\n" % int(h) + seq + b"\n+\n" + qual + b"\n")
+            if p != len(blob):
+                raise ValueError("the gathered records do not add up")
+    finally:
+        mset.free()
+    log, current = [], b"notachr"
+    for r in refs:
+        name = b"*" if r < 0 else names[r]
+        if name != current:
+            log.append(current)
+            current = name
+    return b"".join(out), b"".join(x + b"\n" for x in log + [current])
