@@ -153,6 +153,9 @@ uint64_t rfx_reads_words(const rfx_reads*);
 /* Reads of the block that are exactly `len` bases long, for len < 32 (kept with the block since it was made; 0 for len
  * >= 32).  len = 0: the empty sequence lines the paired filter rejects (src/RUFUS.Filter.cpp:203 reads length() - 1). */
 uint64_t rfx_reads_of_length(const rfx_reads*, uint32_t len);
+/* The block's longest read, in bases (kept with the block since it was made): what rfx_count_add compares with the
+ * tiler's switch length (the buffers of jf/include/jellyfish/mer_overlap_sequence_parser.hpp:124-178, see below). */
+uint32_t rfx_reads_max_len(const rfx_reads*);
 /* D2H copy of a block's arrays (sized by rfx_reads_words / rfx_reads_count; any pointer may be NULL). */
 int rfx_reads_get(const rfx_reads*, uint64_t* codes, uint32_t* acgt, uint32_t* good, uint32_t* word_off, uint32_t* len);
 
@@ -283,6 +286,35 @@ int rfx_text_records(rfx_text* t, uint64_t* records);
 int rfx_text_settle_records(rfx_text* t, rfx_text* next, uint64_t max_records, uint64_t* records, uint64_t* carried);
 int rfx_text_gather(rfx_text* t, const uint64_t* hitmask, uint64_t n_records, void* host_out, uint64_t cap, uint64_t* bytes,
                     uint64_t* n_selected);
+
+/* -------------------------------------------------------------------------------------------
+ * bgzip'd FASTA in: the arena cut at a FASTA record, a record's lines joined into one read on the device
+ * Replaces `zcat ref.fa.gz | jellyfish count ... /dev/stdin` in front of the -e / -f databases (runRufus.sh:77, :115)
+ * and the contig and window counts of scripts/Overlap.shorter.sh:245, :255: the FASTA grammar of
+ * jf/include/jellyfish/mer_overlap_sequence_parser.hpp:124-251 on text that exists only in HBM.  The rule is
+ * rufus_amd/csrc/rfx_fasta_core.h, one source for host and device; the kernels are rufus_amd/csrc/rfx_fasta.hip.  A line
+ * ends at '\n' ('\r' stays a base); a line is a header when it is non-empty and begins with '>'; a record is a header and
+ * every line up to the next header or the end of the text, its sequence the bytes of those lines without their '\n'.
+ *
+ * rfx_text_settle_fasta (replaces the pipe of runRufus.sh:77 as what hands the parser whole records; the FASTA twin of
+ * rfx_text_settle, with its waits and preconditions): the cut lies at the last line start p > 0 whose byte is '>';
+ * t keeps [0, p) and [p, bytes) moves, device to device, to the front of `next` -- the arena's last record is always
+ * carried, because nothing says it is whole before the next header or the end of the file.  *carried = the tail's bytes.
+ * next == NULL: the file ends here, nothing is carried and a last line without '\n' is a line.  No such p (one record
+ * fills the arena): RFX_E_RANGE, rfx_last_error() = "rfx_fasta: one sequence fills the text arena of <bytes> bytes".  A
+ * first byte that is not '>': RFX_E_FORMAT.  A block that did not inflate: RFX_E_FORMAT with the "rfx_bgzf:" text.
+ *
+ * rfx_text_parse_fasta (replaces mer_overlap_sequence_parser.hpp:124-178 and mer_dna.hpp:46-63): the block of the
+ * arena's records, in order: codes, ACGT mask, offsets, lengths, read / word / base counts and the longest read are what
+ * rfx_pack_reads(RFX_PACK_COUNT) makes of the joined sequences, reads of length 0 (a header directly followed by a
+ * header) included, so rfx_count_add tiles a block of chromosomes as it tiles the host route's.  Works the same on text
+ * appended without BGZF.  NULL with *fasta == 0: the arena is empty or does not begin with '>' (no error).  NULL with
+ * *fasta == 1 is a failure, rfx_last_error() = "rfx_text_parse_fasta: RFX_E_INVAL ..." for flags other than
+ * RFX_PACK_COUNT (FASTA has no qualities), "... RFX_E_RANGE ..." for 2^32 reads or words, or the "rfx_bgzf:" text of a
+ * block that did not inflate, as rfx_text_parse.  Waits for its kernels, like rfx_text_parse.
+ * ------------------------------------------------------------------------------------------- */
+int rfx_text_settle_fasta(rfx_text* t, rfx_text* next, uint64_t* carried);
+rfx_reads* rfx_text_parse_fasta(rfx_text* t, int flags, int* fasta);
 
 /* -------------------------------------------------------------------------------------------
  * BAM in: the records of a BAM found and their 4-bit sequences packed on the device

@@ -82,6 +82,7 @@ SIGNATURES = {
     "rfx_reads_count": (C.c_uint32, [C.c_void_p]),
     "rfx_reads_bases": (C.c_uint64, [C.c_void_p]),
     "rfx_reads_words": (C.c_uint64, [C.c_void_p]),
+    "rfx_reads_max_len": (C.c_uint32, [C.c_void_p]),
     "rfx_reads_get": (C.c_int, [C.c_void_p, u64p, u32p, u32p, u32p, u32p]),
     "rfx_tile_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_uint32, u64p, u32p]),
     "rfx_reads_tile": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]),
@@ -102,6 +103,8 @@ SIGNATURES = {
     "rfx_bgzf_scan": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, u32p, u64p, u64p]),
     "rfx_text_append_bgzf": (C.c_long, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "rfx_text_settle": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
+    "rfx_text_settle_fasta": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
+    "rfx_text_parse_fasta": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "rfx_text_records": (C.c_int, [C.c_void_p, u64p]),
     "rfx_text_settle_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p]),
     "rfx_text_gather": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]),
@@ -721,6 +724,26 @@ class TextArena:
             raise RufusError("rfx_text_parse failed: " + lib().rfx_last_error().decode())
         return ReadBlock.from_handle(self.ctx, h)
 
+    def settle_fasta(self, next: "TextArena | None" = None) -> int:
+        """The FASTA twin of settle(): shortens the text to the start of its last header line and moves that record to the
+        front of `next`; next=None: the file ends here, nothing is carried.  The tail's length in bytes
+        (rfx_text_settle_fasta)."""
+        carried = C.c_uint64(0)
+        _check(lib().rfx_text_settle_fasta(self._h, next._h if next is not None else None, C.byref(carried)),
+               "rfx_text_settle_fasta")
+        return int(carried.value)
+
+    def parse_fasta(self, flags: int = PACK_COUNT):
+        """The block of the arena's FASTA records, every record's lines joined into one read, or None when the text does
+        not begin with '>' (rfx_text_parse_fasta)."""
+        fasta = C.c_int(1)
+        h = lib().rfx_text_parse_fasta(self._h, flags, C.byref(fasta))
+        if not h:
+            if fasta.value == 0:
+                return None
+            raise RufusError("rfx_text_parse_fasta failed: " + lib().rfx_last_error().decode())
+        return ReadBlock.from_handle(self.ctx, h)
+
     def fetch(self) -> bytes:
         n = int(lib().rfx_text_bytes(self._h))
         buf = C.create_string_buffer(max(n, 1))
@@ -783,6 +806,11 @@ class ReadBlock:
     @property
     def bases(self) -> int:
         return int(lib().rfx_reads_bases(self._h))
+
+    @property
+    def max_len(self) -> int:
+        """The longest read, in bases (rfx_reads_max_len)."""
+        return int(lib().rfx_reads_max_len(self._h))
 
     @property
     def device_bytes(self) -> int:

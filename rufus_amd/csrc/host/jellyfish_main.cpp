@@ -331,6 +331,10 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // bytes per read over PCIe and the host only reads the file.  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160).
   // Plain gzip (no `BC` subfield) is not BGZF and goes where it went before.
   std::unique_ptr<BgzfIngest> bgzf_ingest;
+  // A bgzip'd FASTA (its first inflated byte is '>': `ref.fa.gz` as `samtools faidx` wants it) takes the same route with
+  // the FASTA carry and parse (rfx_ingest.hpp BgzfIngest, fasta; csrc/rfx_fasta.hip).  Replaces the `zcat ref.fa.gz |`
+  // in front of the -e / -f databases (runRufus.sh:77, :115).
+  std::unique_ptr<BgzfIngest> fasta_ingest;
   // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, neither --sam nor --spool;
   // --keep-packed with one input leaves the BAM-kind cache (rfx_bam_cache.hpp).
   std::unique_ptr<BamIngest> bam_ingest;
@@ -375,19 +379,27 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
         if (n_gpu != 1 || sam_chr || spool_path || keep_path)
           die("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
               "--spool, --keep-packed: inflate it and pipe it in");
-        if (!bgzf_ingest) {
+        // every input decides for itself: a first inflated byte '>' is a reference FASTA (the FASTA route), anything else
+        // goes where it went before
+        const bool fasta = bgzf_first_byte(in.fd, in.size) == '>';
+        std::unique_ptr<BgzfIngest>& route = fasta ? fasta_ingest : bgzf_ingest;
+        if (!route) {
           device_ready();
-          bgzf_ingest.reset(new BgzfIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, (size_t)1 << 30,
-              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20));
-          trace("count: bgzf route, text arenas open");
+          size_t arena_bytes = (size_t)1 << 30;  // RFX_FASTA_ARENA (bytes, >= 1 MiB, < 4 GiB): a test knob like RFX_BAM_ARENA,
+                                                 // and the way out for genomes whose chromosomes pass the default
+          if (const char* ev = fasta ? getenv("RFX_FASTA_ARENA") : nullptr)
+            arena_bytes = (size_t)std::min(0xFFFFDFFFll, std::max(1ll << 20, atoll(ev)));
+          route.reset(new BgzfIngest(
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, arena_bytes,
+              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20, fasta));
+          trace(fasta ? "count: fasta route, text arenas open" : "count: bgzf route, text arenas open");
         }
         void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
         if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
         (void)madvise(m, in.size, MADV_SEQUENTIAL);
-        bgzf_ingest->feed_mapped((const char*)m, in.size);
+        route->feed_mapped((const char*)m, in.size);
         munmap(m, in.size);
-        trace(("count: " + bgzf_ingest->counts()).c_str());
+        trace(("count: " + route->counts()).c_str());
         if (in.fd > 0) ::close(in.fd);
         continue;
       }
@@ -530,6 +542,7 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   std::vector<std::pair<char*, size_t>> out_ring;
   std::thread out_ring_pinner;
   bgzf_ingest.reset();
+  fasta_ingest.reset();
   if (!ingest && text_ingest) {
     trace(("count: text route, " + text_ingest->timing()).c_str());
     text_ingest.reset();  // (its page-locked text buffers go first)

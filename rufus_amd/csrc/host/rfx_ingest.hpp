@@ -26,6 +26,7 @@
 #include <deque>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -37,6 +38,7 @@
 #include "rfx_packed_cache.hpp"
 #include "rfx_bam_cache.hpp"
 #include "rfx_bai.hpp"
+#include "../rfx_bgzf_core.h"
 
 namespace rfxcli {
 
@@ -1103,12 +1105,21 @@ class TextIngest {
 // handed to the host parser arena by arena (an arena's cut would be wrong to begin with).
 // (weak: the host test harness links the executable's source against a stand-in library that has the text arena but no
 // device; there the two are null and BGZF input is refused by the constructor)
+//
+// bgzip'd FASTA (fasta = true; rufus_amd/csrc/rfx_fasta.hip): the same runs, ring and two arenas, with
+// rfx_text_settle_fasta for the carry -- the cut lies at the arena's last header line, so the last record always moves on --
+// and rfx_text_parse_fasta for the block.  Replaces `zcat ref.fa.gz | jellyfish count ... /dev/stdin` in front of the
+// -e / -f databases (runRufus.sh:77, :115).  Every step parses at least one record or ends the run: a record that does
+// not fit an arena is refused, not cut.  (weak, as the two above: without them the FASTA route refuses with one line)
 #pragma weak rfx_text_append_bgzf
 #pragma weak rfx_text_settle
+#pragma weak rfx_text_settle_fasta
+#pragma weak rfx_text_parse_fasta
 class BgzfIngest {
   rfx_ctx* ctx_;
   std::function<void(rfx_reads*)> sink_;
   size_t piece_;
+  bool fasta_;
   rfx_text* arena_[2] = {nullptr, nullptr};
   uint64_t arena_bytes_;
   struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
@@ -1117,6 +1128,12 @@ class BgzfIngest {
   uint64_t blocks_ = 0, arenas_ = 0, reads_ = 0, appends_ = 0;
 
   [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
+  [[noreturn]] void too_long() const {
+    char msg[160];
+    snprintf(msg, sizeof msg, "rufus_amd jellyfish count: a FASTA sequence does not fit a text arena of %llu bytes (RFX_FASTA_ARENA)",
+             (unsigned long long)arena_bytes_);
+    die(msg);
+  }
 
   void settle_buf(Buf& b) {
     if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
@@ -1129,9 +1146,10 @@ class BgzfIngest {
   void parse_and_sink(rfx_text* t) {
     if (rfx_text_bytes(t)) {
       int strict = 1;
-      rfx_reads* r = rfx_text_parse(t, RFX_PACK_COUNT, 0, &strict);
+      rfx_reads* r = fasta_ ? rfx_text_parse_fasta(t, RFX_PACK_COUNT, &strict) : rfx_text_parse(t, RFX_PACK_COUNT, 0, &strict);
+      if (!r && !strict && fasta_) die("rufus_amd jellyfish count: the inflated text does not begin with '>'");
       if (!r && !strict) not_strict();
-      if (!r) die(std::string("rufus_amd: rfx_text_parse: ") + rfx_last_error());
+      if (!r) die(std::string(fasta_ ? "rufus_amd: rfx_text_parse_fasta: " : "rufus_amd: rfx_text_parse: ") + rfx_last_error());
       reads_ += rfx_reads_count(r);
       ++arenas_;
       sink_(r);
@@ -1141,17 +1159,22 @@ class BgzfIngest {
   }
   uint64_t settle(rfx_text* t, rfx_text* next) {
     uint64_t carried = 0;
-    const int rc = rfx_text_settle(t, next, &carried);
+    const int rc = fasta_ ? rfx_text_settle_fasta(t, next, &carried) : rfx_text_settle(t, next, &carried);
     if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
+    if (fasta_ && rc == RFX_E_RANGE) too_long();  // (one record fills the arena, or its tail does not fit the next)
+    if (fasta_ && rc != RFX_OK)
+      die(std::string("rufus_amd jellyfish count: rfx_text_settle_fasta: ") + rfx_strerror(rc) + " " + rfx_last_error());
     if (rc == RFX_E_FORMAT || rc == RFX_E_RANGE) not_strict();  // (ends inside a record / a "record" longer than an arena)
     if (rc != RFX_OK) die(std::string("rufus_amd: rfx_text_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
     return carried;
   }
 
  public:
-  BgzfIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20)
-      : ctx_(ctx), sink_(std::move(sink)), piece_(piece), arena_bytes_(arena_bytes) {
+  BgzfIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20,
+             bool fasta = false)
+      : ctx_(ctx), sink_(std::move(sink)), piece_(piece), fasta_(fasta), arena_bytes_(arena_bytes) {
     if (!rfx_text_append_bgzf || !rfx_text_settle) die("rufus_amd jellyfish count: this library cannot inflate BGZF input");
+    if (fasta_ && (!rfx_text_settle_fasta || !rfx_text_parse_fasta)) die("rufus_amd jellyfish count: this library cannot read bgzip'd FASTA");
     for (rfx_text*& a : arena_) {
       a = rfx_text_open(ctx_, arena_bytes);
       if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
@@ -1173,8 +1196,9 @@ class BgzfIngest {
   uint64_t reads() const { return reads_; }
   std::string counts() const {
     char b[160];
-    snprintf(b, sizeof b, "bgzf route: %llu blocks in %llu appends, %llu arenas, %llu reads", (unsigned long long)blocks_,
-             (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)reads_);
+    snprintf(b, sizeof b, fasta_ ? "fasta route: %llu blocks in %llu appends, %llu arenas, %llu sequences"
+                                 : "bgzf route: %llu blocks in %llu appends, %llu arenas, %llu reads",
+             (unsigned long long)blocks_, (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)reads_);
     return b;
   }
 
@@ -1205,7 +1229,7 @@ class BgzfIngest {
     auto fill = [&](rfx_text* a) {
       for (; i < runs.size(); ++i) {
         const Run& r = runs[i];
-        if (r.inflated > arena_bytes_) not_strict();  // (cannot happen: a run inflates to <= a quarter of an arena)
+        if (r.inflated > arena_bytes_) fasta_ ? too_long() : not_strict();  // (cannot happen: a run inflates to <= a quarter of an arena)
         if (r.inflated > rfx_text_room(a)) return true;
         Buf& b = ring_[next_buf_];
         next_buf_ = (next_buf_ + 1) % ring_.size();
@@ -1225,7 +1249,7 @@ class BgzfIngest {
       rfx_text* nx = arena_[cur ^ 1];
       const uint64_t before = rfx_text_bytes(t);
       const uint64_t carried = settle(t, nx);
-      if (carried == before) not_strict();  // a full arena without one whole record
+      if (carried == before) fasta_ ? too_long() : not_strict();  // a full arena without one whole record
       more = fill(nx);       // queued, not waited for: the device inflates it beside this arena's count
       parse_and_sink(t);
       cur ^= 1;
@@ -1233,6 +1257,11 @@ class BgzfIngest {
     // the last arena; a file without a final newline gets one
     rfx_text* t = arena_[cur];
     rfx_text* nx = arena_[cur ^ 1];
+    if (fasta_) {  // the file ends here: nothing is carried, and a last line without '\n' is a line
+      (void)settle(t, nullptr);
+      parse_and_sink(t);
+      return;
+    }
     if (settle(t, nx)) {
       const long tk = rfx_text_append(nx, "\n", 1);
       if (tk < 0 || rfx_text_wait(nx, tk) != RFX_OK) die(std::string("rufus_amd: rfx_text_append: ") + rfx_last_error());
@@ -1244,6 +1273,44 @@ class BgzfIngest {
     }
   }
 };
+
+// The first inflated byte of a BGZF file, or -1: what sends a bgzip'd input of `jellyfish count` to the FASTA route ('>')
+// or where it went before (anything else), as is_bam does for BAM.  The first non-empty block is inflated by the host side
+// of rfx_bgzf_core.h (a serial copy as its output policy); -1 when no such block lies whole in the file's first 128 KiB or
+// it does not inflate -- the route that takes the file then says what is wrong with it.
+inline int bgzf_first_byte(int fd, uint64_t size) {
+  std::vector<uint8_t> head((size_t)std::min<uint64_t>(size, 1u << 17));
+  size_t got = 0;
+  while (got < head.size()) {
+    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
+    if (n < 0 && errno == EINTR) continue;
+    if (n <= 0) break;
+    got += (size_t)n;
+  }
+  struct Serial {
+    uint8_t* out;
+    void literal(uint32_t pos, uint32_t byte) { out[pos] = (uint8_t)byte; }
+    void match(uint32_t pos, uint32_t len, uint32_t dist) {
+      for (uint32_t i = 0; i < len; ++i) out[pos + i] = out[pos - dist + i % dist];
+    }
+    void stored(uint32_t pos, const uint8_t* src, uint32_t n) { memcpy(out + pos, src, n); }
+    void end() {}
+  };
+  for (size_t at = 0; at < got;) {
+    uint32_t bsize = 0, pay_off = 0, pay_len = 0, isize = 0, crc = 0;
+    if (bgzf_block_header(head.data() + at, got - at, &bsize, &pay_off, &pay_len, &isize, &crc) != 0) return -1;
+    if (isize) {
+      std::vector<uint8_t> out(isize);
+      std::unique_ptr<bgzf_tables> tables(new bgzf_tables());
+      Serial so{out.data()};
+      const uint8_t* p = head.data() + at + pay_off;
+      if (bgzf_inflate(p, p + pay_len, isize, *tables, so) != BGZF_OK) return -1;
+      return out[0];
+    }
+    at += bsize;
+  }
+  return -1;
+}
 
 // ---- BAM: inflated, its records found and their sequences packed on the device (rfx_bam_*; rufus_amd/csrc/rfx_bam.hip) --
 // Replaces `samtools view -F 3328 X.bam | PassThroughSamCheck CHR | jellyfish count ... /dev/fd/0` (runRufus.sh:599,

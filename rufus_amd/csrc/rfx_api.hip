@@ -935,6 +935,7 @@ uint32_t rfx_reads_count(const rfx_reads* r) { return r ? r->n : 0; }
 uint64_t rfx_reads_bases(const rfx_reads* r) { return r ? r->n_bases : 0; }
 uint64_t rfx_reads_of_length(const rfx_reads* r, uint32_t len) { return r && len < 32 ? r->short_cnt[len] : 0; }
 uint64_t rfx_reads_words(const rfx_reads* r) { return r ? r->n_words : 0; }
+uint32_t rfx_reads_max_len(const rfx_reads* r) { return r ? r->max_len : 0; }
 uint64_t rfx_reads_device_bytes(const rfx_reads* r) {
   if (!r) return 0;
   uint64_t b = r->n_words * 8 + (r->good ? r->n_words * 4 : 0);
