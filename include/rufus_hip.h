@@ -259,6 +259,44 @@ long rfx_text_append_bgzf(rfx_text*, const void* host, uint64_t n);
 int rfx_text_settle(rfx_text* t, rfx_text* next, uint64_t* carried);
 
 /* -------------------------------------------------------------------------------------------
+ * Plain-gzip text in: a deflate stream without BGZF's framing, inflated on the device
+ * Replaces the host inflater in front of the counter, `zcat F.fastq.gz | ...` (runRufus.sh:157-160, :229-232, :974-977),
+ * for the .fastq.gz a sequencer or an archive hands out: gzip members (RFC 1952) of any size with no block index.  The
+ * stream is cut speculatively (rufus_amd/csrc/rfx_gzip_core.h, rfx_gzip.hip): k_gz_find looks behind every nominal
+ * boundary (RFX_GZIP_CHUNK compressed bytes, a power of two >= 1024) for the first bit offset at which a non-final
+ * dynamic block's header checks out; k_gz_walk decodes every chunk from its start to the next chunk's, storing nothing,
+ * for its end bit and size; the host confirms the chain (a chunk that ends where the next starts confirms it; a candidate
+ * the chunk before runs past is dropped; a gap gets a chunk of its own and a second walk); k_gz_inflate decodes the
+ * confirmed chunks into 16-bit values -- a byte, or a reference into the 32 KiB in front of the chunk -- and
+ * k_gz_windows / k_gz_resolve turn those into the arena's bytes; k_gz_crc gives each chunk's CRC, combined on the host
+ * against the member's trailer.
+ *
+ * rfx_gzip_open / rfx_gzip_close: the state of ONE compressed stream -- bit offset, member state, running CRC and ISIZE,
+ * the stream's last 32 KiB (on the device) -- and the device buffers of the kernels.
+ *
+ * rfx_text_append_gzip: host[0, n) are the stream's next bytes (eof != 0: its last).  Returns the inflated bytes
+ * appended to the arena, or a negative error; *consumed = the whole bytes of host that are done with: the caller presents
+ * the rest again, from there, with more behind it.  Only whole confirmed chunks are appended, the longest prefix whose
+ * bytes fit rfx_text_room.  A return of 0 with nothing consumed means the arena is full (rfx_gzip_need() != 0: the room
+ * the next chunk wants; settle and switch) or that no chunk lies whole in host yet (rfx_gzip_need() == 0: present more).
+ * A chunk larger than an empty arena is refused.  A malformed file -- a walk status other than "ok" on a confirmed
+ * chunk, a CRC or ISIZE that does not match, a bad or truncated member header or trailer -- is RFX_E_FORMAT, and
+ * rfx_last_error() reads "rfx_gzip: member M, chunk C: <reason>" (or "rfx_gzip: member M: <reason>").  Waits for the
+ * device: the host needs the walk table.  Called like parse: from one thread, while nobody else appends to the arena.
+ *
+ * rfx_gzip_stats: out[0 .. 8) = candidates found, chunks confirmed, candidates dropped, chunks inserted, walk rounds,
+ * members, batches, bytes out.  rfx_gzip_starts: the confirmed chunks' starts as bit offsets in the whole compressed
+ * stream, the first `cap` of them in out (may be NULL); returns how many there are.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rfx_gzip rfx_gzip;
+rfx_gzip* rfx_gzip_open(rfx_ctx*);
+void rfx_gzip_close(rfx_gzip*);
+long rfx_text_append_gzip(rfx_text*, rfx_gzip*, const void* host, uint64_t n, int eof, uint64_t* consumed);
+int rfx_gzip_stats(const rfx_gzip*, uint64_t out[8]);
+uint64_t rfx_gzip_need(const rfx_gzip*);
+long rfx_gzip_starts(const rfx_gzip*, uint64_t* out, uint64_t cap);
+
+/* -------------------------------------------------------------------------------------------
  * Two bgzip'd mate files in lock step, and the text of the hit records gathered on the device
  * Replaces the two host inflaters in front of the filter, `RUFUS.Filter HashList <(zcat A) <(zcat B) ...`
  * (runRufus.sh:974-977), and, for text that exists only in HBM, the write loop of src/RUFUS.Filter.cpp after :196-277.

@@ -30,6 +30,7 @@ NOT_CHAIN = frozenset((
     "k_set_insert", "k_set_bitmap_packed", "k_records_checksum", "k_records_verify", "k_check_sorted",
     # never launched by the bench's device step: record I/O of the executables, the tiler of long sequences, the assembly stage, ModelDist
     "k_parse_records", "k_format_records", "k_txt_count", "k_txt_lines", "k_txt_reads", "k_txt_pack", "k_txt_nth", "k_bgzf_inflate", "k_bam_guess", "k_bam_walk", "k_bam_repair", "k_bam_starts", "k_bam_fields", "k_bam_table", "k_bam_runs", "k_bam_run_out", "k_bam_pack", "k_bamf_fields", "k_bamf_table", "k_bamf_pack", "k_bam_keep", "k_bam_region", "k_bam_kept_at", "k_bam_hashes", "k_bam_mark", "k_bam_locate", "k_fetch_check", "k_fetch_table", "k_nameset_mark", "k_bamg_sizes", "k_bamg_table", "k_bamh_pick", "k_bamh_table", "k_fa_lines", "k_fa_scatter", "k_fa_reads", "k_fa_pack", "k_fa_last_header", "k_reads_tile_count", "k_reads_tile_table", "k_reads_tile", "k_select_words", "k_select_table", "k_select_copy", "k_gather_sizes", "k_gather_table", "k_gather_copy", "k_compute_pos", "k_annotate", "k_overlap_pool", "k_overlap_score",
+    "k_gz_find", "k_gz_walk", "k_gz_inflate", "k_gz_windows", "k_gz_resolve", "k_gz_crc",
     "k_model_colsum", "k_model_dist", "k_model_rowtot", "k_model_sum", "k_model_terms", "k_model_weights",
 ))
 # the chain's kernels as rocprofv3 names them (bench.K2_CHAIN holds the LABELS of the library's HIP-event brackets, several

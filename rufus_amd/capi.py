@@ -103,6 +103,12 @@ SIGNATURES = {
     "rfx_bgzf_scan": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, u32p, u64p, u64p]),
     "rfx_text_append_bgzf": (C.c_long, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "rfx_text_settle": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
+    "rfx_gzip_open": (C.c_void_p, [C.c_void_p]),
+    "rfx_gzip_close": (None, [C.c_void_p]),
+    "rfx_text_append_gzip": (C.c_long, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, u64p]),
+    "rfx_gzip_stats": (C.c_int, [C.c_void_p, u64p]),
+    "rfx_gzip_need": (C.c_uint64, [C.c_void_p]),
+    "rfx_gzip_starts": (C.c_long, [C.c_void_p, u64p, C.c_uint64]),
     "rfx_text_settle_fasta": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
     "rfx_text_parse_fasta": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "rfx_text_records": (C.c_int, [C.c_void_p, u64p]),
@@ -757,6 +763,54 @@ class TextArena:
         if self._h:
             lib().rfx_text_close(self._h)
             self._h = None
+
+
+class GzipStream:
+    """The state of ONE plain-gzip stream that is inflated on the device into text arenas (rfx_gzip_*: the stream's bit
+    offset, member state, running CRC and last 32 KiB).  RFX_GZIP_CHUNK is read when the stream is opened."""
+
+    STATS = ("found", "confirmed", "dropped", "inserted", "rounds", "members", "batches", "bytes")
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = lib().rfx_gzip_open(ctx._h)
+        if not self._h:
+            raise RufusError("rfx_gzip_open failed: " + lib().rfx_last_error().decode())
+
+    def append(self, arena: "TextArena", data: bytes, eof: bool):
+        """(inflated bytes appended to `arena`, bytes of `data` that are done with) of rfx_text_append_gzip.  (0, 0): the
+        arena is full (need() != 0) or `data` holds no whole chunk yet (need() == 0)."""
+        used = C.c_uint64(0)
+        got = lib().rfx_text_append_gzip(arena._h, self._h, data, len(data), 1 if eof else 0, C.byref(used))
+        if got < 0:
+            _check(int(got), "rfx_text_append_gzip")
+        return int(got), int(used.value)
+
+    def need(self) -> int:
+        return int(lib().rfx_gzip_need(self._h))
+
+    def stats(self) -> dict:
+        out = (C.c_uint64 * 8)()
+        _check(lib().rfx_gzip_stats(self._h, out), "rfx_gzip_stats")
+        return dict(zip(self.STATS, (int(x) for x in out)))
+
+    def starts(self):
+        """The confirmed chunks' starts: bit offsets in the whole compressed stream."""
+        n = int(lib().rfx_gzip_starts(self._h, None, 0))
+        out = (C.c_uint64 * max(n, 1))()
+        lib().rfx_gzip_starts(self._h, out, n)
+        return [int(x) for x in out[:n]]
+
+    def close(self):
+        if self._h:
+            lib().rfx_gzip_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class NameSet:

@@ -335,6 +335,13 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // the FASTA carry and parse (rfx_ingest.hpp BgzfIngest, fasta; csrc/rfx_fasta.hip).  Replaces the `zcat ref.fa.gz |`
   // in front of the -e / -f databases (runRufus.sh:77, :115).
   std::unique_ptr<BgzfIngest> fasta_ingest;
+  // A plain-gzip FASTQ (a regular file that begins 1f 8b 08 and is not BGZF: what a sequencer or an archive hands out) is
+  // inflated on the device too (rfx_ingest.hpp GzipIngest; csrc/rfx_gzip.hip: the stream cut speculatively, a chain rule on
+  // the host).  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160, :229-232).  On by default since it was measured
+  // against the pipe on a whole sample (5.4 s against 58 s); RFX_GZIP_DEVICE=0 sends plain gzip where
+  // it went before.
+  const bool gzip_device = !(getenv("RFX_GZIP_DEVICE") && atoi(getenv("RFX_GZIP_DEVICE")) == 0);
+  std::unique_ptr<GzipIngest> gzip_ingest;
   // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, neither --sam nor --spool;
   // --keep-packed with one input leaves the BAM-kind cache (rfx_bam_cache.hpp).
   std::unique_ptr<BamIngest> bam_ingest;
@@ -400,6 +407,35 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
         route->feed_mapped((const char*)m, in.size);
         munmap(m, in.size);
         trace(("count: " + route->counts()).c_str());
+        if (in.fd > 0) ::close(in.fd);
+        continue;
+      }
+      if (gzip_device && is_plain_gzip(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
+        // (the refusals below wait for the opener thread first: exit() must not run the HIP runtime's exit handlers while
+        // that thread is still inside the runtime's start)
+        if (n_gpu != 1 || sam_chr || spool_path || keep_path) device_ready();
+        if (n_gpu != 1 || sam_chr || spool_path || keep_path)
+          die("rufus_amd jellyfish count: plain-gzip input is inflated on the device, which needs one device and none of --sam, "
+              "--spool, --keep-packed: inflate it and pipe it in");
+        if (gzip_first_byte(in.fd, in.size) != '@') device_ready();
+        if (gzip_first_byte(in.fd, in.size) != '@')
+          die(std::string("rufus_amd jellyfish count: '") + in.path + "' is plain gzip and its first inflated byte is not '@': only "
+              "FASTQ is inflated on the device; pipe anything else in through zcat");
+        if (!gzip_ingest) {
+          device_ready();
+          size_t arena_bytes = (size_t)1 << 30;  // RFX_GZIP_ARENA (a test knob, bytes, >= 1 MiB, < 4 GiB): small files cross arenas
+          if (const char* ev = getenv("RFX_GZIP_ARENA")) arena_bytes = (size_t)std::min(0xFFFFDFFFll, std::max(1ll << 20, atoll(ev)));
+          gzip_ingest.reset(new GzipIngest(
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, arena_bytes,
+              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)128 << 20));
+          trace("count: gzip route, text arenas open");
+        }
+        void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
+        if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
+        (void)madvise(m, in.size, MADV_SEQUENTIAL);
+        gzip_ingest->feed_mapped((const char*)m, in.size);
+        munmap(m, in.size);
+        trace(("count: " + gzip_ingest->counts()).c_str());
         if (in.fd > 0) ::close(in.fd);
         continue;
       }
@@ -492,6 +528,10 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
             if (got == head.size()) break;
           }
           head.resize(got);
+          if (gzip_device && got >= 3 && (unsigned char)head[0] == 0x1f && (unsigned char)head[1] == 0x8b && head[2] == 0x08) {
+            device_ready();  // (as above: no exit() beside the opener thread)
+            die("rufus_amd jellyfish count: gzip input needs a regular file, not a pipe: the file is mapped; or inflate it and pipe the text in");
+          }
           done = got == 0 || ingest->feed_stream(in.fd, head);
           if (!done && spool_path) die("rufus_amd jellyfish count: --spool needs SAM (--sam) or strict 4-line FASTQ on the pipe");
           if (!done) {
@@ -543,6 +583,7 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   std::thread out_ring_pinner;
   bgzf_ingest.reset();
   fasta_ingest.reset();
+  gzip_ingest.reset();
   if (!ingest && text_ingest) {
     trace(("count: text route, " + text_ingest->timing()).c_str());
     text_ingest.reset();  // (its page-locked text buffers go first)

@@ -626,6 +626,16 @@ inline bool is_bgzf(int fd, bool regular, uint64_t size) {
   return rfx_bgzf_scan(head.data(), got, 1, &nb, nullptr, nullptr) == RFX_OK && nb == 1;
 }
 
+// Is the open file plain gzip?  A regular file that begins 1f 8b 08 (a gzip member, deflate) and is not BGZF: what a
+// sequencer or an archive hands out as .fastq.gz.  What sends an input of `jellyfish count` down the speculative
+// device-inflate route (rfx_ingest.hpp GzipIngest).
+inline bool is_plain_gzip(int fd, bool regular, uint64_t size) {
+  if (!regular || size < 18) return false;
+  unsigned char h[3] = {0, 0, 0};
+  if (::pread(fd, h, 3, 0) != 3 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 0x08) return false;
+  return !is_bgzf(fd, regular, size);
+}
+
 // RFX_CLI_TRACE=1: wall-clock marks of a tool's phases on stderr (scratch/cli_scale.sh reads them)
 inline void trace(const char* what) {
   static const bool on = getenv("RFX_CLI_TRACE") != nullptr;

@@ -39,6 +39,7 @@
 #include "rfx_bam_cache.hpp"
 #include "rfx_bai.hpp"
 #include "../rfx_bgzf_core.h"
+#include "../rfx_gzip_core.h"
 
 namespace rfxcli {
 
@@ -1310,6 +1311,161 @@ inline int bgzf_first_byte(int fd, uint64_t size) {
     at += bsize;
   }
   return -1;
+}
+
+// ---- plain-gzip FASTQ: inflated on the device (rfx_text_append_gzip; rufus_amd/csrc/rfx_gzip.hip) -------------------------
+// Replaces `zcat F.fastq.gz | jellyfish count ... /dev/stdin` (runRufus.sh:157-160, :229-232) for files that are gzip but
+// not BGZF: what a sequencer or an archive hands out.  BgzfIngest's two arenas, settle (the carry of a record that an arena
+// cuts), parse and sink; what differs is the fill: the stream has no block index, so the mapped file is PRESENTED, a piece
+// at a time, and rfx_text_append_gzip says how many of the piece's bytes are done with -- it appends whole confirmed chunks
+// only.  Nothing consumed and nothing appended is either a full arena (rfx_gzip_need() != 0: settle and switch) or a piece
+// that holds no whole chunk (a stream of stored or fixed blocks has no chunk starts to find: the piece doubles, up to the
+// rest of the file).  The append waits for the device, so the inflate of the next arena does not overlap this arena's
+// count.  (weak: as BgzfIngest's)
+#pragma weak rfx_gzip_open
+#pragma weak rfx_gzip_close
+#pragma weak rfx_text_append_gzip
+#pragma weak rfx_gzip_need
+#pragma weak rfx_gzip_stats
+class GzipIngest {
+  rfx_ctx* ctx_;
+  std::function<void(rfx_reads*)> sink_;
+  size_t piece_;
+  rfx_text* arena_[2] = {nullptr, nullptr};
+  uint64_t arenas_ = 0, reads_ = 0, appends_ = 0, files_ = 0;
+  uint64_t stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
+  void parse_and_sink(rfx_text* t) {
+    if (rfx_text_bytes(t)) {
+      int strict = 1;
+      rfx_reads* r = rfx_text_parse(t, RFX_PACK_COUNT, 0, &strict);
+      if (!r && !strict) not_strict();
+      if (!r) die(std::string("rufus_amd: rfx_text_parse: ") + rfx_last_error());
+      reads_ += rfx_reads_count(r);
+      ++arenas_;
+      sink_(r);
+    }
+    rfx_text_reset(t);
+  }
+  uint64_t settle(rfx_text* t, rfx_text* next) {
+    uint64_t carried = 0;
+    const int rc = rfx_text_settle(t, next, &carried);
+    if (rc == RFX_E_FORMAT || rc == RFX_E_RANGE) not_strict();  // (ends inside a record / a "record" longer than an arena)
+    if (rc != RFX_OK) die(std::string("rufus_amd: rfx_text_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
+    return carried;
+  }
+
+ public:
+  GzipIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 128u << 20)
+      : ctx_(ctx), sink_(std::move(sink)), piece_(std::max<size_t>(piece, 64)) {
+    if (!rfx_gzip_open || !rfx_gzip_close || !rfx_text_append_gzip || !rfx_gzip_need || !rfx_gzip_stats || !rfx_text_settle)
+      die("rufus_amd jellyfish count: this library cannot inflate plain-gzip input");
+    for (rfx_text*& a : arena_) {
+      a = rfx_text_open(ctx_, arena_bytes);
+      if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
+    }
+  }
+  ~GzipIngest() {
+    for (rfx_text* a : arena_) rfx_text_close(a);
+  }
+  uint64_t reads() const { return reads_; }
+  std::string counts() const {
+    char b[320];
+    snprintf(b, sizeof b,
+             "gzip route: %llu files, %llu appends, %llu arenas, %llu reads; chunks found %llu, confirmed %llu, dropped %llu, "
+             "inserted %llu, rounds %llu, members %llu, batches %llu, bytes %llu",
+             (unsigned long long)files_, (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)reads_,
+             (unsigned long long)stats_[0], (unsigned long long)stats_[1], (unsigned long long)stats_[2], (unsigned long long)stats_[3],
+             (unsigned long long)stats_[4], (unsigned long long)stats_[5], (unsigned long long)stats_[6], (unsigned long long)stats_[7]);
+    return b;
+  }
+
+  // A whole mapped plain-gzip file.  Dies on what rfx_text_append_gzip refuses (its "rfx_gzip:" text) and on text that is
+  // not strict 4-line FASTQ.
+  void feed_mapped(const char* m, size_t size) {
+    rfx_gzip* gz = rfx_gzip_open(ctx_);
+    if (!gz) die(std::string("rufus_amd: rfx_gzip_open: ") + rfx_last_error());
+    ++files_;
+    int cur = 0;
+    size_t at = 0, piece = piece_;
+    uint64_t fresh = 0;  // bytes this file has put into the current arena
+    double ratio = 4.0;  // inflated / compressed bytes, the largest seen
+    auto next_arena = [&] {  // the arena's tail moves on, it is counted, the other one is filled
+      rfx_text* a = arena_[cur];
+      const uint64_t before = rfx_text_bytes(a);
+      if (settle(a, arena_[cur ^ 1]) == before) not_strict();  // a full arena without one whole record
+      parse_and_sink(a);
+      cur ^= 1;
+      fresh = 0;
+    };
+    while (at < size) {
+      const size_t n = std::min(piece, size - at);
+      // a piece that will not fit what is left of the arena would be found and walked twice: the arena goes as it is
+      if (fresh && (double)n * ratio > (double)rfx_text_room(arena_[cur])) next_arena();
+      rfx_text* a = arena_[cur];
+      uint64_t used = 0;
+      const long got = rfx_text_append_gzip(a, gz, m + at, n, at + n == size, &used);
+      ++appends_;
+      if (got == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_gzip:", 9)) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
+      if (got < 0) die(std::string("rufus_amd: rfx_text_append_gzip: ") + rfx_strerror((int)got) + " " + rfx_last_error());
+      at += (size_t)used;
+      fresh += (uint64_t)got;
+      if (used >= 65536) ratio = std::max(ratio, 1.05 * (double)got / (double)used);
+      if (got || used) continue;
+      if (rfx_gzip_need(gz)) {  // the arena is full
+        next_arena();
+      } else if (n == size - at) {
+        die("rufus_amd jellyfish count: rfx_text_append_gzip made no progress at the end of the file");  // (it reports such a file itself)
+      } else {
+        piece *= 2;  // no whole chunk in the piece
+      }
+    }
+    uint64_t st[8];
+    if (rfx_gzip_stats(gz, st) == RFX_OK)
+      for (int i = 0; i < 8; ++i) stats_[i] += st[i];
+    rfx_gzip_close(gz);
+    // the last arena; a file without a final newline gets one
+    rfx_text* t = arena_[cur];
+    rfx_text* nx = arena_[cur ^ 1];
+    if (settle(t, nx)) {
+      const long tk = rfx_text_append(nx, "\n", 1);
+      if (tk < 0 || rfx_text_wait(nx, tk) != RFX_OK) die(std::string("rufus_amd: rfx_text_append: ") + rfx_last_error());
+      parse_and_sink(t);
+      (void)settle(nx, nullptr);
+      parse_and_sink(nx);
+    } else {
+      parse_and_sink(t);
+    }
+  }
+};
+
+// The first inflated byte of a plain-gzip file, or -1: what lets `jellyfish count` refuse anything but FASTQ ('@') before
+// the device sees it.  The first member's header, then the host side of rfx_gzip_core.h over the file's first 64 KiB with
+// an output policy that keeps byte 0.
+inline int gzip_first_byte(int fd, uint64_t size) {
+  std::vector<uint8_t> head((size_t)std::min<uint64_t>(size, 1u << 16));
+  size_t got = 0;
+  while (got < head.size()) {
+    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
+    if (n < 0 && errno == EINTR) continue;
+    if (n <= 0) break;
+    got += (size_t)n;
+  }
+  struct First {
+    int byte = -1;
+    void literal(uint64_t pos, uint32_t b) { if (pos == 0) byte = (int)b; }
+    void match(uint64_t, uint32_t, uint32_t) {}
+    void stored(uint64_t pos, const uint8_t* src, uint32_t) { if (pos == 0) byte = src[0]; }
+    void end() {}
+  };
+  uint64_t hl = 0;
+  if (gz_member_header(head.data(), got, &hl) != 0) return -1;
+  std::unique_ptr<bgzf_tables> tables(new bgzf_tables());
+  First f;
+  gz_result r;
+  gz_run(head.data(), head.data() + got, hl * 8u, hl * 8u + 1u, true, ~0ull, *tables, f, r);  // (the first block, or what of it is there)
+  return f.byte;
 }
 
 // ---- BAM: inflated, its records found and their sequences packed on the device (rfx_bam_*; rufus_amd/csrc/rfx_bam.hip) --

@@ -593,6 +593,10 @@ struct text_bam {
 rfx_ctx* text_ctx(rfx_text* t);
 text_bam& text_bam_of(rfx_text* t);
 int text_cut(rfx_text* t, rfx_text* next, uint64_t cut, uint64_t* carried, const char* who);
+// What rfx_gzip.hip needs of an arena: text_claim waits for the arena's appends (as text_ready does) and reports where the
+// next byte goes -- arena + *used, room cap - used; text_grow makes the n bytes written there part of the text.
+int text_claim(rfx_text* t, rfx_ctx** c, uint8_t** arena, uint64_t* cap, uint64_t* used);
+void text_grow(rfx_text* t, uint64_t n);
 // k_gather_copy (rfx_gather.hip) queued on the ctx stream for rfx_bam_gather: record o of the selection is the arena's
 // bytes from src_off[o], dst_off[o + 1] - dst_off[o] of them, and goes to byte dst_off[o] of `out` (dst_off[n_sel] =
 // n_bytes > 0; `out` holds n_bytes rounded up to a dword).  Every record is at least four bytes long and a record that

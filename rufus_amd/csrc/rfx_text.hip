@@ -324,6 +324,18 @@ int text_ready(rfx_text* t, rfx_ctx** c, const uint8_t** arena, uint64_t* used) 
   return RFX_OK;
 }
 
+int text_claim(rfx_text* t, rfx_ctx** c, uint8_t** arena, uint64_t* cap, uint64_t* used) {
+  const uint8_t* a = nullptr;
+  if (const int rc = text_ready(t, c, &a, used)) return rc;
+  *arena = t->arena;
+  *cap = t->cap;
+  return RFX_OK;
+}
+void text_grow(rfx_text* t, uint64_t n) {
+  std::lock_guard<std::mutex> g(t->mu);
+  t->used += n;
+}
+
 rfx_ctx* text_ctx(rfx_text* t) { return t->ctx; }
 text_bam& text_bam_of(rfx_text* t) { return t->bam; }
 

@@ -239,10 +239,66 @@ def bam_read_blocks(ctx: capi.Context, data: bytes, exclude_flags: int = 3328, a
         yield blk, runs, hdr["names"]
 
 
+def is_plain_gzip(data: bytes) -> bool:
+    """A gzip file (magic 1f 8b, deflate) that is not BGZF: what a sequencer or an archive hands out as .fastq.gz."""
+    if data[:3] != b"\x1f\x8b\x08":
+        return False
+    try:
+        return capi.bgzf_scan(data[:1 << 16], 1)[0] == 0
+    except capi.RufusError:
+        return True
+
+
+def gzip_read_blocks(ctx: capi.Context, data: bytes, arena_bytes: int = 256 << 20, piece: int = 128 << 20):
+    """The reads of a plain-gzip FASTQ file as count blocks, an arena at a time, inflated on the device
+    (capi.GzipStream.append: the stream cut speculatively, a chain rule on the host; TextArena.settle / parse): what
+    `zcat F.fastq.gz |` hands the counter.  Strict 4-line FASTQ only.  The caller frees the blocks."""
+    arenas = [capi.TextArena(ctx, arena_bytes), capi.TextArena(ctx, arena_bytes)]
+    gz = capi.GzipStream(ctx)
+    try:
+        cur, at = 0, 0
+
+        def sink(a):
+            if a.bytes:
+                block = a.parse(capi.PACK_COUNT)
+                if block is None:
+                    raise ValueError("compressed input must be strict 4-line FASTQ")
+                yield block
+            a.reset()
+
+        while at < len(data):
+            a = arenas[cur]
+            n = min(piece, len(data) - at)
+            got, used = gz.append(a, data[at:at + n], at + n == len(data))
+            at += used
+            if got or used:
+                continue
+            if gz.need():  # the arena is full
+                before = a.bytes
+                if a.settle(arenas[cur ^ 1]) == before:
+                    raise ValueError("compressed input must be strict 4-line FASTQ")
+                yield from sink(a)
+                cur ^= 1
+            else:
+                piece *= 2
+        a, nx = arenas[cur], arenas[cur ^ 1]
+        if a.settle(nx):  # a file without a final newline gets one
+            nx.append(b"\n")
+            yield from sink(a)
+            nx.settle(None)
+            yield from sink(nx)
+        else:
+            yield from sink(a)
+    finally:
+        gz.close()
+        for a in arenas:
+            a.close()
+
+
 def jellyfish_count(ctx: capi.Context, inputs, k: int, size: int, canonical: bool = True, lower: int = 0,
                     upper: int = 2**64 - 1, out: str | None = None, capacity: int = 0, argv=(),
                     mode: int = capi.COUNT_AUTO, region=None, index: bytes | None = None) -> JhashFile:
-    """Count the k-mers of FASTA/FASTQ files (paths or bytes); a BAM file is counted as `samtools view -F 3328` of it, with
+    """Count the k-mers of FASTA/FASTQ files (paths or bytes; a plain-gzip FASTQ is inflated on the device); a BAM file is counted as `samtools view -F 3328` of it, with
     `region` as `samtools view -F 3328 X.bam REGION` (ONE BAM input; index: its .bai's bytes, or None for the whole walk)."""
     if region is not None and len(inputs) != 1:
         raise ValueError("region goes with ONE BAM input")
@@ -259,6 +315,13 @@ def jellyfish_count(ctx: capi.Context, inputs, k: int, size: int, canonical: boo
                 continue
             if region is not None:
                 raise ValueError("region goes with a BAM input: only a BAM's records carry a position")
+            if is_plain_gzip(bytes(data)):  # (FASTQ: anything else wants `zcat`, as the executable says)
+                for block in gzip_read_blocks(ctx, bytes(data)):
+                    try:
+                        table.add(block)
+                    finally:
+                        block.free()
+                continue
             seqs = parse_sequences(bytes(data))
             block = ctx.upload(capi.PackedReads.from_reads(seqs, flags=capi.PACK_COUNT))
             try:
