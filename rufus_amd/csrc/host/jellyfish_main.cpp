@@ -33,19 +33,12 @@ static double secs_since(std::chrono::steady_clock::time_point t0) {
 // that says --bam instead of the FASTQ one.
 static bool is_bam(int fd, uint64_t size) {
   if (!rfx_bam_header) return false;
-  std::vector<char> head((size_t)std::min<uint64_t>(size, 1u << 16));
-  size_t got = 0;
-  while (got < head.size()) {
-    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
-    if (n < 0 && errno == EINTR) continue;
-    if (n <= 0) break;
-    got += (size_t)n;
-  }
+  const std::vector<uint8_t> head = read_head(fd, size, 1u << 16);
   int complete = 0;
   int32_t n_ref = 0;
   uint64_t names_bytes = 0, first_block = 0;
   uint32_t skip = 0;
-  return rfx_bam_header(head.data(), got, &complete, &n_ref, nullptr, 0, &names_bytes, &first_block, &skip) == RFX_OK;
+  return rfx_bam_header(head.data(), head.size(), &complete, &n_ref, nullptr, 0, &names_bytes, &first_block, &skip) == RFX_OK;
 }
 
 static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
@@ -181,6 +174,12 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   });
   auto device_ready = [&] {
     if (opener.joinable()) opener.join();
+  };
+  // What the main thread refuses while it looks at the inputs: exit() must not run the HIP runtime's exit handlers while
+  // the opener is still inside the runtime's start (the heap is found damaged and the exit status is an abort's, not 1)
+  auto refuse = [&](const std::string& msg) {
+    device_ready();
+    die(msg);
   };
   const bool sync_open = getenv("RFX_SYNC_OPEN") != nullptr;  // (A/B: the device opened before anything else, as until round 6)
   const auto t_init = std::chrono::steady_clock::now();
@@ -345,98 +344,77 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, neither --sam nor --spool;
   // --keep-packed with one input leaves the BAM-kind cache (rfx_bam_cache.hpp).
   std::unique_ptr<BamIngest> bam_ingest;
-  if (bam_chr && n_gpu != 1) die(bam_alone);
+  if (bam_chr && n_gpu != 1) refuse(bam_alone);
+  // a regular input of one of the three routes above: mapped, fed whole, unmapped, the route's counts traced
+  auto feed_whole = [&](auto& route, Input& in) {
+    void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
+    if (m == MAP_FAILED) refuse(std::string("cannot map '") + in.path + "': " + strerror(errno));
+    (void)madvise(m, in.size, MADV_SEQUENTIAL);
+    route.feed_mapped((const char*)m, in.size);
+    munmap(m, in.size);
+    trace(("count: " + route.counts()).c_str());
+    if (in.fd > 0) ::close(in.fd);
+  };
   {
     for (Input& in : inputs) {
       bool done = false;
       if (bam_chr) {
-        if (!in.regular) die("rufus_amd jellyfish count: --bam needs a regular file, not a pipe: the BAM is mapped");
-        if (!is_bgzf(in.fd, in.regular, in.size)) die(std::string("rufus_amd jellyfish count: --bam: '") + in.path + "' is not BGZF");
+        if (!in.regular) refuse("rufus_amd jellyfish count: --bam needs a regular file, not a pipe: the BAM is mapped");
+        if (!is_bgzf(in.fd, in.regular, in.size)) refuse(std::string("rufus_amd jellyfish count: --bam: '") + in.path + "' is not BGZF");
         if (!bam_ingest) {
           device_ready();
-          size_t arena_bytes = (size_t)1 << 30;  // RFX_BAM_ARENA (a test knob, bytes, >= 1 MiB): small files cross arenas
-          if (const char* ev = getenv("RFX_BAM_ARENA")) arena_bytes = (size_t)std::max(1ll << 20, atoll(ev));
           bam_ingest.reset(new BamIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, bam_exclude, arena_bytes,
-              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20));
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, bam_exclude, env_arena("RFX_BAM_ARENA"), env_piece((size_t)8 << 20)));
           if (keep_path) {
             const int kfd = ::open(keep_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (kfd < 0) die(std::string("Can't open the packed-read cache '") + keep_path + "'");
+            if (kfd < 0) refuse(std::string("Can't open the packed-read cache '") + keep_path + "'");
             bam_ingest->set_keep_packed(kfd, keep_minq);
           }
           if (bam_region) bam_ingest->set_region(bam_region, in.path);
           trace("count: bam route, arenas open");
         }
-        void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
-        if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
-        (void)madvise(m, in.size, MADV_SEQUENTIAL);
-        bam_ingest->feed_mapped((const char*)m, in.size);
-        munmap(m, in.size);
-        trace(("count: " + bam_ingest->counts()).c_str());
+        feed_whole(*bam_ingest, in);
         if (keep_path) {  // (one input: checked above) the file is a cache only from here on
           bam_ingest->finish_keep_packed();
           trace(("count: " + bam_ingest->keep_counts()).c_str());
         }
-        if (in.fd > 0) ::close(in.fd);
         continue;
       }
       if (is_bgzf(in.fd, in.regular, in.size) && is_bam(in.fd, in.size))
-        die(std::string("rufus_amd jellyfish count: '") + in.path + "' is a BAM file: count it with --bam CHR_FILE");
+        refuse(std::string("rufus_amd jellyfish count: '") + in.path + "' is a BAM file: count it with --bam CHR_FILE");
       if (is_bgzf(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
         if (n_gpu != 1 || sam_chr || spool_path || keep_path)
-          die("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
-              "--spool, --keep-packed: inflate it and pipe it in");
+          refuse("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
+                 "--spool, --keep-packed: inflate it and pipe it in");
         // every input decides for itself: a first inflated byte '>' is a reference FASTA (the FASTA route), anything else
         // goes where it went before
         const bool fasta = bgzf_first_byte(in.fd, in.size) == '>';
         std::unique_ptr<BgzfIngest>& route = fasta ? fasta_ingest : bgzf_ingest;
         if (!route) {
           device_ready();
-          size_t arena_bytes = (size_t)1 << 30;  // RFX_FASTA_ARENA (bytes, >= 1 MiB, < 4 GiB): a test knob like RFX_BAM_ARENA,
-                                                 // and the way out for genomes whose chromosomes pass the default
-          if (const char* ev = fasta ? getenv("RFX_FASTA_ARENA") : nullptr)
-            arena_bytes = (size_t)std::min(0xFFFFDFFFll, std::max(1ll << 20, atoll(ev)));
+          // (the FASTQ mode has no arena knob; RFX_FASTA_ARENA: >= 1 MiB, < 4 GiB)
           route.reset(new BgzfIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, arena_bytes,
-              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20, fasta));
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, env_arena(fasta ? "RFX_FASTA_ARENA" : nullptr, 1ll << 20, ARENA_MAX),
+              env_piece((size_t)8 << 20), fasta));
           trace(fasta ? "count: fasta route, text arenas open" : "count: bgzf route, text arenas open");
         }
-        void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
-        if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
-        (void)madvise(m, in.size, MADV_SEQUENTIAL);
-        route->feed_mapped((const char*)m, in.size);
-        munmap(m, in.size);
-        trace(("count: " + route->counts()).c_str());
-        if (in.fd > 0) ::close(in.fd);
+        feed_whole(*route, in);
         continue;
       }
       if (gzip_device && is_plain_gzip(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
-        // (the refusals below wait for the opener thread first: exit() must not run the HIP runtime's exit handlers while
-        // that thread is still inside the runtime's start)
-        if (n_gpu != 1 || sam_chr || spool_path || keep_path) device_ready();
         if (n_gpu != 1 || sam_chr || spool_path || keep_path)
-          die("rufus_amd jellyfish count: plain-gzip input is inflated on the device, which needs one device and none of --sam, "
-              "--spool, --keep-packed: inflate it and pipe it in");
-        if (gzip_first_byte(in.fd, in.size) != '@') device_ready();
+          refuse("rufus_amd jellyfish count: plain-gzip input is inflated on the device, which needs one device and none of --sam, "
+                 "--spool, --keep-packed: inflate it and pipe it in");
         if (gzip_first_byte(in.fd, in.size) != '@')
-          die(std::string("rufus_amd jellyfish count: '") + in.path + "' is plain gzip and its first inflated byte is not '@': only "
-              "FASTQ is inflated on the device; pipe anything else in through zcat");
+          refuse(std::string("rufus_amd jellyfish count: '") + in.path + "' is plain gzip and its first inflated byte is not '@': only "
+                 "FASTQ is inflated on the device; pipe anything else in through zcat");
         if (!gzip_ingest) {
           device_ready();
-          size_t arena_bytes = (size_t)1 << 30;  // RFX_GZIP_ARENA (a test knob, bytes, >= 1 MiB, < 4 GiB): small files cross arenas
-          if (const char* ev = getenv("RFX_GZIP_ARENA")) arena_bytes = (size_t)std::min(0xFFFFDFFFll, std::max(1ll << 20, atoll(ev)));
           gzip_ingest.reset(new GzipIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, arena_bytes,
-              getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)128 << 20));
+              ctx, [&](rfx_reads* r) { sink_to(0, r); }, env_arena("RFX_GZIP_ARENA", 1ll << 20, ARENA_MAX), env_piece((size_t)128 << 20)));
           trace("count: gzip route, text arenas open");
         }
-        void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
-        if (m == MAP_FAILED) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
-        (void)madvise(m, in.size, MADV_SEQUENTIAL);
-        gzip_ingest->feed_mapped((const char*)m, in.size);
-        munmap(m, in.size);
-        trace(("count: " + gzip_ingest->counts()).c_str());
-        if (in.fd > 0) ::close(in.fd);
+        feed_whole(*gzip_ingest, in);
         continue;
       }
       if (device_text && in.regular && in.size > 0) {
@@ -450,7 +428,7 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
                 lr.close_input();
                 sequential(lr);
               },
-              (size_t)1 << 30, getenv("RFX_INGEST_PIECE") ? (size_t)std::max(1024ll, atoll(getenv("RFX_INGEST_PIECE"))) : (size_t)8 << 20));
+              (size_t)1 << 30, env_piece((size_t)8 << 20)));
           trace("count: text arenas open, copiers up");
         }
         if (!getenv("RFX_TEXT_PREAD")) {  // (the mapped route; RFX_TEXT_PREAD=1: the workers pread their ranges -- faster for one
@@ -480,15 +458,15 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
           ingest->set_sam(sam_chr != nullptr);
           if (spool_path) {
             const int sfd = ::open(spool_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (sfd < 0) die(std::string("Can't open spool file '") + spool_path + "'");
+            if (sfd < 0) refuse(std::string("Can't open spool file '") + spool_path + "'");
             ingest->set_spool(sfd);
           }
           if (keep_path) {
             const int kfd = ::open(keep_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (kfd < 0) die(std::string("Can't open the packed-read cache '") + keep_path + "'");
+            if (kfd < 0) refuse(std::string("Can't open the packed-read cache '") + keep_path + "'");
             ingest->set_keep_packed(kfd, keep_minq);
           }
-          if (const char* ev = getenv("RFX_INGEST_PIECE")) ingest->set_piece_bytes((size_t)std::max(1024ll, atoll(ev)));
+          if (getenv("RFX_INGEST_PIECE")) ingest->set_piece_bytes(env_piece(0));
           if (prealloc.growing())
             ingest->on_stream_bytes = [&prealloc, prealloc_frac, prealloc_min](uint64_t so_far) {
               if (so_far > prealloc_min) prealloc.want((uint64_t)((double)so_far * prealloc_frac));
@@ -522,18 +500,16 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
           for (;;) {
             const ssize_t n = ::read(in.fd, head.data() + got, head.size() - got);
             if (n < 0 && errno == EINTR) continue;
-            if (n < 0) die(std::string("read error on input: ") + strerror(errno));
+            if (n < 0) refuse(std::string("read error on input: ") + strerror(errno));
             if (n == 0) break;
             got += (size_t)n;
             if (got == head.size()) break;
           }
           head.resize(got);
-          if (gzip_device && got >= 3 && (unsigned char)head[0] == 0x1f && (unsigned char)head[1] == 0x8b && head[2] == 0x08) {
-            device_ready();  // (as above: no exit() beside the opener thread)
-            die("rufus_amd jellyfish count: gzip input needs a regular file, not a pipe: the file is mapped; or inflate it and pipe the text in");
-          }
+          if (gzip_device && got >= 3 && (unsigned char)head[0] == 0x1f && (unsigned char)head[1] == 0x8b && head[2] == 0x08)
+            refuse("rufus_amd jellyfish count: gzip input needs a regular file, not a pipe: the file is mapped; or inflate it and pipe the text in");
           done = got == 0 || ingest->feed_stream(in.fd, head);
-          if (!done && spool_path) die("rufus_amd jellyfish count: --spool needs SAM (--sam) or strict 4-line FASTQ on the pipe");
+          if (!done && spool_path) refuse("rufus_amd jellyfish count: --spool needs SAM (--sam) or strict 4-line FASTQ on the pipe");
           if (!done) {
             LineReader lr;
             lr.preload(head.data(), head.size());

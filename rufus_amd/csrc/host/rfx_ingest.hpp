@@ -25,6 +25,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -43,7 +44,26 @@
 
 namespace rfxcli {
 
-// The stream cutter's line count.  Fast pass: newlines of [p, e) and how many of them are blank lines (a '\n' at a
+// pread until `want` bytes are there, the file ends or a read fails (EINTR: again).  Returns the bytes read; errno is the
+// failed read's.
+inline size_t pread_all(int fd, void* buf, size_t want, uint64_t off) {
+  size_t got = 0;
+  while (got < want) {
+    const ssize_t n = ::pread(fd, (char*)buf + got, want - got, (off_t)(off + got));
+    if (n < 0 && errno == EINTR) continue;
+    if (n <= 0) break;
+    got += (size_t)n;
+  }
+  return got;
+}
+// The first min(size, cap) bytes of an open regular file, or as many of them as can be read: what the routes sniff.
+inline std::vector<uint8_t> read_head(int fd, uint64_t size, size_t cap) {
+  std::vector<uint8_t> head((size_t)std::min<uint64_t>(size, cap));
+  head.resize(pread_all(fd, head.data(), head.size(), 0));
+  return head;
+}
+
+// The stream cutter's line count. Fast pass: newlines of [p, e) and how many of them are blank lines (a '\n' at a
 // line start); at_start (in / out): the byte at p begins a line.
 static inline void count_newlines_plain(const char* p, const char* e, bool& at_start, size_t& nl, size_t& blanks) {
   for (; p < e; ++p) {
@@ -370,13 +390,7 @@ class CountIngest {
     const uint64_t SLACK = 1u << 20;  // longest record the tail may hold
     const uint64_t from = pc.lo ? pc.lo - 1 : 0, to = std::min<uint64_t>(pc.fsize, pc.hi + SLACK);
     buf.resize((size_t)(to - from));
-    size_t got = 0;
-    while (got < buf.size()) {
-      const ssize_t n = ::pread(pc.fd, buf.data() + got, buf.size() - got, (off_t)(from + got));
-      if (n < 0 && errno == EINTR) continue;
-      if (n <= 0) return fail(std::string("read error on input: ") + strerror(errno));
-      got += (size_t)n;
-    }
+    if (pread_all(pc.fd, buf.data(), buf.size(), from) != buf.size()) return fail(std::string("read error on input: ") + strerror(errno));
     const char *b = buf.data(), *e = buf.data() + buf.size();
     const char* s0 = pc.lo ? record_start(b + 1, b, e) : b;                       // first record starting at >= lo
     const char* hi_p = b + (pc.hi - from);
@@ -642,15 +656,8 @@ class CountIngest {
   // A whole regular file by descriptor: byte ranges, read by the workers themselves.  Returns false if the file
   // does not start like strict 4-line FASTQ (nothing consumed).
   bool feed_file(int fd, uint64_t size) {
-    std::vector<char> head((size_t)std::min<uint64_t>(size, 1u << 16));
-    size_t got = 0;
-    while (got < head.size()) {
-      const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
-      if (n < 0 && errno == EINTR) continue;
-      if (n <= 0) break;
-      got += (size_t)n;
-    }
-    if (!looks_4line(head.data(), got)) return false;
+    const std::vector<uint8_t> head = read_head(fd, size, 1u << 16);
+    if (!looks_4line((const char*)head.data(), head.size())) return false;
     for (uint64_t lo = 0; lo < size; lo += PIECE) {
       Piece pc{nullptr, nullptr, nullptr};
       pc.fd = fd;
@@ -875,15 +882,8 @@ class TextIngest {
       if (pc.fd >= 0) {
         // one byte before the range (is `lo` a line start?) and, behind it, the tail of the record that straddles `hi`
         const uint64_t from = pc.lo ? pc.lo - 1 : 0, to = std::min<uint64_t>(pc.fsize, pc.hi + TAIL);
-        size_t got = 0;
         const size_t want = (size_t)(to - from);
-        while (got < want) {
-          const ssize_t r = ::pread(pc.fd, b.p + got, want - got, (off_t)(from + got));
-          if (r < 0 && errno == EINTR) continue;
-          if (r <= 0) break;
-          got += (size_t)r;
-        }
-        if (got != want) { fail(std::string("read error on input: ") + strerror(errno)); break; }
+        if (pread_all(pc.fd, b.p, want, from) != want) { fail(std::string("read error on input: ") + strerror(errno)); break; }
         const char *tb = b.p, *te = b.p + want;
         const char* s0 = pc.lo ? CountIngest::record_start(tb + 1, tb, te) : tb;
         const char* s1 = pc.hi >= pc.fsize ? te : CountIngest::record_start(tb + (pc.hi - from), tb, te);
@@ -1038,15 +1038,8 @@ class TextIngest {
   // (munmap of a 20 GB mapping: 0.3 s of a count that takes 1.5).  false: the file does not start like strict 4-line
   // FASTQ (nothing consumed).
   bool feed_file(int fd, uint64_t size) {
-    std::vector<char> head((size_t)std::min<uint64_t>(size, 1u << 16));
-    size_t got = 0;
-    while (got < head.size()) {
-      const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
-      if (n < 0 && errno == EINTR) continue;
-      if (n <= 0) break;
-      got += (size_t)n;
-    }
-    if (!CountIngest::looks_4line(head.data(), got)) return false;
+    const std::vector<uint8_t> head = read_head(fd, size, 1u << 16);
+    if (!CountIngest::looks_4line((const char*)head.data(), head.size())) return false;
     for (uint64_t lo = 0; lo < size; lo += piece_) {
       Piece pc{nullptr, nullptr};
       pc.fd = fd;
@@ -1093,172 +1086,228 @@ class TextIngest {
   }
 };
 
-// ---- bgzip'd FASTQ: inflated on the device (rfx_text_append_bgzf; rufus_amd/csrc/rfx_bgzf.hip) -------------------------
-// Replaces `zcat F.fastq.gz | jellyfish count ... /dev/stdin` (runRufus.sh:157-160): the host only reads the file.  One
-// cheap pass over the block headers (rfx_bgzf_scan) cuts the mapped file into runs of whole blocks of at most `piece`
-// compressed bytes; the runs go, IN FILE ORDER (records straddle blocks, so the text must arrive in order), through a
-// ring of page-locked buffers into the arena that is being filled.  BGZF blocks end anywhere: a full arena is cut at its
-// last whole record (rfx_text_settle), the tail moves to the front of the next arena, which is then filled -- its copies
-// and inflate kernels queued, nothing waited for -- BEFORE the settled arena is parsed and counted, so the device
-// inflates the next arena's text beside the count of this one.  Two arenas: one thread feeds, settles, parses and sinks,
-// so a third would never be filled while two are busy.
-// Strict 4-line FASTQ only: the carry rule counts four lines per record, and text the device parser refuses cannot be
-// handed to the host parser arena by arena (an arena's cut would be wrong to begin with).
-// (weak: the host test harness links the executable's source against a stand-in library that has the text arena but no
-// device; there the two are null and BGZF input is refused by the constructor)
-//
-// bgzip'd FASTA (fasta = true; rufus_amd/csrc/rfx_fasta.hip): the same runs, ring and two arenas, with
-// rfx_text_settle_fasta for the carry -- the cut lies at the arena's last header line, so the last record always moves on --
-// and rfx_text_parse_fasta for the block.  Replaces `zcat ref.fa.gz | jellyfish count ... /dev/stdin` in front of the
-// -e / -f databases (runRufus.sh:77, :115).  Every step parses at least one record or ends the run: a record that does
-// not fit an arena is refused, not cut.  (weak, as the two above: without them the FASTA route refuses with one line)
+// ---- what the device-inflate routes below share -------------------------------------------------------------------------
+// (weak, here and in front of the classes: the host test harnesses link an executable's source against stand-in libraries
+// that lack some of these; a route's constructor then refuses with one line)
+#pragma weak rfx_text_open
+#pragma weak rfx_text_close
+#pragma weak rfx_text_room
+#pragma weak rfx_text_bytes
+#pragma weak rfx_text_append
+#pragma weak rfx_text_wait
+#pragma weak rfx_text_reset
+#pragma weak rfx_text_parse
 #pragma weak rfx_text_append_bgzf
 #pragma weak rfx_text_settle
 #pragma weak rfx_text_settle_fasta
 #pragma weak rfx_text_parse_fasta
-class BgzfIngest {
-  rfx_ctx* ctx_;
-  std::function<void(rfx_reads*)> sink_;
-  size_t piece_;
-  bool fasta_;
-  rfx_text* arena_[2] = {nullptr, nullptr};
-  uint64_t arena_bytes_;
-  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
-  std::vector<Buf> ring_;
-  size_t next_buf_ = 0, buf_cap_ = 0;
-  uint64_t blocks_ = 0, arenas_ = 0, reads_ = 0, appends_ = 0;
 
-  [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
-  [[noreturn]] void too_long() const {
-    char msg[160];
-    snprintf(msg, sizeof msg, "rufus_amd jellyfish count: a FASTA sequence does not fit a text arena of %llu bytes (RFX_FASTA_ARENA)",
-             (unsigned long long)arena_bytes_);
-    die(msg);
+[[noreturn]] inline void die_not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
+[[noreturn]] inline void die_rc(const char* what, int rc) {
+  die(std::string("rufus_amd: ") + what + ": " + rfx_strerror(rc) + " " + rfx_last_error());
+}
+
+// The knobs both executables read.  RFX_INGEST_PIECE: the compressed (or text) bytes a route hands over at a time, at
+// least 1024; unset: the route's default.
+inline size_t env_piece(size_t dflt) {
+  const char* ev = getenv("RFX_INGEST_PIECE");
+  return ev ? (size_t)std::max(1024ll, atoll(ev)) : dflt;
+}
+// RFX_*_ARENA: the bytes of an arena, clamped to [lo, hi]; unset (or no name): 1 GiB.  Test knobs -- small files cross
+// arenas -- and, for RFX_FASTA_ARENA, the way out for genomes whose chromosomes pass the default.  (hi = ARENA_MAX where
+// the route's offsets are 32 bits wide.)
+static constexpr long long ARENA_MAX = 0xFFFFDFFFll;
+inline size_t env_arena(const char* name, long long lo = 1ll << 20, long long hi = std::numeric_limits<long long>::max()) {
+  const char* ev = name ? getenv(name) : nullptr;
+  return ev ? (size_t)std::min(hi, std::max(lo, atoll(ev))) : (size_t)1 << 30;
+}
+
+// The ring of page-locked buffers that compressed bytes go through on their way to an arena: a buffer is copied from
+// asynchronously (rfx_text_append_bgzf queues the copy and the inflate), so each remembers the arena and the ticket of
+// the copy that last read it, and is handed out again only when that copy is done.  An arena's tickets die with its
+// reset: settle_arena comes first.  cap = max(piece, 64 KiB): a BGZF block is at most 64 KiB.
+class PinnedRing {
+ public:
+  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
+  PinnedRing(size_t n, size_t piece) : cap_(std::max<size_t>(piece, 1u << 16)), ring_(n) {
+    for (Buf& b : ring_) {
+      b.p = (char*)rfx_host_alloc(cap_);
+      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
+    }
+  }
+  PinnedRing(const PinnedRing&) = delete;
+  PinnedRing& operator=(const PinnedRing&) = delete;
+  ~PinnedRing() {
+    settle_all();
+    for (Buf& b : ring_) rfx_host_free(b.p);
+  }
+  size_t cap() const { return cap_; }
+  Buf& take() {  // the next buffer, round robin, settled
+    Buf& b = ring_[next_];
+    next_ = (next_ + 1) % ring_.size();
+    settle(b);
+    return b;
+  }
+  static void sent(Buf& b, rfx_text* arena, long ticket) {
+    b.t = arena;
+    b.ticket = ticket;
+  }
+  void settle_arena(rfx_text* t) {  // before an arena is reset
+    for (Buf& b : ring_)
+      if (b.t == t) settle(b);
+  }
+  void settle_all() {  // before the arenas are closed
+    for (Buf& b : ring_) settle(b);
   }
 
-  void settle_buf(Buf& b) {
+ private:
+  static void settle(Buf& b) {
     if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
     b.ticket = -1;
   }
-  void settle_ring_of(rfx_text* t) {  // before an arena is reset: its tickets die with the reset
-    for (Buf& b : ring_)
-      if (b.t == t) settle_buf(b);
+  size_t cap_, next_ = 0;
+  std::vector<Buf> ring_;
+};
+
+// The run rule.  One cheap pass over the block headers (rfx_bgzf_scan) cuts [from, to) of a mapped BGZF file into runs of
+// whole blocks, in file order: at most max_bytes compressed bytes (a ring buffer) and at most max_blocks blocks each --
+// bgzf_run_blocks(arena): a quarter of an arena of inflated bytes, and at least one block.  *blocks and *inflated (either
+// may be null) grow by what the runs hold.  Dies, with the caller's prefix, on a block that is not BGZF or not whole.
+struct BgzfRun { size_t at, n; uint64_t inflated; };
+inline uint32_t bgzf_run_blocks(uint64_t arena_bytes) { return (uint32_t)std::max<uint64_t>(1, arena_bytes / 4 / 65536); }
+inline std::vector<BgzfRun> bgzf_runs(const char* m, size_t from, size_t to, size_t max_bytes, uint32_t max_blocks, const std::string& who,
+                                      uint64_t* blocks, uint64_t* inflated = nullptr) {
+  std::vector<BgzfRun> runs;
+  for (size_t at = from; at < to;) {
+    uint32_t nb = 0;
+    uint64_t used = 0, inf = 0;
+    const int rc = rfx_bgzf_scan(m + at, std::min(to - at, max_bytes), max_blocks, &nb, &used, &inf);
+    if (nb == 0) die(who + (rc == RFX_OK ? "truncated" : "no") + " BGZF block at byte " + std::to_string(at) + " of the compressed input");
+    runs.push_back({at, (size_t)used, inf});
+    if (blocks) *blocks += nb;
+    if (inflated) *inflated += inf;
+    at += (size_t)used;
+  }
+  return runs;
+}
+// The fill.  Queues runs[i], runs[i + 1], ... into arena `a` until the next does not fit: a settled buffer of the ring,
+// memcpy, rfx_text_append_bgzf -- queued, nothing waited for.  true: runs[i] is left (the arena is full, or smaller than
+// the run); false: the file is at its end.  An append the library refuses goes to `refuse`.
+inline bool bgzf_fill(PinnedRing& ring, rfx_text* a, const char* m, const std::vector<BgzfRun>& runs, size_t& i, uint64_t& appends,
+                      void (*refuse)(const char*, int) = die_rc) {
+  for (; i < runs.size(); ++i) {
+    const BgzfRun& r = runs[i];
+    if (r.inflated > rfx_text_room(a)) return true;
+    PinnedRing::Buf& b = ring.take();
+    memcpy(b.p, m + r.at, r.n);
+    const long tk = rfx_text_append_bgzf(a, b.p, r.n);
+    if (tk < 0) refuse("rfx_text_append_bgzf", (int)tk);
+    PinnedRing::sent(b, a, tk);
+    ++appends;
+  }
+  return false;
+}
+
+// A page-locked buffer that grows: what a gather writes into.  The gathers answer RFX_E_RANGE with the size they need;
+// need() then makes room for that and a quarter more, and the caller asks again.
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  void need(size_t bytes) {
+    if (bytes <= cap) return;
+    if (p) rfx_host_free(p);
+    cap = bytes + bytes / 4 + 4096;
+    p = rfx_host_alloc(cap);
+    if (!p) die("rufus_amd: cannot allocate page-locked memory for the pulled records");
+  }
+  ~PinnedBuf() { if (p) rfx_host_free(p); }
+};
+
+// The two text arenas of a route that counts compressed FASTQ (or, fasta: FASTA) text, and what happens to a full one.
+// Blocks and chunks end anywhere: a full arena is cut at its last whole record (rfx_text_settle; FASTA: at its last header
+// line, rfx_text_settle_fasta, so the last record always moves on), the tail moves to the front of the other arena, and
+// the arena is parsed, handed to the sink and reset -- behind the tickets of `ring`, where the route has one.  Two arenas:
+// one thread feeds, settles, parses and sinks, so a third would never be filled while two are busy.  What a route does
+// between cut() and parse_and_sink() -- filling the other arena -- is the route's.
+// Strict 4-line FASTQ only: the carry rule counts four lines per record, and text the device parser refuses cannot be
+// handed to the host parser arena by arena (an arena's cut would be wrong to begin with).  FASTA: every step parses at
+// least one record or ends the run: a record that does not fit an arena is refused, not cut.
+class TextArenaPair {
+  rfx_text* arena_[2] = {nullptr, nullptr};
+  std::function<void(rfx_reads*)> sink_;
+  uint64_t bytes_;
+  bool fasta_;
+  PinnedRing* ring_;
+  uint64_t arenas_ = 0, reads_ = 0;
+
+ public:
+  TextArenaPair(std::function<void(rfx_reads*)> sink, uint64_t arena_bytes, bool fasta = false, PinnedRing* ring = nullptr)
+      : sink_(std::move(sink)), bytes_(arena_bytes), fasta_(fasta), ring_(ring) {}
+  void open(rfx_ctx* ctx) {  // (not the constructor's: a route refuses a library that cannot serve it first)
+    for (rfx_text*& a : arena_) {
+      a = rfx_text_open(ctx, bytes_);
+      if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
+    }
+  }
+  ~TextArenaPair() {
+    if (ring_) ring_->settle_all();
+    for (rfx_text* a : arena_)
+      if (a) rfx_text_close(a);
+  }
+  rfx_text* operator[](int i) const { return arena_[i]; }
+  uint64_t bytes() const { return bytes_; }
+  uint64_t arenas() const { return arenas_; }
+  uint64_t reads() const { return reads_; }
+
+  [[noreturn]] void too_long() const {
+    char msg[160];
+    snprintf(msg, sizeof msg, "rufus_amd jellyfish count: a FASTA sequence does not fit a text arena of %llu bytes (RFX_FASTA_ARENA)",
+             (unsigned long long)bytes_);
+    die(msg);
+  }
+  [[noreturn]] void no_record() const { fasta_ ? too_long() : die_not_strict(); }  // text that no arena holds a whole record of
+
+  // cuts t behind its last whole record; the bytes moved to `next` (null: the input ends here, nothing may be left)
+  uint64_t settle(rfx_text* t, rfx_text* next) {
+    uint64_t carried = 0;
+    const int rc = fasta_ ? rfx_text_settle_fasta(t, next, &carried) : rfx_text_settle(t, next, &carried);
+    // (a block that did not inflate: only an arena that BGZF blocks went into says so)
+    if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
+    if (fasta_ && rc == RFX_E_RANGE) too_long();  // (one record fills the arena, or its tail does not fit the next)
+    if (fasta_ && rc != RFX_OK)
+      die(std::string("rufus_amd jellyfish count: rfx_text_settle_fasta: ") + rfx_strerror(rc) + " " + rfx_last_error());
+    if (rc == RFX_E_FORMAT || rc == RFX_E_RANGE) die_not_strict();  // (ends inside a record / a "record" longer than an arena)
+    if (rc != RFX_OK) die_rc("rfx_text_settle", rc);
+    return carried;
+  }
+  void cut(rfx_text* t, rfx_text* next) {  // a full arena
+    const uint64_t before = rfx_text_bytes(t);
+    if (settle(t, next) == before) no_record();  // a full arena without one whole record
   }
   void parse_and_sink(rfx_text* t) {
     if (rfx_text_bytes(t)) {
       int strict = 1;
       rfx_reads* r = fasta_ ? rfx_text_parse_fasta(t, RFX_PACK_COUNT, &strict) : rfx_text_parse(t, RFX_PACK_COUNT, 0, &strict);
       if (!r && !strict && fasta_) die("rufus_amd jellyfish count: the inflated text does not begin with '>'");
-      if (!r && !strict) not_strict();
+      if (!r && !strict) die_not_strict();
       if (!r) die(std::string(fasta_ ? "rufus_amd: rfx_text_parse_fasta: " : "rufus_amd: rfx_text_parse: ") + rfx_last_error());
       reads_ += rfx_reads_count(r);
       ++arenas_;
       sink_(r);
     }
-    settle_ring_of(t);
+    if (ring_) ring_->settle_arena(t);
     rfx_text_reset(t);
   }
-  uint64_t settle(rfx_text* t, rfx_text* next) {
-    uint64_t carried = 0;
-    const int rc = fasta_ ? rfx_text_settle_fasta(t, next, &carried) : rfx_text_settle(t, next, &carried);
-    if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string("rufus_amd jellyfish count: ") + rfx_last_error());
-    if (fasta_ && rc == RFX_E_RANGE) too_long();  // (one record fills the arena, or its tail does not fit the next)
-    if (fasta_ && rc != RFX_OK)
-      die(std::string("rufus_amd jellyfish count: rfx_text_settle_fasta: ") + rfx_strerror(rc) + " " + rfx_last_error());
-    if (rc == RFX_E_FORMAT || rc == RFX_E_RANGE) not_strict();  // (ends inside a record / a "record" longer than an arena)
-    if (rc != RFX_OK) die(std::string("rufus_amd: rfx_text_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
-    return carried;
-  }
-
- public:
-  BgzfIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20,
-             bool fasta = false)
-      : ctx_(ctx), sink_(std::move(sink)), piece_(piece), fasta_(fasta), arena_bytes_(arena_bytes) {
-    if (!rfx_text_append_bgzf || !rfx_text_settle) die("rufus_amd jellyfish count: this library cannot inflate BGZF input");
-    if (fasta_ && (!rfx_text_settle_fasta || !rfx_text_parse_fasta)) die("rufus_amd jellyfish count: this library cannot read bgzip'd FASTA");
-    for (rfx_text*& a : arena_) {
-      a = rfx_text_open(ctx_, arena_bytes);
-      if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
-    }
-    buf_cap_ = std::max<size_t>(piece_, 1u << 16);  // (a block is at most 64 KiB)
-    ring_.resize(4);
-    for (Buf& b : ring_) {
-      b.p = (char*)rfx_host_alloc(buf_cap_);
-      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
-    }
-  }
-  ~BgzfIngest() {
-    for (Buf& b : ring_) {
-      settle_buf(b);
-      rfx_host_free(b.p);
-    }
-    for (rfx_text* a : arena_) rfx_text_close(a);
-  }
-  uint64_t reads() const { return reads_; }
-  std::string counts() const {
-    char b[160];
-    snprintf(b, sizeof b, fasta_ ? "fasta route: %llu blocks in %llu appends, %llu arenas, %llu sequences"
-                                 : "bgzf route: %llu blocks in %llu appends, %llu arenas, %llu reads",
-             (unsigned long long)blocks_, (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)reads_);
-    return b;
-  }
-
-  // A whole mapped BGZF file.  Dies on a block that is not BGZF or not whole, on text that is not strict 4-line FASTQ
-  // and on a block that does not inflate.
-  void feed_mapped(const char* m, size_t size) {
-    // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of text
-    struct Run { size_t at, n; uint64_t inflated; };
-    std::vector<Run> runs;
-    const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
-    for (size_t at = 0; at < size;) {
-      uint32_t nb = 0;
-      uint64_t used = 0, inf = 0;
-      int rc = rfx_bgzf_scan(m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
-      if (nb == 0) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "rufus_amd jellyfish count: %s BGZF block at byte %llu of the compressed input",
-                 rc == RFX_OK ? "truncated" : "no", (unsigned long long)at);
-        die(msg);
-      }
-      runs.push_back({at, (size_t)used, inf});
-      blocks_ += nb;
-      at += (size_t)used;
-    }
-    int cur = 0;
-    size_t i = 0;
-    // queues runs into arena `a` until the next does not fit (false: the file is at its end)
-    auto fill = [&](rfx_text* a) {
-      for (; i < runs.size(); ++i) {
-        const Run& r = runs[i];
-        if (r.inflated > arena_bytes_) fasta_ ? too_long() : not_strict();  // (cannot happen: a run inflates to <= a quarter of an arena)
-        if (r.inflated > rfx_text_room(a)) return true;
-        Buf& b = ring_[next_buf_];
-        next_buf_ = (next_buf_ + 1) % ring_.size();
-        settle_buf(b);
-        memcpy(b.p, m + r.at, r.n);
-        const long tk = rfx_text_append_bgzf(a, b.p, r.n);
-        if (tk < 0) die(std::string("rufus_amd: rfx_text_append_bgzf: ") + rfx_strerror((int)tk) + " " + rfx_last_error());
-        b.t = a;
-        b.ticket = tk;
-        ++appends_;
-      }
-      return false;
-    };
-    bool more = fill(arena_[cur]);
-    while (more) {
-      rfx_text* t = arena_[cur];
-      rfx_text* nx = arena_[cur ^ 1];
-      const uint64_t before = rfx_text_bytes(t);
-      const uint64_t carried = settle(t, nx);
-      if (carried == before) fasta_ ? too_long() : not_strict();  // a full arena without one whole record
-      more = fill(nx);       // queued, not waited for: the device inflates it beside this arena's count
-      parse_and_sink(t);
-      cur ^= 1;
-    }
-    // the last arena; a file without a final newline gets one
+  // The end of the input, in arena `cur`.  FASTQ: a file without a final newline gets one -- what is left behind the last
+  // whole record moves to the other arena, the newline goes behind it, and that arena is the last.  FASTA: nothing is
+  // carried, and a last line without '\n' is a line.
+  void finish(int cur) {
     rfx_text* t = arena_[cur];
     rfx_text* nx = arena_[cur ^ 1];
-    if (fasta_) {  // the file ends here: nothing is carried, and a last line without '\n' is a line
+    if (fasta_) {
       (void)settle(t, nullptr);
       parse_and_sink(t);
       return;
@@ -1275,19 +1324,73 @@ class BgzfIngest {
   }
 };
 
+// ---- bgzip'd FASTQ: inflated on the device (rfx_text_append_bgzf; rufus_amd/csrc/rfx_bgzf.hip) -------------------------
+// Replaces `zcat F.fastq.gz | jellyfish count ... /dev/stdin` (runRufus.sh:157-160): the host only reads the file.  The
+// run rule (bgzf_runs) cuts the mapped file; the runs go, IN FILE ORDER (records straddle blocks, so the text must arrive
+// in order), through a PinnedRing into the arena of a TextArenaPair that is being filled (bgzf_fill).  A full arena is
+// cut, then the next one is filled -- its copies and inflate kernels queued, nothing waited for -- BEFORE the cut arena is
+// parsed and counted, so the device inflates the next arena's text beside the count of this one.
+// (without rfx_text_append_bgzf and rfx_text_settle -- a stand-in library that has the text arena but no device -- BGZF
+// input is refused by the constructor)
+//
+// bgzip'd FASTA (fasta = true; rufus_amd/csrc/rfx_fasta.hip): the same runs, ring and steps, the pair in its FASTA mode.
+// Replaces `zcat ref.fa.gz | jellyfish count ... /dev/stdin` in front of the -e / -f databases (runRufus.sh:77, :115).
+// (without rfx_text_settle_fasta and rfx_text_parse_fasta the FASTA route refuses with one line)
+class BgzfIngest {
+  bool fasta_;
+  PinnedRing ring_;  // (in front of the pair: the pair settles it before the arenas close)
+  TextArenaPair pair_;
+  uint64_t blocks_ = 0, appends_ = 0;
+
+ public:
+  BgzfIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 8u << 20,
+             bool fasta = false)
+      : fasta_(fasta), ring_(4, piece), pair_(std::move(sink), arena_bytes, fasta, &ring_) {
+    if (!rfx_text_append_bgzf || !rfx_text_settle) die("rufus_amd jellyfish count: this library cannot inflate BGZF input");
+    if (fasta_ && (!rfx_text_settle_fasta || !rfx_text_parse_fasta)) die("rufus_amd jellyfish count: this library cannot read bgzip'd FASTA");
+    pair_.open(ctx);
+  }
+  uint64_t reads() const { return pair_.reads(); }
+  std::string counts() const {
+    char b[160];
+    snprintf(b, sizeof b, fasta_ ? "fasta route: %llu blocks in %llu appends, %llu arenas, %llu sequences"
+                                 : "bgzf route: %llu blocks in %llu appends, %llu arenas, %llu reads",
+             (unsigned long long)blocks_, (unsigned long long)appends_, (unsigned long long)pair_.arenas(), (unsigned long long)pair_.reads());
+    return b;
+  }
+
+  // A whole mapped BGZF file.  Dies on a block that is not BGZF or not whole, on text that is not strict 4-line FASTQ
+  // and on a block that does not inflate.
+  void feed_mapped(const char* m, size_t size) {
+    const std::vector<BgzfRun> runs =
+        bgzf_runs(m, 0, size, ring_.cap(), bgzf_run_blocks(pair_.bytes()), "rufus_amd jellyfish count: ", &blocks_);
+    int cur = 0;
+    size_t i = 0;
+    auto fill = [&](rfx_text* a) {
+      const bool more = bgzf_fill(ring_, a, m, runs, i, appends_);
+      // A run that no arena holds.  A run is a quarter of an arena of text at most, but one block at least: below 256 KiB
+      // a run may pass the quarter, and below the 64 KiB that one block may inflate to, the arena.
+      if (more && runs[i].inflated > pair_.bytes()) pair_.no_record();
+      return more;
+    };
+    bool more = fill(pair_[cur]);
+    while (more) {
+      pair_.cut(pair_[cur], pair_[cur ^ 1]);
+      more = fill(pair_[cur ^ 1]);  // queued, not waited for: the device inflates it beside this arena's count
+      pair_.parse_and_sink(pair_[cur]);
+      cur ^= 1;
+    }
+    pair_.finish(cur);
+  }
+};
+
 // The first inflated byte of a BGZF file, or -1: what sends a bgzip'd input of `jellyfish count` to the FASTA route ('>')
 // or where it went before (anything else), as is_bam does for BAM.  The first non-empty block is inflated by the host side
 // of rfx_bgzf_core.h (a serial copy as its output policy); -1 when no such block lies whole in the file's first 128 KiB or
 // it does not inflate -- the route that takes the file then says what is wrong with it.
 inline int bgzf_first_byte(int fd, uint64_t size) {
-  std::vector<uint8_t> head((size_t)std::min<uint64_t>(size, 1u << 17));
-  size_t got = 0;
-  while (got < head.size()) {
-    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
-    if (n < 0 && errno == EINTR) continue;
-    if (n <= 0) break;
-    got += (size_t)n;
-  }
+  const std::vector<uint8_t> head = read_head(fd, size, 1u << 17);
+  const size_t got = head.size();
   struct Serial {
     uint8_t* out;
     void literal(uint32_t pos, uint32_t byte) { out[pos] = (uint8_t)byte; }
@@ -1315,8 +1418,8 @@ inline int bgzf_first_byte(int fd, uint64_t size) {
 
 // ---- plain-gzip FASTQ: inflated on the device (rfx_text_append_gzip; rufus_amd/csrc/rfx_gzip.hip) -------------------------
 // Replaces `zcat F.fastq.gz | jellyfish count ... /dev/stdin` (runRufus.sh:157-160, :229-232) for files that are gzip but
-// not BGZF: what a sequencer or an archive hands out.  BgzfIngest's two arenas, settle (the carry of a record that an arena
-// cuts), parse and sink; what differs is the fill: the stream has no block index, so the mapped file is PRESENTED, a piece
+// not BGZF: what a sequencer or an archive hands out.  BgzfIngest's TextArenaPair, without a ring; what differs is the
+// fill: the stream has no block index, so the mapped file is PRESENTED, a piece
 // at a time, and rfx_text_append_gzip says how many of the piece's bytes are done with -- it appends whole confirmed chunks
 // only.  Nothing consumed and nothing appended is either a full arena (rfx_gzip_need() != 0: settle and switch) or a piece
 // that holds no whole chunk (a stream of stored or fixed blocks has no chunk starts to find: the piece doubles, up to the
@@ -1329,53 +1432,25 @@ inline int bgzf_first_byte(int fd, uint64_t size) {
 #pragma weak rfx_gzip_stats
 class GzipIngest {
   rfx_ctx* ctx_;
-  std::function<void(rfx_reads*)> sink_;
   size_t piece_;
-  rfx_text* arena_[2] = {nullptr, nullptr};
-  uint64_t arenas_ = 0, reads_ = 0, appends_ = 0, files_ = 0;
+  TextArenaPair pair_;
+  uint64_t appends_ = 0, files_ = 0;
   uint64_t stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-  [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
-  void parse_and_sink(rfx_text* t) {
-    if (rfx_text_bytes(t)) {
-      int strict = 1;
-      rfx_reads* r = rfx_text_parse(t, RFX_PACK_COUNT, 0, &strict);
-      if (!r && !strict) not_strict();
-      if (!r) die(std::string("rufus_amd: rfx_text_parse: ") + rfx_last_error());
-      reads_ += rfx_reads_count(r);
-      ++arenas_;
-      sink_(r);
-    }
-    rfx_text_reset(t);
-  }
-  uint64_t settle(rfx_text* t, rfx_text* next) {
-    uint64_t carried = 0;
-    const int rc = rfx_text_settle(t, next, &carried);
-    if (rc == RFX_E_FORMAT || rc == RFX_E_RANGE) not_strict();  // (ends inside a record / a "record" longer than an arena)
-    if (rc != RFX_OK) die(std::string("rufus_amd: rfx_text_settle: ") + rfx_strerror(rc) + " " + rfx_last_error());
-    return carried;
-  }
 
  public:
   GzipIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, size_t arena_bytes = (size_t)1 << 30, size_t piece = 128u << 20)
-      : ctx_(ctx), sink_(std::move(sink)), piece_(std::max<size_t>(piece, 64)) {
+      : ctx_(ctx), piece_(std::max<size_t>(piece, 64)), pair_(std::move(sink), arena_bytes) {
     if (!rfx_gzip_open || !rfx_gzip_close || !rfx_text_append_gzip || !rfx_gzip_need || !rfx_gzip_stats || !rfx_text_settle)
       die("rufus_amd jellyfish count: this library cannot inflate plain-gzip input");
-    for (rfx_text*& a : arena_) {
-      a = rfx_text_open(ctx_, arena_bytes);
-      if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
-    }
+    pair_.open(ctx_);
   }
-  ~GzipIngest() {
-    for (rfx_text* a : arena_) rfx_text_close(a);
-  }
-  uint64_t reads() const { return reads_; }
+  uint64_t reads() const { return pair_.reads(); }
   std::string counts() const {
     char b[320];
     snprintf(b, sizeof b,
              "gzip route: %llu files, %llu appends, %llu arenas, %llu reads; chunks found %llu, confirmed %llu, dropped %llu, "
              "inserted %llu, rounds %llu, members %llu, batches %llu, bytes %llu",
-             (unsigned long long)files_, (unsigned long long)appends_, (unsigned long long)arenas_, (unsigned long long)reads_,
+             (unsigned long long)files_, (unsigned long long)appends_, (unsigned long long)pair_.arenas(), (unsigned long long)pair_.reads(),
              (unsigned long long)stats_[0], (unsigned long long)stats_[1], (unsigned long long)stats_[2], (unsigned long long)stats_[3],
              (unsigned long long)stats_[4], (unsigned long long)stats_[5], (unsigned long long)stats_[6], (unsigned long long)stats_[7]);
     return b;
@@ -1392,18 +1467,16 @@ class GzipIngest {
     uint64_t fresh = 0;  // bytes this file has put into the current arena
     double ratio = 4.0;  // inflated / compressed bytes, the largest seen
     auto next_arena = [&] {  // the arena's tail moves on, it is counted, the other one is filled
-      rfx_text* a = arena_[cur];
-      const uint64_t before = rfx_text_bytes(a);
-      if (settle(a, arena_[cur ^ 1]) == before) not_strict();  // a full arena without one whole record
-      parse_and_sink(a);
+      pair_.cut(pair_[cur], pair_[cur ^ 1]);
+      pair_.parse_and_sink(pair_[cur]);
       cur ^= 1;
       fresh = 0;
     };
     while (at < size) {
       const size_t n = std::min(piece, size - at);
       // a piece that will not fit what is left of the arena would be found and walked twice: the arena goes as it is
-      if (fresh && (double)n * ratio > (double)rfx_text_room(arena_[cur])) next_arena();
-      rfx_text* a = arena_[cur];
+      if (fresh && (double)n * ratio > (double)rfx_text_room(pair_[cur])) next_arena();
+      rfx_text* a = pair_[cur];
       uint64_t used = 0;
       const long got = rfx_text_append_gzip(a, gz, m + at, n, at + n == size, &used);
       ++appends_;
@@ -1425,18 +1498,7 @@ class GzipIngest {
     if (rfx_gzip_stats(gz, st) == RFX_OK)
       for (int i = 0; i < 8; ++i) stats_[i] += st[i];
     rfx_gzip_close(gz);
-    // the last arena; a file without a final newline gets one
-    rfx_text* t = arena_[cur];
-    rfx_text* nx = arena_[cur ^ 1];
-    if (settle(t, nx)) {
-      const long tk = rfx_text_append(nx, "\n", 1);
-      if (tk < 0 || rfx_text_wait(nx, tk) != RFX_OK) die(std::string("rufus_amd: rfx_text_append: ") + rfx_last_error());
-      parse_and_sink(t);
-      (void)settle(nx, nullptr);
-      parse_and_sink(nx);
-    } else {
-      parse_and_sink(t);
-    }
+    pair_.finish(cur);
   }
 };
 
@@ -1444,14 +1506,8 @@ class GzipIngest {
 // the device sees it.  The first member's header, then the host side of rfx_gzip_core.h over the file's first 64 KiB with
 // an output policy that keeps byte 0.
 inline int gzip_first_byte(int fd, uint64_t size) {
-  std::vector<uint8_t> head((size_t)std::min<uint64_t>(size, 1u << 16));
-  size_t got = 0;
-  while (got < head.size()) {
-    const ssize_t n = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
-    if (n < 0 && errno == EINTR) continue;
-    if (n <= 0) break;
-    got += (size_t)n;
-  }
+  const std::vector<uint8_t> head = read_head(fd, size, 1u << 16);
+  const size_t got = head.size();
   struct First {
     int byte = -1;
     void literal(uint64_t pos, uint32_t b) { if (pos == 0) byte = (int)b; }
@@ -1496,13 +1552,10 @@ inline int gzip_first_byte(int fd, uint64_t size) {
 class BamIngest {
   rfx_ctx* ctx_;
   std::function<void(rfx_reads*)> sink_;
-  size_t piece_;
   uint32_t exclude_;
   rfx_text* arena_[2] = {nullptr, nullptr};
   uint64_t arena_bytes_;
-  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
-  std::vector<Buf> ring_;
-  size_t next_buf_ = 0, buf_cap_ = 0;
+  PinnedRing ring_;
   uint64_t blocks_ = 0, arenas_ = 0, records_ = 0, reads_ = 0, appends_ = 0;
   int32_t n_ref_ = 0;
   std::vector<std::string> ref_names_;
@@ -1573,14 +1626,6 @@ class BamIngest {
     if (!cache_.add_chunk(c)) cache_write_error();
   }
 
-  void settle_buf(Buf& b) {
-    if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
-    b.ticket = -1;
-  }
-  void settle_ring_of(rfx_text* t) {  // before an arena is reset: its tickets die with the reset
-    for (Buf& b : ring_)
-      if (b.t == t) settle_buf(b);
-  }
   void parse_and_sink(rfx_text* t, uint64_t n_records, uint64_t base) {
     if (n_records && cache_fd_ >= 0) keep_chunk(t, n_records, base);
     if (n_records && per_arena_) {
@@ -1598,7 +1643,7 @@ class BamIngest {
       ++arenas_;
       sink_(r);
     }
-    settle_ring_of(t);
+    ring_.settle_arena(t);
     rfx_text_reset(t);
   }
   // the whole records of t; *carried = the bytes moved to `next`
@@ -1692,25 +1737,16 @@ class BamIngest {
   }
   BamIngest(rfx_ctx* ctx, std::function<void(rfx_reads*)> sink, uint32_t exclude_flags, size_t arena_bytes = (size_t)1 << 30,
             size_t piece = 8u << 20)
-      : ctx_(ctx), sink_(std::move(sink)), piece_(piece), exclude_(exclude_flags), arena_bytes_(arena_bytes) {
+      : ctx_(ctx), sink_(std::move(sink)), exclude_(exclude_flags), arena_bytes_(arena_bytes), ring_(4, piece) {
     if (!rfx_text_append_bgzf || !rfx_bam_header || !rfx_bam_settle || !rfx_bam_parse)
       die(tool_ + ": this library cannot read BAM input");
     for (rfx_text*& a : arena_) {
       a = rfx_text_open(ctx_, arena_bytes);
       if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
     }
-    buf_cap_ = std::max<size_t>(piece_, 1u << 16);  // (a block is at most 64 KiB)
-    ring_.resize(4);
-    for (Buf& b : ring_) {
-      b.p = (char*)rfx_host_alloc(buf_cap_);
-      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
-    }
   }
   ~BamIngest() {
-    for (Buf& b : ring_) {
-      settle_buf(b);
-      rfx_host_free(b.p);
-    }
+    ring_.settle_all();
     for (rfx_text* a : arena_) rfx_text_close(a);
   }
   // the other step per arena, and the tool the messages name (before feed_mapped)
@@ -1787,19 +1823,9 @@ class BamIngest {
       std::string names;
       for (const std::string& n : ref_names_) names.append(n).push_back('\0');
       if (!cache_.open(cache_fd_, cache_minq_, exclude_, (uint32_t)n_ref_, names.data(), names.size())) cache_write_error();
-      for (size_t at = 0; at < size;) {
-        uint32_t nb = 0;
-        uint64_t used = 0, inf = 0;
-        rc = rfx_bgzf_scan(m + at, std::min<size_t>(size - at, 1u << 16), 1, &nb, &used, &inf);
-        if (nb != 1) {
-          char msg[128];
-          snprintf(msg, sizeof msg, "%s BGZF block at byte %llu of the compressed input", rc == RFX_OK ? "truncated" : "no",
-                   (unsigned long long)at);
-          die(tool_ + ": " + msg);
-        }
-        if (at == (size_t)first_block) base = cache_.stream_bytes();
-        cache_.add_block((uint32_t)used, (uint32_t)inf);
-        at += (size_t)used;
+      for (const BgzfRun& b : bgzf_runs(m, 0, size, 1u << 16, 1, tool_ + ": ", nullptr)) {  // (runs of one block)
+        if (b.at == (size_t)first_block) base = cache_.stream_bytes();
+        cache_.add_block((uint32_t)b.n, (uint32_t)b.inflated);
       }
     }
     // --region: the index's one range of blocks instead of all of them (region_range)
@@ -1817,48 +1843,16 @@ class BamIngest {
         skip_first = skip0;
       }
     }
-    // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of inflated bytes
-    struct Run { size_t at, n; uint64_t inflated; };
-    std::vector<Run> runs;
-    const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
     uint64_t range_inflated = 0;
-    for (size_t at = (size_t)walk_from; at < (size_t)walk_to;) {
-      uint32_t nb = 0;
-      uint64_t used = 0, inf = 0;
-      rc = rfx_bgzf_scan(m + at, std::min((size_t)walk_to - at, buf_cap_), max_blocks, &nb, &used, &inf);
-      if (nb == 0) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "%s BGZF block at byte %llu of the compressed input", rc == RFX_OK ? "truncated" : "no",
-                 (unsigned long long)at);
-        die(tool_ + (per_arena_ ? ": --bam: " : ": ") + msg);
-      }
-      runs.push_back({at, (size_t)used, inf});
-      blocks_ += nb;
-      range_inflated += inf;
-      at += (size_t)used;
-    }
+    const std::vector<BgzfRun> runs = bgzf_runs(m, (size_t)walk_from, (size_t)walk_to, ring_.cap(), bgzf_run_blocks(arena_bytes_),
+                                                tool_ + (per_arena_ ? ": --bam: " : ": "), &blocks_, &range_inflated);
     if (ranged && runs.empty()) return;
     // STOP as an offset in the inflated bytes of the range (the first arena's byte 0 = the first block's)
     const uint64_t stop_stream = stop_in ? range_inflated - stop_inf + stop_in : range_inflated;
     int cur = 0;
     size_t i = 0;
-    // queues runs into arena `a` until the next does not fit (false: the file is at its end)
-    auto fill = [&](rfx_text* a) {
-      for (; i < runs.size(); ++i) {
-        const Run& r = runs[i];
-        if (r.inflated > rfx_text_room(a)) return true;
-        Buf& b = ring_[next_buf_];
-        next_buf_ = (next_buf_ + 1) % ring_.size();
-        settle_buf(b);
-        memcpy(b.p, m + r.at, r.n);
-        const long tk = rfx_text_append_bgzf(a, b.p, r.n);
-        if (tk < 0) die(std::string("rufus_amd: rfx_text_append_bgzf: ") + rfx_strerror((int)tk) + " " + rfx_last_error());
-        b.t = a;
-        b.ticket = tk;
-        ++appends_;
-      }
-      return false;
-    };
+    // (no check for a run that no arena holds: an arena that fills with nothing ends below, in n_records == 0)
+    auto fill = [&](rfx_text* a) { return bgzf_fill(ring_, a, m, runs, i, appends_); };
     uint64_t skip = skip_first;
     bool more = fill(arena_[cur]);
     while (more) {
@@ -1909,14 +1903,6 @@ class BamIngest {
 // holds is ignored, as src/RUFUS.Filter.cpp:165 stops at the end of file 1); mate 2 at its end with records of mate 1
 // left is refused -- the text route's records of empty lines for the missing mates are not reproduced.
 // (weak, as above: tests/host/filter_sam_harness.cpp links the executable's source against a stand-in without a text arena)
-#pragma weak rfx_text_open
-#pragma weak rfx_text_close
-#pragma weak rfx_text_room
-#pragma weak rfx_text_bytes
-#pragma weak rfx_text_append
-#pragma weak rfx_text_wait
-#pragma weak rfx_text_reset
-#pragma weak rfx_text_parse
 #pragma weak rfx_text_records
 #pragma weak rfx_text_settle_records
 #pragma weak rfx_text_gather
@@ -1931,72 +1917,32 @@ class BgzfPairFilter {
   rfx_set* set_;
   int min_q_, thresh_;
   Sink sink_;
-  size_t piece_;
   uint64_t arena_bytes_;
-  struct Run { size_t at, n; uint64_t inflated; };
   struct Mate {
     const char* m = nullptr;
-    std::vector<Run> runs;
+    std::vector<BgzfRun> runs;
     size_t i = 0;         // the next run to queue
     bool closed = false;  // every run is queued and the final newline lies behind them
     rfx_text* arena[2] = {nullptr, nullptr};
     std::vector<uint64_t> mask;
-    char* out = nullptr;  // page-locked: the gathered text
-    uint64_t out_cap = 0;
+    PinnedBuf out;  // the gathered text
   };
   Mate mate_[2];
-  struct Buf { char* p = nullptr; rfx_text* t = nullptr; long ticket = -1; };
-  std::vector<Buf> ring_;
-  size_t next_buf_ = 0, buf_cap_ = 0;
+  PinnedRing ring_;
   uint64_t blocks_ = 0, appends_ = 0, steps_ = 0, pairs_ = 0, pulled_ = 0;
 
-  [[noreturn]] static void not_strict() { die("compressed input must be strict 4-line FASTQ: inflate it and pipe it in"); }
   [[noreturn]] static void fail(const char* what, int rc) {
     if (rc == RFX_E_FORMAT && !strncmp(rfx_last_error(), "rfx_bgzf:", 9)) die(std::string("rufus_amd RUFUS.Filter: ") + rfx_last_error());
-    die(std::string("rufus_amd: ") + what + ": " + rfx_strerror(rc) + " " + rfx_last_error());
+    die_rc(what, rc);
   }
 
-  void settle_buf(Buf& b) {
-    if (b.ticket >= 0 && rfx_text_wait(b.t, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
-    b.ticket = -1;
-  }
-  void reset(rfx_text* t) {  // (an arena's tickets die with its reset)
-    for (Buf& b : ring_)
-      if (b.t == t) settle_buf(b);
+  void reset(rfx_text* t) {
+    ring_.settle_arena(t);
     rfx_text_reset(t);
-  }
-  void scan(Mate& M, size_t size) {  // runs of whole blocks: <= piece compressed bytes and <= a quarter of an arena of text
-    const uint32_t max_blocks = (uint32_t)std::max<uint64_t>(1, arena_bytes_ / 4 / 65536);
-    for (size_t at = 0; at < size;) {
-      uint32_t nb = 0;
-      uint64_t used = 0, inf = 0;
-      const int rc = rfx_bgzf_scan(M.m + at, std::min(size - at, buf_cap_), max_blocks, &nb, &used, &inf);
-      if (nb == 0) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "rufus_amd RUFUS.Filter: %s BGZF block at byte %llu of the compressed input",
-                 rc == RFX_OK ? "truncated" : "no", (unsigned long long)at);
-        die(msg);
-      }
-      M.runs.push_back({at, (size_t)used, inf});
-      blocks_ += nb;
-      at += (size_t)used;
-    }
   }
   // queues runs into arena `a` until the next does not fit or the file is at its end (then the newline behind it)
   void fill(Mate& M, rfx_text* a) {
-    for (; M.i < M.runs.size(); ++M.i) {
-      const Run& r = M.runs[M.i];
-      if (r.inflated > rfx_text_room(a)) return;
-      Buf& b = ring_[next_buf_];
-      next_buf_ = (next_buf_ + 1) % ring_.size();
-      settle_buf(b);
-      memcpy(b.p, M.m + r.at, r.n);
-      const long tk = rfx_text_append_bgzf(a, b.p, r.n);
-      if (tk < 0) fail("rfx_text_append_bgzf", (int)tk);
-      b.t = a;
-      b.ticket = tk;
-      ++appends_;
-    }
+    if (bgzf_fill(ring_, a, M.m, M.runs, M.i, appends_, fail)) return;
     if (!M.closed && rfx_text_room(a) >= 1) {
       static const char nl = '\n';
       const long tk = rfx_text_append(a, &nl, 1);
@@ -2013,26 +1959,23 @@ class BgzfPairFilter {
   void cut(rfx_text* t, rfx_text* next, uint64_t n) {
     uint64_t kept = 0, carried = 0;
     const int rc = rfx_text_settle_records(t, next, n, &kept, &carried);
-    if (rc == RFX_E_RANGE) not_strict();  // (cannot be: the arenas of a mate are equally large)
+    if (rc == RFX_E_RANGE) die_not_strict();  // (cannot be: the arenas of a mate are equally large)
     if (rc != RFX_OK) fail("rfx_text_settle_records", rc);
     if (kept != n) die("rufus_amd RUFUS.Filter: an arena lost records between the count and the cut");
   }
   void gather(Mate& M, rfx_text* t, const uint64_t* mask, uint64_t n, uint64_t* bytes, uint64_t* n_sel) {
     for (;;) {
-      const int rc = rfx_text_gather(t, mask, n, M.out, M.out_cap, bytes, n_sel);
+      const int rc = rfx_text_gather(t, mask, n, M.out.p, M.out.cap, bytes, n_sel);
       if (rc == RFX_OK) return;
       if (rc != RFX_E_RANGE) fail("rfx_text_gather", rc);
-      if (M.out) rfx_host_free(M.out);
-      M.out_cap = *bytes + *bytes / 4 + 4096;
-      M.out = (char*)rfx_host_alloc(M.out_cap);
-      if (!M.out) die("rufus_amd: cannot allocate page-locked memory for the pulled records");
+      M.out.need((size_t)*bytes);
     }
   }
 
  public:
   BgzfPairFilter(rfx_ctx* ctx, rfx_set* set, int min_q, int thresh, Sink sink, size_t arena_bytes = (size_t)1 << 30,
                  size_t piece = 8u << 20)
-      : ctx_(ctx), set_(set), min_q_(min_q), thresh_(thresh), sink_(std::move(sink)), piece_(piece), arena_bytes_(arena_bytes) {
+      : ctx_(ctx), set_(set), min_q_(min_q), thresh_(thresh), sink_(std::move(sink)), arena_bytes_(arena_bytes), ring_(8, piece) {
     if (!rfx_text_open || !rfx_text_close || !rfx_text_room || !rfx_text_bytes || !rfx_text_append || !rfx_text_wait ||
         !rfx_text_reset || !rfx_text_parse || !rfx_text_append_bgzf || !rfx_text_records || !rfx_text_settle_records ||
         !rfx_text_gather || !rfx_reads_of_length)
@@ -2043,22 +1986,11 @@ class BgzfPairFilter {
         a = rfx_text_open(ctx_, arena_bytes_);
         if (!a) die(std::string("rufus_amd: rfx_text_open: ") + rfx_last_error());
       }
-    buf_cap_ = std::max<size_t>(piece_, 1u << 16);  // (a block is at most 64 KiB)
-    ring_.resize(8);
-    for (Buf& b : ring_) {
-      b.p = (char*)rfx_host_alloc(buf_cap_);
-      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
-    }
   }
   ~BgzfPairFilter() {
-    for (Buf& b : ring_) {
-      settle_buf(b);
-      rfx_host_free(b.p);
-    }
-    for (Mate& M : mate_) {
+    ring_.settle_all();
+    for (Mate& M : mate_)
       for (rfx_text* a : M.arena) rfx_text_close(a);
-      if (M.out) rfx_host_free(M.out);
-    }
   }
   std::string counts() const {
     char b[200];
@@ -2075,8 +2007,9 @@ class BgzfPairFilter {
   void run(const char* m1, size_t n1, const char* m2, size_t n2) {
     mate_[0].m = m1;
     mate_[1].m = m2;
-    scan(mate_[0], n1);
-    scan(mate_[1], n2);
+    const size_t sizes[2] = {n1, n2};
+    for (int m = 0; m < 2; ++m)
+      mate_[m].runs = bgzf_runs(mate_[m].m, 0, sizes[m], ring_.cap(), bgzf_run_blocks(arena_bytes_), "rufus_amd RUFUS.Filter: ", &blocks_);
     int cur = 0;
     for (Mate& M : mate_) fill(M, M.arena[cur]);
     for (;;) {
@@ -2086,10 +2019,10 @@ class BgzfPairFilter {
       const uint64_t n = std::min(r1, r2);
       if (n == 0) {
         if (r1 == 0) {
-          if (!mate_[0].closed || rfx_text_bytes(t[0]) > 1) not_strict();  // a full arena without a record / a file that ends inside one
-          break;                                                           // mate 1 is at its end
+          if (!mate_[0].closed || rfx_text_bytes(t[0]) > 1) die_not_strict();  // a full arena without a record / a file that ends inside one
+          break;                                                               // mate 1 is at its end
         }
-        if (!mate_[1].closed || rfx_text_bytes(t[1]) > 1) not_strict();
+        if (!mate_[1].closed || rfx_text_bytes(t[1]) > 1) die_not_strict();
         die("rufus_amd RUFUS.Filter: mate files hold different numbers of records");
       }
       for (int m = 0; m < 2; ++m) cut(t[m], nx[m], n);
@@ -2098,7 +2031,7 @@ class BgzfPairFilter {
       for (int m = 0; m < 2; ++m) {
         int strict = 1;
         rd[m] = rfx_text_parse(t[m], RFX_PACK_FILTER, min_q_, &strict);
-        if (!rd[m] && !strict) not_strict();
+        if (!rd[m] && !strict) die_not_strict();
         if (!rd[m]) fail("rfx_text_parse", RFX_E_HIP);
       }
       if (rfx_reads_of_length(rd[0], 0))
@@ -2122,7 +2055,7 @@ class BgzfPairFilter {
       if (any)
         for (int m = 0; m < 2; ++m) gather(mate_[m], t[m], either.data(), n, &bytes[m], &sel[m]);
       if (sel[0] != sel[1]) die("rufus_amd RUFUS.Filter: the two mates' gathers disagree");
-      sink_(mate_[0].out, (size_t)bytes[0], mate_[1].out, (size_t)bytes[1], n, sel[0]);
+      sink_((const char*)mate_[0].out.p, (size_t)bytes[0], (const char*)mate_[1].out.p, (size_t)bytes[1], n, sel[0]);
       ++steps_;
       pairs_ += n;
       pulled_ += sel[0];
@@ -2308,18 +2241,7 @@ class BamSingleFilter {
   std::function<void(const char*, size_t)> sink_;
   std::vector<uint32_t> runs_buf_;
   std::vector<std::string> chr_log_;
-  struct Pinned {
-    void* p = nullptr;
-    size_t cap = 0;
-    void need(size_t bytes) {
-      if (bytes <= cap) return;
-      if (p) rfx_host_free(p);
-      cap = bytes + bytes / 4 + 4096;
-      p = rfx_host_alloc(cap);
-      if (!p) die("rufus_amd: cannot allocate page-locked memory for the pulled records");
-    }
-    ~Pinned() { if (p) rfx_host_free(p); }
-  } out_, hits_;
+  PinnedBuf out_, hits_;
   rfxsam::BamSingleTail tail_;
   uint64_t arenas_ = 0, records_ = 0, reads_ = 0;
   std::string region_, bam_path_, ingest_counts_;
@@ -2489,27 +2411,15 @@ class BamCachePull {
       die(std::string(TOOL) + ": --packed: " + err + " (RFX_BAM_ARENA)");
     rfx_text* arena = rfx_text_open(ctx_, arena_bytes_);
     if (!arena) fail("rfx_text_open");
-    struct Buf { char* p = nullptr; long ticket = -1; };
-    std::vector<Buf> ring(4);
-    for (Buf& b : ring) {
-      b.p = (char*)rfx_host_alloc(piece_);
-      if (!b.p) die("rufus_amd: cannot allocate page-locked buffers for the compressed input");
-    }
-    auto settle_buf = [&](Buf& b) {
-      if (b.ticket >= 0 && rfx_text_wait(arena, b.ticket) != RFX_OK) die(std::string("rufus_amd: rfx_text_wait: ") + rfx_last_error());
-      b.ticket = -1;
-    };
+    PinnedRing ring(4, piece_);
     std::vector<uint8_t> out;
     std::vector<uint32_t> nbytes;
     bool same = true;
-    size_t next_buf = 0;
     for (const rfxbamcache::Batch& b : plan) {
       // the batch's blocks, one behind the other (blocks that are not neighbours in the file are each self-contained)
       size_t k = 0;
       while (k < b.block.size()) {
-        Buf& buf = ring[next_buf];
-        next_buf = (next_buf + 1) % ring.size();
-        settle_buf(buf);
+        PinnedRing::Buf& buf = ring.take();
         size_t used = 0;
         for (; k < b.block.size(); ++k) {
           const rfxbamcache::IndexEntry& e = cache.index[b.block[k]];
@@ -2520,8 +2430,8 @@ class BamCachePull {
         }
         const long tk = rfx_text_append_bgzf(arena, buf.p, used);
         if (tk == RFX_E_FORMAT) { same = false; break; }  // (not whole BGZF blocks where the index says blocks are)
-        if (tk < 0) die(std::string("rufus_amd: rfx_text_append_bgzf: ") + rfx_strerror((int)tk) + " " + rfx_last_error());
-        buf.ticket = tk;
+        if (tk < 0) die_rc("rfx_text_append_bgzf", (int)tk);
+        PinnedRing::sent(buf, arena, tk);
       }
       blocks_ += b.block.size();
       ++batches_;
@@ -2545,12 +2455,11 @@ class BamCachePull {
         tail_.add(out.data(), p, std::binary_search(hit_index_.begin(), hit_index_.end(), sel_index[b.first + i]));
         p += nbytes[i];
       }
-      for (Buf& x : ring) settle_buf(x);  // (an arena's tickets die with its reset)
+      ring.settle_arena(arena);
       rfx_text_reset(arena);
       if (!same) break;
     }
-    for (Buf& x : ring) rfx_host_free(x.p);
-    rfx_text_close(arena);
+    rfx_text_close(arena);  // (nothing of the ring is in flight: every batch ends in settle_arena)
     return same;
   }
   const std::string& mate1() const { return tail_.walk.o1; }

@@ -67,9 +67,7 @@ static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<u
     (void)madvise(p, sizes[m], MADV_SEQUENTIAL);
     map[m] = (const char*)p;
   }
-  size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
-  if (const char* ev = getenv("RFX_FILTER_ARENA")) arena = (size_t)std::max(0ll, atoll(ev));
-  if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+  const size_t arena = env_arena("RFX_FILTER_ARENA", 0), piece = env_piece((size_t)8 << 20);  // (the route refuses an arena below 256 KiB)
   unsigned long long total = 0, found = 0;
   {
     BgzfPairFilter route(
@@ -223,8 +221,7 @@ static int run(int argc, char** argv) {
   helpers = std::min(helpers, rfx_host_cpus() > 2 ? rfx_host_cpus() - 2 : 1u);
   if (const char* ev = getenv("RFX_HOST_THREADS")) helpers = (unsigned)std::max(1, atoi(ev));
   helpers = std::max(helpers, (unsigned)n_gpu);
-  size_t PIECE = 32u << 20;
-  if (const char* ev = getenv("RFX_INGEST_PIECE")) PIECE = (size_t)std::max(1024, atoi(ev));
+  const size_t PIECE = env_piece(32u << 20);
   const size_t LAG = 3;
   const size_t MAX_IN_FLIGHT = 2 * (size_t)helpers + 2 + LAG;
 
@@ -816,9 +813,7 @@ static int run(int argc, char** argv) {
   void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
   if (m == MAP_FAILED) die(std::string(TOOL) + ": --bam: cannot map the input: " + strerror(errno));
   (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
-  size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
-  if (const char* ev = getenv("RFX_BAM_ARENA")) arena = (size_t)std::max(1ll << 20, atoll(ev));
-  if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+  const size_t arena = env_arena("RFX_BAM_ARENA"), piece = env_piece((size_t)8 << 20);
 #ifdef RFX_SINGLE_END
   {
     BamSingleFilter route(
@@ -906,9 +901,7 @@ static int run_cached(int argc, char** argv) {
   std::vector<uint64_t> keys((size_t)nk + 1);
   rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
   printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
-  size_t arena = (size_t)1 << 30, piece = (size_t)8 << 20;
-  if (const char* ev = getenv("RFX_BAM_ARENA")) arena = (size_t)std::max(1ll << 20, atoll(ev));
-  if (const char* ev = getenv("RFX_INGEST_PIECE")) piece = (size_t)std::max(1024ll, atoll(ev));
+  const size_t arena = env_arena("RFX_BAM_ARENA"), piece = env_piece((size_t)8 << 20);
   rfx_ctx* ctx = open_ctxs(gpus)[0];
   rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
   if (!set) die(std::string("rufus_amd: ") + rfx_last_error());

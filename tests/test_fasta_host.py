@@ -164,6 +164,57 @@ def test_ingest_refuses_a_sequence_that_does_not_fit_an_arena(harness, tmp_path)
     assert reads == F.read_crcs(F.pack(tools.parse_sequences(text)))
 
 
+# ---- the FASTQ mode's end of file and the ring's wrap-around ----------------------------------------------------------------
+# The smallest arena at which a run is one block and a whole block still fits; piece 1024, so a ring buffer is 64 KiB.
+FQ_ARENA = 262144
+
+
+def fastq_records(rng, lens):
+    seqs = [F.bases(rng, int(L), b"ACGTN") for L in lens]
+    return [b"@q%d some words\n%s\n+\n%s\n" % (i, s, b"I" * len(s)) for i, s in enumerate(seqs)]
+
+
+def fastq_outcome(harness, d, text, blob, n_blocks, n_records, min_arenas):
+    reads, _, oks = outcome(ingest(harness, d, [blob], arena=FQ_ARENA))
+    assert reads == F.read_crcs(F.pack(tools.parse_sequences(text)))
+    w = oks[0].split()  # ok bgzf route: B blocks in A appends, N arenas, R reads
+    assert w[1:3] == ["bgzf", "route:"], oks[0]
+    assert (int(w[3]), int(w[6]), int(w[10])) == (n_blocks, n_blocks, n_records), oks[0]  # (a run is one block)
+    assert int(w[8]) >= min_arenas, oks[0]
+
+
+@pytest.mark.parametrize("final_newline", [True, False])
+def test_ingest_fastq_over_arenas_and_a_wrapped_ring(harness, tmp_path, final_newline):
+    """Ten blocks and the EOF marker through the four buffers of the ring (it wraps twice); four blocks fill an arena, so two
+    arenas are cut before the file's end, which comes with and without the last newline."""
+    rng = np.random.default_rng(43)
+    recs = fastq_records(rng, rng.integers(30, 260, 1900))
+    text = b"".join(recs)
+    assert len(text) > 9 * 60000
+    text = text if final_newline else text[:-1]
+    blob = B.write(text, 1, cut=60000)
+    n_blocks = len(B.split(blob))
+    assert n_blocks >= 10
+    fastq_outcome(harness, str(tmp_path), text, blob, n_blocks, len(recs), 3)
+
+
+def test_ingest_fastq_whose_last_record_is_cut_by_the_first_arena(harness, tmp_path):
+    """The first arena takes ten blocks of 26000 bytes and ends inside the file's last record, whose rest does not fit the
+    room that is left: the record's head is carried, its rest arrives behind it, and -- the file has no final newline -- the
+    whole record is carried once more, to the arena that gets the newline."""
+    rng = np.random.default_rng(47)
+    end = 10 * 26000
+    recs = fastq_records(rng, rng.integers(30, 260, 1200))
+    recs = recs[:int(np.searchsorted(np.cumsum([len(x) for x in recs]), end - 3000))]
+    size = sum(len(x) for x in recs)
+    recs.append(fastq_records(rng, [4000])[0][:-1])  # the last record, without its newline
+    text = b"".join(recs)
+    assert size < end and len(text) - end > FQ_ARENA - end  # (it starts in the first arena; its rest is more than the room)
+    cuts = list(range(0, end + 1, 26000)) + [len(text)]
+    blob = b"".join(B.block(text[a:b], 1) for a, b in zip(cuts, cuts[1:])) + B.EOF
+    fastq_outcome(harness, str(tmp_path), text, blob, 12, len(recs), 2)
+
+
 def test_ingest_takes_a_fasta_beside_a_fastq(harness, tmp_path):
     rng = np.random.default_rng(41)
     fa = b"".join(small_records(rng, 40))
