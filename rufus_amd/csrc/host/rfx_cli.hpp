@@ -610,6 +610,38 @@ inline void drop_mapped(const char* b, const char* e) {
   if (hi > lo) (void)madvise((void*)lo, (size_t)(hi - lo), MADV_DONTNEED);
 }
 
+// A regular file mapped read-only, whole.  ok == false: not a regular file, an empty one (unless `empty_ok`: then ok with
+// p null and n 0), or mmap refused (errno says why) -- every caller has its own sentence, or its own way round.
+// `sequential`: madvise(MADV_SEQUENTIAL), for the tools that walk the file front to back.  By path: opened, mapped and
+// closed again (the mapping stays).
+struct Mapped {
+  const char* p = nullptr;
+  size_t n = 0;
+  bool ok = false;
+};
+inline Mapped map_regular(int fd, bool sequential, bool empty_ok = false) {
+  Mapped m;
+  struct stat sb;
+  if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return m;
+  m.n = (size_t)sb.st_size;
+  if (!m.n) {
+    m.ok = empty_ok;
+    return m;
+  }
+  void* p = mmap(nullptr, m.n, PROT_READ, MAP_PRIVATE, fd, 0);
+  if (p == MAP_FAILED) return m;
+  if (sequential) (void)madvise(p, m.n, MADV_SEQUENTIAL);
+  m.p = (const char*)p;
+  m.ok = true;
+  return m;
+}
+inline Mapped map_regular(const char* path, bool sequential, bool empty_ok = false) {
+  const int fd = ::open(path, O_RDONLY);
+  const Mapped m = map_regular(fd, sequential, empty_ok);
+  if (fd >= 0) ::close(fd);
+  return m;
+}
+
 // Is the open file bgzip'd?  A regular file of `size` bytes whose first block rfx_bgzf_scan accepts (plain gzip has no
 // `BC` subfield and is not).  What sends an input down the device-inflate routes of `jellyfish count` and `RUFUS.Filter`.
 inline bool is_bgzf(int fd, bool regular, uint64_t size) {

@@ -11,15 +11,17 @@
 // they are read interleaved, 4 lines each (src/RUFUS.Filter.cpp:165-173) -- never one file ahead.
 // Pulled records are written in input order (the reference's order depends on OpenMP scheduling; at
 // one thread it is input order too).  The scan itself runs in k_filter; no CPU fallback.
+//
+// Every route is parse(argc, argv, FilterArgs&) -- the usage line, the argument count -- and a body that takes the
+// FilterArgs; a route that falls back to another calls that route's body with a changed copy.  What the bodies share
+// (hash list, devices, staging memory, the scan step, the output files and the finish) stands once, in front of them; each
+// body calls it in its own order, which is the order of its refusals.  main() only dispatches.
 #include <condition_variable>
 #include <deque>
 #include <fstream>
 #include <map>
 #include <memory>
 #include <mutex>
-
-#include <sys/mman.h>
-#include <sys/stat.h>
 
 #include "rfx_cli.hpp"
 
@@ -32,7 +34,7 @@ using namespace rfxcli;
 #include "rfx_bam_cache.hpp"
 #include "rfx_ingest.hpp"
 
-// the two executables this source makes: what differs between them in the routes both have (--sam, --bam)
+// the two executables this source makes; everything below asks SINGLE, nothing else asks the preprocessor
 #ifdef RFX_SINGLE_END
 static constexpr int SINGLE = 1;
 static const char* const TOOL = "rufus_amd RUFUS.Filter.single";
@@ -41,56 +43,215 @@ static constexpr int SINGLE = 0;
 static const char* const TOOL = "rufus_amd RUFUS.Filter";
 #endif
 
-#ifndef RFX_SINGLE_END
+// ---- what the routes share ---------------------------------------------------------------------------------------------
+// One run of one route.  The strings are argv's (or a caller's that outlives the run).
+struct FilterArgs {
+  const char* cache = nullptr;     // --packed
+  const char* chr = nullptr;       // the chromosome log (the flag routes)
+  const char* hashlist = nullptr;
+  const char* in1 = nullptr;       // mate 1 / the one FASTQ, the SAM stream, the spool, the BAM
+  const char* in2 = nullptr;       // mate 2 (the paired text route)
+  std::string stub;
+  int k = 0, min_q = 0, thresh = 0, threads = 0;
+  uint32_t exclude = 3328;         // --bam-exclude
+  const char* region = nullptr;    // --region
+  bool has_caller = false;         // this run's caller still has work to do (a temporary file to remove): no leave()
+};
+// CHRFILE HashList INPUT STUB K MinQ HashCountThreshold Threads, as the flag routes find them from v[0] on
+static void positional(FilterArgs& a, char** v) {
+  a.chr = v[0];
+  a.hashlist = v[1];
+  a.in1 = v[2];
+  a.stub = v[3];
+  a.k = atoi(v[4]);
+  a.min_q = atoi(v[5]);
+  a.thresh = atoi(v[6]);
+  a.threads = atoi(v[7]);
+}
+
+// An input by name; the first `stdin_names` of "stdin", "/dev/stdin", "-" mean descriptor 0.  < 0: said so on stdout, and
+// the caller returns 0 (the reference tools report on stdout and exit 0; the shell checks for empty outputs).
+static int open_input(const char* path, int stdin_names) {
+  static const char* const names[] = {"stdin", "/dev/stdin", "-"};
+  for (int i = 0; i < stdin_names; ++i)
+    if (strcmp(path, names[i]) == 0) return 0;
+  const int fd = ::open(path, O_RDONLY);
+  if (fd < 0) printf("Error, MutFile could not be opened");
+  return fd;
+}
+
+// The hash list in two steps, because the routes open their inputs and outputs between them.  false: said so, return 0.
+static bool read_hash_list(const char* path, std::string& text) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f.is_open()) {
+    printf("Error, ParentHashFile could not be opened");
+    return false;
+  }
+  text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+  return true;
+}
+// -> the keys and one spare slot (size() - 1 keys).  `tool` names the executable where k is refused; `announce`: the
+// reference's two lines (not wanted from a route whose inner run prints them).
+static std::vector<uint64_t> load_keys(const std::string& text, int k, const std::string& tool, bool announce = true) {
+  if (k < 1 || k > 32) die(tool + ": hash size must be 1..32");
+  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, nullptr, 0);
+  if (nk < 0) die("rufus_amd: cannot parse the hash list");
+  std::vector<uint64_t> keys((size_t)nk + 1);
+  rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, keys.data(), keys.size());
+  if (announce) printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
+  return keys;
+}
+
+// The devices of a run (RUFUS_GPUS; a route that needs exactly one says so in its own words before it opens them), the
+// k-mer set on each, and a lock per device: uploads and scans of one device go one at a time.
+struct Devices {
+  std::vector<rfx_ctx*> ctxs;
+  std::vector<rfx_set*> sets;
+  std::vector<std::mutex> mu;
+  size_t size() const { return ctxs.size(); }
+  void open(const std::vector<int>& gpus, const std::vector<uint64_t>& keys, int k, const char* traced) {
+    ctxs = open_ctxs(gpus);
+    for (rfx_ctx* c : ctxs) {
+      rfx_set* st = rfx_set_build(c, keys.data(), (uint64_t)keys.size() - 1, k);
+      if (!st) die(std::string("rufus_amd: ") + rfx_last_error());
+      sets.push_back(st);
+    }
+    mu = std::vector<std::mutex>(ctxs.size());
+    trace(traced);
+  }
+  // One packed block through device d: up, scanned, freed.  The paired tool never examines a read's last base
+  // (`i < length()-1`, src/RUFUS.Filter.cpp:203) and wants the hit bit per read (`mask`); the single-end tool examines it
+  // and wants the counts too (`hits`, else null; src/RUFUS.Filter.ss.cpp:176-198).
+  void scan_block(size_t d, const uint64_t* codes, const uint32_t* good, const uint32_t* woff, const uint32_t* lens, uint32_t n,
+                  int thresh, uint32_t* hits, uint64_t* mask) {
+    std::lock_guard<std::mutex> g(mu[d]);
+    rfx_reads* rd = rfx_reads_upload(ctxs[d], codes, nullptr, good, woff, lens, n);
+    if (!rd) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
+    uint64_t nh = 0;
+    const int rc = rfx_filter(sets[d], rd, thresh, SINGLE ? 0 : 1, hits, mask, &nh);
+    rfx_reads_free(rd);
+    if (rc) die(std::string("rufus_amd: filter failed: ") + rfx_last_error());
+  }
+  void close() {
+    for (rfx_set* st : sets) rfx_set_free(st);
+    for (rfx_ctx* c : ctxs) rfx_close(c);
+  }
+};
+
+// Packed reads go up from page-locked memory (a pageable source costs a staging copy inside the runtime, under the
+// device lock).  A buffer asked for while the device is still being opened is plain memory, page-locked by lock() before
+// its first upload.  (rfx_ingest.hpp's PinnedBuf grows by another rule and stays what it is.)
+struct Pinned {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool locked = false;
+  void* need(size_t bytes, bool device_up) {  // null: no memory
+    if (bytes > cap) {
+      if (p) rfx_host_free(p);
+      cap = bytes + bytes / 4;
+      p = device_up ? rfx_host_alloc(cap) : rfx_host_alloc_lazy(cap);
+      locked = device_up;
+    }
+    return p;
+  }
+  void lock() {
+    if (p && !locked) (void)rfx_host_pin(p);  // (refused: the upload stages the pageable buffer itself)
+    locked = true;
+  }
+  ~Pinned() { if (p) rfx_host_free(p); }
+};
+// the four arrays of a packed block of n reads in `words` words, as rfx_pack_spans fills and scan_block uploads them
+struct Staging {
+  Pinned pin[4];
+  uint64_t* codes = nullptr;
+  uint32_t *good = nullptr, *woff = nullptr, *lens = nullptr;
+  bool need(uint64_t words, size_t n, bool device_up = true) {  // false: no memory (the caller refuses, in its own way)
+    codes = (uint64_t*)pin[0].need((words + 1) * 8, device_up);
+    good = (uint32_t*)pin[1].need((words + 1) * 4, device_up);
+    woff = (uint32_t*)pin[2].need((n + 1) * 4, device_up);
+    lens = (uint32_t*)pin[3].need((n + 1) * 4, device_up);
+    return codes && good && woff && lens;
+  }
+  void lock() {
+    for (Pinned& b : pin) b.lock();
+  }
+};
+static const char* const NO_STAGING = "rufus_amd: cannot allocate pinned staging memory";
+
+// What a run writes: the chromosome log (the flag routes) and STUB.Mutations.Mate1.fastq / .Mate2.fastq, or
+// STUB.Mutations.fastq alone: the single-end tool never opens out2, and what is written to it goes nowhere.
+struct Outputs {
+  FILE* chr = nullptr;
+  std::ofstream out1, out2;
+  bool open(const char* chr_path, const std::string& stub) {  // false: said so, return 0
+    if (chr_path) chr = fopen(chr_path, "w");
+    out1.open((stub + (SINGLE ? ".Mutations.fastq" : ".Mutations.Mate1.fastq")).c_str(), std::ios::binary);
+    if (!SINGLE) out2.open((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
+    if ((chr_path && !chr) || !out1.is_open() || (!SINGLE && !out2.is_open())) {
+      printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
+      return false;
+    }
+    return true;
+  }
+  // The end of a run: what is still to be written (the log's lines, the mates' text; each may be empty), everything
+  // closed, the route's counts to the trace, the reference's last line, and the process leaves (rfx_cli.hpp leave():
+  // unmapping 20 GB of input, unpinning the staging blocks and the runtime's own teardown took 0.5 s of a 1.5 s run) --
+  // unless RFX_CLEAN_EXIT=1 asks for the orderly way, or the run has a caller: then the route's teardown follows.
+  void finish(const std::vector<std::string>& chr_log, const std::string& mate1, const std::string& mate2, const std::string& counts,
+              bool has_caller = false) {
+    if (chr) {
+      for (const std::string& name : chr_log) fprintf(chr, "%s\n", name.c_str());
+      fclose(chr);
+    }
+    out1.write(mate1.data(), (std::streamsize)mate1.size());
+    out2.write(mate2.data(), (std::streamsize)mate2.size());
+    out1.close();
+    out2.close();
+    if (!counts.empty()) trace(counts.c_str());
+    printf("\nDone running RUFUS.Filter.cpp\n");
+    if (!has_caller) leave(0);
+  }
+};
+
 // ---- RUFUS.Filter HashList A.fastq.gz B.fastq.gz STUB K MinQ HashCountThreshold Threads --------------------------------
 // Both mate files bgzip'd (regular files whose first block rfx_bgzf_scan accepts): replaces runRufus.sh:974-977's
 // `<(zcat A) <(zcat B)`.  The files are mapped and handed to rfx_ingest.hpp's BgzfPairFilter: inflated, parsed, scanned
 // and the pulled pairs' text gathered on the device; this thread reads the files and appends what comes back to
 // STUB.Mutations.Mate1.fastq / .Mate2.fastq, in input order.  RFX_FILTER_ARENA: bytes of text per arena (four arenas).
+// Paired only; the text route (below) sends it here.
 namespace bgzff {
-static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<uint64_t>& keys, long nk, int k, int min_q, int thresh,
-               std::ofstream& out1, std::ofstream& out2) {
+static int run(const FilterArgs& a, int fd1, int fd2, const std::vector<uint64_t>& keys, Outputs& out) {
   const std::vector<int> gpus = gpu_list();
   if (gpus.size() != 1)
     die("rufus_amd RUFUS.Filter: BGZF input is inflated on the device, which needs one device (RUFUS_GPUS names more): "
         "inflate it and pipe it in");
-  rfx_ctx* ctx = open_ctxs(gpus)[0];
-  rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
-  if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
-  trace("filter: device open, set built");
-  const char* map[2];
-  const int fds[2] = {fd1, fd2};
-  const size_t sizes[2] = {size1, size2};
+  Devices dv;
+  dv.open(gpus, keys, a.k, "filter: device open, set built");
+  Mapped map[2];
   for (int m = 0; m < 2; ++m) {
-    void* p = mmap(nullptr, sizes[m], PROT_READ, MAP_PRIVATE, fds[m], 0);
-    if (p == MAP_FAILED) die(std::string("rufus_amd RUFUS.Filter: cannot map a mate file: ") + strerror(errno));
-    (void)madvise(p, sizes[m], MADV_SEQUENTIAL);
-    map[m] = (const char*)p;
+    map[m] = map_regular(m ? fd2 : fd1, true);
+    if (!map[m].ok) die(std::string("rufus_amd RUFUS.Filter: cannot map a mate file: ") + strerror(errno));
   }
   const size_t arena = env_arena("RFX_FILTER_ARENA", 0), piece = env_piece((size_t)8 << 20);  // (the route refuses an arena below 256 KiB)
   unsigned long long total = 0, found = 0;
   {
     BgzfPairFilter route(
-        ctx, set, min_q, thresh,
-        [&](const char* a, size_t na, const char* b, size_t nb, uint64_t pairs, uint64_t pulled) {
-          out1.write(a, (std::streamsize)na);
-          out2.write(b, (std::streamsize)nb);
+        dv.ctxs[0], dv.sets[0], a.min_q, a.thresh,
+        [&](const char* t1, size_t n1, const char* t2, size_t n2, uint64_t pairs, uint64_t pulled) {
+          out.out1.write(t1, (std::streamsize)n1);
+          out.out2.write(t2, (std::streamsize)n2);
           total += pairs;
           found += pulled;
           printf("Read in %llu lines: Found %llu \r", total * 4, found);
         },
         arena, piece);
     trace("filter: bgzf route, text arenas open");
-    route.run(map[0], sizes[0], map[1], sizes[1]);
+    route.run(map[0].p, map[0].n, map[1].p, map[1].n);
     trace(route.counts().c_str());
     trace("filter: all pieces written");
-    out1.close();
-    out2.close();
-    printf("\nDone running RUFUS.Filter.cpp\n");
-    leave(0);  // (outputs closed: see the text route's end)
+    out.finish({}, "", "", "");
   }
-  rfx_set_free(set);
-  rfx_close(ctx);
+  dv.close();
   return 0;
 }
 }  // namespace bgzff
@@ -108,16 +269,12 @@ static int run(int fd1, size_t size1, int fd2, size_t size2, const std::vector<u
 // order the pairs complete.  The same bytes as the two-process route; no FASTQ text exists for the other pairs.
 // A waiting record is a pointer into its piece (no copy); a piece is recycled LAG pieces later, and only the few
 // records that still wait then (mates far apart, unpaired reads) are copied out.
-namespace bamf {
-static int run_cached(int argc, char** argv);  // --packed with a BAM-kind cache (below)
-}
-#endif
-// RUFUS.Filter.single --sam CHRFILE HashList SAM|stdin STUB K MinQ HashCountThreshold Threads (-DRFX_SINGLE_END): the same
-// pipeline -- reader, helper threads, the stranded form packed per record, the chromosome log -- for what
-// `PassThroughSamCheck.stranded.se CHR | RUFUS.Filter.single HashList stdin ...` does with the stream (runRufus.sh:1031-1032;
-// a CRAM subject, :609, gets one process instead of two).  The scan examines the last base too (`i < length()`,
-// src/RUFUS.Filter.ss.cpp:176) and the counts come back; there is no pairing: the records whose count reaches the threshold
-// are written in stream order to STUB.Mutations.fastq with ":MH<hits>" (:194-203).
+//
+// RUFUS.Filter.single --sam (the same arguments): the same pipeline -- reader, helper threads, the stranded form packed
+// per record, the chromosome log -- for what `PassThroughSamCheck.stranded.se CHR | RUFUS.Filter.single HashList stdin ...`
+// does with the stream (runRufus.sh:1031-1032; a CRAM subject, :609, gets one process instead of two).  The scan examines
+// the last base too (`i < length()`, src/RUFUS.Filter.ss.cpp:176) and the counts come back; there is no pairing: the
+// records whose count reaches the threshold are written in stream order to STUB.Mutations.fastq with ":MH<hits>" (:194-203).
 namespace samf {
 using namespace rfxsam;
 
@@ -157,76 +314,44 @@ struct SPiece {
   std::vector<uint32_t> waited;  // records of this piece that went into the waiting table
   uint64_t seq = 0;
 };
-static bool in_process = false;  // run() called by run_packed: it has a temporary file to remove afterwards
 
-static int run(int argc, char** argv) {
-  printf("Call is --sam CHRFILE PreBuiltMutHash SAM|stdin firstpassfile hashsize MinQ HashCountThreshold threads\n");
+static const char* const USAGE = "Call is --sam CHRFILE PreBuiltMutHash SAM|stdin firstpassfile hashsize MinQ HashCountThreshold threads\n";
+static bool parse(int argc, char** argv, FilterArgs& a) {
+  fputs(USAGE, stdout);
   if (argc < 10) {
     printf("ERROR: expected 9 arguments\n");
-    return 0;
+    return false;
   }
-  const char* chr_path = argv[2];
-  const char* hashlist = argv[3];
-  const char* sam = argv[4];
-  const std::string stub = argv[5];
-  const int k = atoi(argv[6]), min_q = atoi(argv[7]), thresh = atoi(argv[8]);
+  positional(a, argv + 2);
+  return true;
+}
+
+static int run(const FilterArgs& a) {
+  const int min_q = a.min_q, thresh = a.thresh;
   std::string text;
-  {
-    std::ifstream f(hashlist, std::ios::binary);
-    if (!f.is_open()) {
-      printf("Error, ParentHashFile could not be opened");
-      return 0;
-    }
-    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-  }
-  const int fd = strcmp(sam, "stdin") == 0 || strcmp(sam, "/dev/stdin") == 0 || strcmp(sam, "-") == 0 ? 0 : ::open(sam, O_RDONLY);
-  if (fd < 0) {
-    printf("Error, MutFile could not be opened");
-    return 0;
-  }
-  FILE* chr = fopen(chr_path, "w");
-#ifdef RFX_SINGLE_END
-  std::ofstream out1((stub + ".Mutations.fastq").c_str(), std::ios::binary);
-  if (!chr || !out1.is_open()) {
-#else
-  std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
-  std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
-  if (!chr || !out1.is_open() || !out2.is_open()) {
-#endif
-    printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
-    return 0;
-  }
-  if (k < 1 || k > 32) die(std::string(TOOL) + ": hash size must be 1..32");
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, nullptr, 0);
-  if (nk < 0) die("rufus_amd: cannot parse the hash list");
-  std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, keys.data(), keys.size());
-  printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
+  if (!read_hash_list(a.hashlist, text)) return 0;
+  const int fd = open_input(a.in1, 3);
+  if (fd < 0) return 0;
+  Outputs out;
+  if (!out.open(a.chr, a.stub)) return 0;
+  const std::vector<uint64_t> keys = load_keys(text, a.k, TOOL);
   // RUFUS_GPUS: the pieces are dealt to the devices by helper thread (the filter shards by read block)
-  const std::vector<int> gpus = gpu_list();
-  const int n_gpu = (int)gpus.size();
-  std::vector<rfx_ctx*> ctxs = open_ctxs(gpus);
-  std::vector<rfx_set*> sets;
-  for (rfx_ctx* c : ctxs) {
-    rfx_set* st = rfx_set_build(c, keys.data(), (uint64_t)nk, k);
-    if (!st) die(std::string("rufus_amd: ") + rfx_last_error());
-    sets.push_back(st);
-  }
-  trace("filter --sam: device open, set built");
+  Devices dv;
+  dv.open(gpu_list(), keys, a.k, "filter --sam: device open, set built");
+  const unsigned n_gpu = (unsigned)dv.size();
 #ifdef F_SETPIPE_SZ
   (void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);
 #endif
 
-  unsigned helpers = (unsigned)std::max(1, atoi(argv[9]));
+  unsigned helpers = (unsigned)std::max(1, a.threads);
   helpers = std::min(helpers, rfx_host_cpus() > 2 ? rfx_host_cpus() - 2 : 1u);
   if (const char* ev = getenv("RFX_HOST_THREADS")) helpers = (unsigned)std::max(1, atoi(ev));
-  helpers = std::max(helpers, (unsigned)n_gpu);
+  helpers = std::max(helpers, n_gpu);
   const size_t PIECE = env_piece(32u << 20);
   const size_t LAG = 3;
   const size_t MAX_IN_FLIGHT = 2 * (size_t)helpers + 2 + LAG;
 
   std::mutex mu;
-  std::vector<std::mutex> dev_mu((size_t)n_gpu);
   std::condition_variable cv;
   std::deque<SPiece*> todo, spare;
   std::map<uint64_t, SPiece*> done;
@@ -235,19 +360,10 @@ static int run(int argc, char** argv) {
   size_t in_flight = 0;
   // A regular file (the spool `jellyfish count --spool` left, a SAM file): mapped and cut at line ends, no copy -- one
   // reader thread copying out of the page cache gave 5.8 GB/s, less than the helpers parse.
-  const char* map = nullptr;
-  size_t map_size = 0;
-  {
-    struct stat sb;
-    if (fd != 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0 && !getenv("RFX_FILTER_NO_MMAP")) {
-      void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m != MAP_FAILED) {
-        (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
-        map = (const char*)m;
-        map_size = (size_t)sb.st_size;
-      }
-    }
-  }
+  Mapped file;
+  if (fd != 0 && !getenv("RFX_FILTER_NO_MMAP")) file = map_regular(fd, true);
+  const char* map = file.p;
+  const size_t map_size = file.n;
   std::thread reader([&] {
     if (map) {
       size_t at = 0;
@@ -323,22 +439,7 @@ static int run(int argc, char** argv) {
 
   auto helper = [&](unsigned me) {
     const size_t dev = (size_t)me % (size_t)n_gpu;
-    rfx_ctx* ctx = ctxs[dev];
-    rfx_set* set = sets[dev];
-    struct Pinned {
-      void* p = nullptr;
-      size_t cap = 0;
-      void* need(size_t bytes) {
-        if (bytes > cap) {
-          if (p) rfx_host_free(p);
-          cap = bytes + bytes / 4;
-          p = rfx_host_alloc(cap);
-          if (!p) die("rufus_amd: cannot allocate pinned staging memory");
-        }
-        return p;
-      }
-      ~Pinned() { if (p) rfx_host_free(p); }
-    } pin_codes, pin_good, pin_woff, pin_lens;
+    Staging stage;
     std::vector<uint64_t> so, qo;
     std::vector<uint32_t> sl;
     std::string rs, rq;
@@ -410,23 +511,13 @@ static int run(int argc, char** argv) {
             qo[i] = (uint64_t)((uintptr_t)side - (uintptr_t)base);
           }
         }
-        uint64_t* codes = (uint64_t*)pin_codes.need((words + 1) * 8);
-        uint32_t* good = (uint32_t*)pin_good.need((words + 1) * 4);
-        uint32_t* woff = (uint32_t*)pin_woff.need((n + 1) * 4);
-        uint32_t* lens = (uint32_t*)pin_lens.need((n + 1) * 4);
-        woff[0] = 0;
-        if (rfx_pack_spans(base, so.data(), sl.data(), qo.data(), (uint32_t)n, min_q, RFX_PACK_FILTER, codes, nullptr, good,
-                           woff, lens) != RFX_OK)
+        if (!stage.need(words, n)) die(NO_STAGING);
+        stage.woff[0] = 0;
+        if (rfx_pack_spans(base, so.data(), sl.data(), qo.data(), (uint32_t)n, min_q, RFX_PACK_FILTER, stage.codes, nullptr,
+                           stage.good, stage.woff, stage.lens) != RFX_OK)
           die("rufus_amd: pack failed");
-        std::lock_guard<std::mutex> g(dev_mu[dev]);
-        rfx_reads* rd = rfx_reads_upload(ctx, codes, nullptr, good, woff, lens, (uint32_t)n);
-        if (!rd) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
-        uint64_t nh = 0;
-        // (the paired tool never examines a read's last base, src/RUFUS.Filter.cpp:203; the single-end tool does and wants
-        // the counts, src/RUFUS.Filter.ss.cpp:176-198)
-        const int rc = rfx_filter(set, rd, thresh, SINGLE ? 0 : 1, SINGLE ? pc.hits.data() : nullptr, pc.mask.data(), &nh);
-        rfx_reads_free(rd);
-        if (rc) die(std::string("rufus_amd: filter failed: ") + rfx_last_error());
+        dv.scan_block(dev, stage.codes, stage.good, stage.woff, stage.lens, (uint32_t)n, thresh,
+                      SINGLE ? pc.hits.data() : nullptr, pc.mask.data());
       }
       std::lock_guard<std::mutex> g(mu);
       done[pc.seq] = pcp;
@@ -434,13 +525,11 @@ static int run(int argc, char** argv) {
     }
   };
   std::vector<std::thread> workers;
-  helpers = std::max(helpers, (unsigned)n_gpu);
   for (unsigned t = 0; t < helpers; ++t) workers.emplace_back(helper, t);
 
   PairWalk walk;  // (rfx_sam.hpp: the walk `--bam` runs too)
   WaitTable& waiting = walk.waiting;
   std::string &o1 = walk.o1, &o2 = walk.o2;
-  (void)o2;
   unsigned long long &n_pairs = walk.n_pairs, &n_found = walk.n_found;
   std::deque<SPiece*> live;
   std::string current = "notachr";
@@ -477,15 +566,19 @@ static int run(int argc, char** argv) {
     }
     for (const std::string& name : pc->chr_runs)
       if (name != current) {
-        fprintf(chr, "%s\n", current.c_str());
+        fprintf(out.chr, "%s\n", current.c_str());
         current = name;
       }
     const size_t n = pc->recs.size();
-#ifdef RFX_SINGLE_END
-    // no pairing: a record whose count reaches the threshold is written, `@QNAME:MH<hits>` (selected by the COUNT, as the
-    // reference's `>=` does: a threshold <= 0 writes every record)
     for (size_t i = 0; i < n; ++i) {
       const Rec& r = pc->recs[i];
+      if (!SINGLE) {
+        const uint32_t hit = (uint32_t)((pc->mask[i >> 6] >> (i & 63)) & 1);
+        if (walk.meet(r, hit)) pc->waited.push_back((uint32_t)i);
+        continue;
+      }
+      // no pairing: a record whose count reaches the threshold is written, `@QNAME:MH<hits>` (selected by the COUNT, as the
+      // reference's `>=` does: a threshold <= 0 writes every record)
       ++n_pairs;
       if ((int)pc->hits[i] < thresh) continue;
       ++n_found;
@@ -499,23 +592,11 @@ static int run(int argc, char** argv) {
     }
     n_rec += n;
     if (!o1.empty()) {
-      out1.write(o1.data(), (std::streamsize)o1.size());
-      o1.clear();
-    }
-#else
-    for (size_t i = 0; i < n; ++i) {
-      const Rec& r = pc->recs[i];
-      const uint32_t hit = (uint32_t)((pc->mask[i >> 6] >> (i & 63)) & 1);
-      if (walk.meet(r, hit)) pc->waited.push_back((uint32_t)i);
-    }
-    n_rec += n;
-    if (!o1.empty()) {
-      out1.write(o1.data(), (std::streamsize)o1.size());
-      out2.write(o2.data(), (std::streamsize)o2.size());
+      out.out1.write(o1.data(), (std::streamsize)o1.size());
+      out.out2.write(o2.data(), (std::streamsize)o2.size());
       o1.clear();
       o2.clear();
     }
-#endif
     live.push_back(pc);
     if (live.size() > LAG) {
       retire(live.front());
@@ -527,129 +608,218 @@ static int run(int argc, char** argv) {
     retire(live.front());
     live.pop_front();
   }
-  fprintf(chr, "%s\n", current.c_str());
-  fclose(chr);
   reader.join();
   for (auto& w : workers) w.join();
   trace("filter --sam: all pieces done");
   printf("\nSAM records %llu, pairs %llu, pulled %llu\n", n_rec, n_pairs, n_found);
-  out1.close();
-#ifndef RFX_SINGLE_END
-  out2.close();
-#endif
-  printf("\nDone running RUFUS.Filter.cpp\n");
-  if (!in_process) leave(0);  // (outputs closed: see the FASTQ route's end)
-  for (rfx_set* st : sets) rfx_set_free(st);
-  for (rfx_ctx* c : ctxs) rfx_close(c);
+  out.finish({current}, "", "", "", a.has_caller);
+  dv.close();
+  return 0;
+}
+}  // namespace samf
+
+// ---- RUFUS.Filter --bam CHRFILE HashList X.bam STUB K MinQ HashCountThreshold Threads [--bam-exclude N] ---------------
+// The subject straight from its BAM: what `samtools view -F N X.bam | RUFUS.Filter --sam CHRFILE HashList stdin ...` writes
+// (runRufus.sh:964-967; N defaults to 3328), byte for byte, without samtools and without SAM text.  The file is mapped and
+// handed to rfx_ingest.hpp's BamPairFilter: two passes, inflated and framed on the device both times; this thread reads
+// the file and writes the three outputs.  One device: RUFUS_GPUS naming more is refused, as for the bgzip'd mates.
+// RFX_BAM_ARENA (bytes per arena, >= 1 MiB) and RFX_INGEST_PIECE as in `jellyfish count --bam`.  Threads is accepted and
+// not used: no host thread parses anything.
+//
+// RUFUS.Filter.single --bam ...: the same arguments, checks and refusals; what `samtools view -F N X.bam
+// [REG] | PassThroughSamCheck.stranded.se CHRFILE | RUFUS.Filter.single HashList stdin STUB K MinQ Threshold 1` writes
+// (runRufus.sh:1031-1032), byte for byte: STUB.Mutations.fastq and CHRFILE.  rfx_ingest.hpp's BamSingleFilter: ONE pass --
+// nothing is paired by name -- and the file's text is written arena by arena, in stream order.
+namespace bamf {
+static const char* const USAGE =
+    "Call is --bam CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads [--bam-exclude N] [--region REG]\n";
+static bool parse(int argc, char** argv, FilterArgs& a) {
+  fputs(USAGE, stdout);
+  if (argc < 10) {
+    printf("ERROR: expected 9 arguments\n");
+    return false;
+  }
+  positional(a, argv + 2);
+  // --region REG: `samtools view -F N X.bam REG` in front of both passes (BamIngest::set_region)
+  for (int i = 10; i < argc; ++i) {
+    if (strcmp(argv[i], "--bam-exclude") == 0 && i + 1 < argc) a.exclude = (uint32_t)strtoul(argv[++i], nullptr, 0);
+    else if (strcmp(argv[i], "--region") == 0 && i + 1 < argc) {
+      if (a.region) die(std::string(TOOL) + ": --bam: --region given twice: one region per run");
+      a.region = argv[++i];
+    } else die(std::string(TOOL) + ": --bam: unknown argument " + argv[i]);
+  }
+  return true;
+}
+
+static int run(const FilterArgs& a) {
+  std::string text;
+  if (!read_hash_list(a.hashlist, text)) return 0;
+  const int fd = open_input(a.in1, 0);
+  if (fd < 0) return 0;
+  struct stat sb;
+  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode))
+    die(std::string(TOOL) + ": --bam needs a regular file, not a pipe: the BAM is mapped and read " + (SINGLE ? "once" : "twice"));
+  if (!is_bgzf(fd, true, (uint64_t)sb.st_size)) die(std::string(TOOL) + ": --bam: '" + a.in1 + "' is not BGZF");
+  const std::vector<uint64_t> keys = load_keys(text, a.k, TOOL);
+  const std::vector<int> gpus = gpu_list();
+  if (gpus.size() != 1)
+    die(std::string(TOOL) + ": --bam finds, scans and pulls the records on the device, which needs one device (RUFUS_GPUS names "
+        "more)");
+  Outputs out;
+  if (!out.open(a.chr, a.stub)) return 0;
+  Devices dv;
+  dv.open(gpus, keys, a.k, "filter --bam: device open, set built");
+  const Mapped bam = map_regular(fd, true);
+  if (!bam.ok) die(std::string(TOOL) + ": --bam: cannot map the input: " + strerror(errno));
+  const size_t arena = env_arena("RFX_BAM_ARENA"), piece = env_piece((size_t)8 << 20);
+  if constexpr (SINGLE) {
+    BamSingleFilter route(
+        dv.ctxs[0], dv.sets[0], a.min_q, a.thresh, a.exclude, [&](const char* p, size_t n) { out.out1.write(p, (std::streamsize)n); },
+        arena, piece);
+    if (a.region) route.set_region(a.region, a.in1);
+    route.run(bam.p, bam.n);
+    out.finish(route.chr_log(), "", "", route.counts());
+  } else {
+    BamPairFilter route(dv.ctxs[0], dv.sets[0], a.min_q, a.thresh, a.exclude, arena, piece);
+    if (a.region) route.set_region(a.region, a.in1);
+    route.run(bam.p, bam.n);
+    out.finish(route.chr_log(), route.mate1(), route.mate2(), route.counts());
+  }
+  dv.close();
   return 0;
 }
 
-#ifndef RFX_SINGLE_END
+// `RUFUS.Filter --packed CACHE CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads` with the
+// BAM-kind cache `jellyfish count --bam CHR --keep-packed CACHE X.bam` left (rfx_bam_cache.hpp): what `--bam` writes, byte
+// for byte, without a pass over the file -- the cache is scanned, and only the BGZF blocks that hold the hit names' records
+// are read and inflated (rfx_ingest.hpp BamCachePull).  Replaces the two inflates of runRufus.sh:964-967's generator that
+// `--bam` still does.  A cache that read_cache refuses, one made for another MinQ or other exclude flags than `--bam`'s
+// 3328, an X.bam that is not a regular BGZF file of the recorded size, or a fetched record that is not the record the cache
+// describes: one line on stderr and the two-pass `--bam` route in this process, with the same arguments.  One device.
+// Paired only; samf::run_packed sends it here.
+static int run_cached(const FilterArgs& a) {
+  const std::vector<int> gpus = gpu_list();
+  if (gpus.size() != 1)
+    die("rufus_amd RUFUS.Filter: --packed with a BAM's cache scans and fetches on the device, which needs one device (RUFUS_GPUS "
+        "names more)");
+  auto two_pass = [&]() {
+    fprintf(stderr, "rufus_amd RUFUS.Filter: %s is not a usable packed-read cache of %s for MinQ %d: reading the BAM twice\n", a.cache,
+            a.in1, a.min_q);
+    fputs(USAGE, stdout);
+    return run(a);  // (--packed takes neither --bam-exclude nor --region: a holds --bam's defaults)
+  };
+  // the cache, mapped and checked
+  rfxbamcache::Cache cache;
+  const Mapped cm = map_regular(a.cache, false);
+  if (!cm.ok || !rfxbamcache::read_cache(cm.p, cm.n, cache) || cache.h.min_q != a.min_q || cache.h.exclude_flags != 3328u) return two_pass();
+  struct stat bs;
+  if (stat(a.in1, &bs) != 0 || !S_ISREG(bs.st_mode) || (uint64_t)bs.st_size != cache.h.bam_bytes) return two_pass();
+  std::string text;
+  if (!read_hash_list(a.hashlist, text)) return 0;
+  const std::vector<uint64_t> keys = load_keys(text, a.k, TOOL);
+  const size_t arena = env_arena("RFX_BAM_ARENA"), piece = env_piece((size_t)8 << 20);
+  Devices dv;
+  dv.open(gpus, keys, a.k, "filter --packed: device open, set built");
+  bool same = true;
+  {
+    // (the fetch arena is a quarter of RFX_BAM_ARENA, the size of BamIngest's runs: it holds the few blocks of the selection,
+    // not a stretch of the file)
+    BamCachePull route(dv.ctxs[0], dv.sets[0], a.thresh, arena / 4, piece);
+    route.scan(cache);
+    trace("filter --packed: cache scanned");
+    if (route.hits()) {  // (no hit: the BAM is not opened)
+      const int fd = ::open(a.in1, O_RDONLY);
+      const Mapped bam = map_regular(fd, false);
+      same = bam.ok && (uint64_t)bam.n == cache.h.bam_bytes && is_bgzf(fd, true, (uint64_t)bam.n);
+      if (fd >= 0) ::close(fd);
+      same = same && route.pull(cache, bam.p, bam.n);
+      if (bam.p) munmap((void*)bam.p, bam.n);
+    }
+    if (same) {
+      Outputs out;
+      if (!out.open(a.chr, a.stub)) return 0;
+      out.finish(route.chr_log(), route.mate1(), route.mate2(), route.counts());
+    }
+  }
+  dv.close();
+  return same ? 0 : two_pass();  // (a fetched record was not the cache's: nothing has been written)
+}
+}  // namespace bamf
+
 // `RUFUS.Filter --packed CACHE CHRFILE PreBuiltMutHash SPOOL firstpassfile hashsize MinQ HashCountThreshold threads`
 // (rfx_packed_cache.hpp): the subject's records were packed once, by `jellyfish count --sam ..
 // --keep-packed CACHE`.  Here they are uploaded as they lie in CACHE and scanned; only the lines of the names with a hit
-// are gathered from SPOOL (the stream's bytes: `--spool`, or the SAM file itself) and go through the text route above.
+// are gathered from SPOOL (the stream's bytes: `--spool`, or the SAM file itself) and go through samf::run above.
 // A CACHE that begins with rfx_bam_cache.hpp's magic is `jellyfish count --bam .. --keep-packed`'s: SPOOL is then the BAM
-// file itself and the route is bamf::run_cached.
-static int run_packed(int argc, char** argv) {
+// file itself and the route is bamf::run_cached.  Paired only.
+namespace samf {
+static bool parse_packed(int argc, char** argv, FilterArgs& a) {
   printf("Call is --packed CACHE CHRFILE PreBuiltMutHash SPOOL firstpassfile hashsize MinQ HashCountThreshold threads\n");
   if (argc < 11) {
     printf("ERROR: expected 10 arguments\n");
-    return 0;
+    return false;
   }
-  for (int a = 11; a < argc; ++a)
-    if (strcmp(argv[a], "--region") == 0)
+  for (int i = 11; i < argc; ++i)
+    if (strcmp(argv[i], "--region") == 0)
       die("rufus_amd RUFUS.Filter: --region does not go with --packed: the cache does not record a region (use --bam)");
+  a.cache = argv[2];
+  positional(a, argv + 3);
+  return true;
+}
+
+static int run_packed(const FilterArgs& a) {
   {
     uint64_t magic = 0;
-    const int cfd = ::open(argv[2], O_RDONLY);
+    const int cfd = ::open(a.cache, O_RDONLY);
     const bool bam_kind = cfd >= 0 && ::pread(cfd, &magic, 8, 0) == 8 && magic == rfxbamcache::FILE_MAGIC;
     if (cfd >= 0) ::close(cfd);
-    if (bam_kind) return bamf::run_cached(argc, argv);
+    if (bam_kind) return bamf::run_cached(a);
   }
-  const char *cache_path = argv[2], *chr_path = argv[3], *hashlist = argv[4], *spool = argv[5];
-  const int k = atoi(argv[7]), min_q = atoi(argv[8]), thresh = atoi(argv[9]);
-  auto text_route = [&](const char* sam_path, const char* chr_to) {  // the ordinary --sam route on `sam_path`
-    std::vector<std::string> a{argv[0], "--sam", chr_to, hashlist, sam_path, argv[6], argv[7], argv[8], argv[9], argv[10]};
-    std::vector<char*> av;
-    for (std::string& x : a) av.push_back(&x[0]);
-    return run((int)av.size(), av.data());
+  const char *cache_path = a.cache, *spool = a.in1;
+  auto text_route = [&](const char* sam_path, const char* chr_to, bool has_caller) {  // the ordinary --sam route on `sam_path`
+    FilterArgs b = a;
+    b.in1 = sam_path;
+    b.chr = chr_to;
+    b.has_caller = has_caller;
+    fputs(USAGE, stdout);
+    return run(b);
   };
-  // the cache and the spool, mapped
-  struct Map {
-    const char* p = nullptr;
-    size_t n = 0;
-    bool open(const char* path) {
-      const int fd = ::open(path, O_RDONLY);
-      struct stat sb;
-      if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { if (fd >= 0) ::close(fd); return false; }
-      n = (size_t)sb.st_size;
-      if (n) {
-        void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) { ::close(fd); return false; }
-        p = (const char*)m;
-      }
-      ::close(fd);
-      return true;
-    }
-  } cm, sm;
   std::vector<rfxcache::ChunkView> chunks;
   int cached_q = 0;
-  if (!sm.open(spool)) {
+  const Mapped sm = map_regular(spool, false, true);
+  if (!sm.ok) {
     printf("Error, MutFile could not be opened");
     return 0;
   }
-  if (!cm.open(cache_path) || !rfxcache::read_chunks(cm.p, cm.n, sm.n, cached_q, chunks) || cached_q != min_q) {
+  const Mapped cm = map_regular(cache_path, false, true);
+  if (!cm.ok || !rfxcache::read_chunks(cm.p, cm.n, sm.n, cached_q, chunks) || cached_q != a.min_q) {
     // no cache, one its producer did not finish, a cache of another stream (length), or packed for another MinQ: the text decides
-    fprintf(stderr, "rufus_amd RUFUS.Filter: %s is not a usable packed-read cache for MinQ %d: scanning the text\n", cache_path, min_q);
-    return text_route(spool, chr_path);
+    fprintf(stderr, "rufus_amd RUFUS.Filter: %s is not a usable packed-read cache for MinQ %d: scanning the text\n", cache_path, a.min_q);
+    return text_route(spool, a.chr, false);
   }
   std::string text;
-  {
-    std::ifstream f(hashlist, std::ios::binary);
-    if (!f.is_open()) {
-      printf("Error, ParentHashFile could not be opened");
-      return 0;
-    }
-    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-  }
-  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, 0, nullptr, 0);
-  if (nk < 0) die("rufus_amd: cannot parse the hash list");
-  std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
+  if (!read_hash_list(a.hashlist, text)) return 0;
+  const std::vector<uint64_t> keys = load_keys(text, a.k, TOOL, false);  // (the text route below announces them)
   std::unordered_set<uint64_t> hit_names;
   uint64_t n_rec = 0, n_hit = 0, n_always = 0;
   {
-    const std::vector<int> gpus = gpu_list();
-    std::vector<rfx_ctx*> ctxs = open_ctxs(gpus);
-    std::vector<rfx_set*> sets;
-    for (rfx_ctx* c : ctxs) {
-      rfx_set* st = rfx_set_build(c, keys.data(), (uint64_t)nk, k);
-      if (!st) die(std::string("rufus_amd: ") + rfx_last_error());
-      sets.push_back(st);
-    }
-    trace("filter --packed: device open, set built");
+    Devices dv;
+    dv.open(gpu_list(), keys, a.k, "filter --packed: device open, set built");
     // chunk i goes to device i mod N; one thread per device uploads and scans (the arrays lie in the cache as the
     // upload wants them: no parsing, no packing)
     std::mutex mu;
     std::vector<std::thread> th;
-    for (size_t d = 0; d < ctxs.size(); ++d)
+    for (size_t d = 0; d < dv.size(); ++d)
       th.emplace_back([&, d] {
         std::vector<uint64_t> mask;
         std::vector<uint64_t> local;
         uint64_t rec = 0, hit = 0, always = 0;
-        for (size_t i = d; i < chunks.size(); i += ctxs.size()) {
+        for (size_t i = d; i < chunks.size(); i += dv.size()) {
           const rfxcache::ChunkView& v = chunks[i];
           const uint32_t n = v.h->n;
           if (!n) continue;
           mask.assign(((size_t)n + 63) / 64, 0);
-          rfx_reads* rd = rfx_reads_upload(ctxs[d], v.codes, nullptr, v.good, v.word_off, v.len, n);
-          if (!rd) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
-          uint64_t nh = 0;
-          const int rc = rfx_filter(sets[d], rd, thresh, 1, nullptr, mask.data(), &nh);
-          rfx_reads_free(rd);
-          if (rc) die(std::string("rufus_amd: filter failed: ") + rfx_last_error());
+          dv.scan_block(d, v.codes, v.good, v.word_off, v.len, n, a.thresh, nullptr, mask.data());
           for (uint32_t r = 0; r < n; ++r) {
             const bool al = v.flags[r] & rfxcache::REC_ALWAYS;
             if (al || ((mask[r >> 6] >> (r & 63)) & 1)) {
@@ -666,8 +836,7 @@ static int run_packed(int argc, char** argv) {
         n_always += always;
       });
     for (auto& t : th) t.join();
-    for (rfx_set* st : sets) rfx_set_free(st);
-    for (rfx_ctx* c : ctxs) rfx_close(c);
+    dv.close();
   }
   trace("filter --packed: cache scanned");
   // every line whose name (hash) has a hit, in stream order
@@ -684,7 +853,7 @@ static int run_packed(int argc, char** argv) {
         if (!tab || rfxsam::name_hash(ln, (size_t)(tab - ln)) != v.hash[r]) {
           fprintf(stderr, "rufus_amd RUFUS.Filter: %s does not describe %s (a line is not the record it was packed from): scanning the text\n",
                   cache_path, spool);
-          return text_route(spool, chr_path);
+          return text_route(spool, a.chr, false);
         }
         mini.append(ln, v.line_len[r]);
         mini.push_back('\n');
@@ -694,9 +863,9 @@ static int run_packed(int argc, char** argv) {
          (unsigned long long)n_rec, (unsigned long long)n_hit, (unsigned long long)n_always, (unsigned long long)n_lines);
   // the chromosome log of the WHOLE stream (src/PassThroughSamCheck.stranded.cpp: "notachr", then every run of RNAME)
   {
-    FILE* chr = fopen(chr_path, "w");
+    FILE* chr = fopen(a.chr, "w");
     if (!chr) {
-      printf("ERROR, Output file could not be opened -%s\n", chr_path);
+      printf("ERROR, Output file could not be opened -%s\n", a.chr);
       return 0;
     }
     std::string current = "notachr";
@@ -727,339 +896,104 @@ static int run_packed(int argc, char** argv) {
     at += (size_t)w;
   }
   ::close(tfd);
-  in_process = true;
-  const int rc = text_route(tmp.c_str(), "/dev/null");
+  const int rc = text_route(tmp.c_str(), "/dev/null", true);
   ::unlink(tmp.c_str());
   return rc;
 }
-#endif
 }  // namespace samf
 
-// ---- RUFUS.Filter --bam CHRFILE HashList X.bam STUB K MinQ HashCountThreshold Threads [--bam-exclude N] ---------------
-// The subject straight from its BAM: what `samtools view -F N X.bam | RUFUS.Filter --sam CHRFILE HashList stdin ...` writes
-// (runRufus.sh:964-967; N defaults to 3328), byte for byte, without samtools and without SAM text.  The file is mapped and
-// handed to rfx_ingest.hpp's BamPairFilter: two passes, inflated and framed on the device both times; this thread reads
-// the file and writes the three outputs.  One device: RUFUS_GPUS naming more is refused, as for the bgzip'd mates.
-// RFX_BAM_ARENA (bytes per arena, >= 1 MiB) and RFX_INGEST_PIECE as in `jellyfish count --bam`.  Threads is accepted and
-// not used: no host thread parses anything.
-//
-// RUFUS.Filter.single --bam ... (-DRFX_SINGLE_END): the same arguments, checks and refusals; what `samtools view -F N X.bam
-// [REG] | PassThroughSamCheck.stranded.se CHRFILE | RUFUS.Filter.single HashList stdin STUB K MinQ Threshold 1` writes
-// (runRufus.sh:1031-1032), byte for byte: STUB.Mutations.fastq and CHRFILE.  rfx_ingest.hpp's BamSingleFilter: ONE pass --
-// nothing is paired by name -- and the file's text is written arena by arena, in stream order.
-namespace bamf {
-static int run(int argc, char** argv) {
-  printf("Call is --bam CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads [--bam-exclude N] [--region REG]\n");
-  if (argc < 10) {
-    printf("ERROR: expected 9 arguments\n");
-    return 0;
-  }
-  const char *chr_path = argv[2], *hashlist = argv[3], *bam = argv[4];
-  const std::string stub = argv[5];
-  const int k = atoi(argv[6]), min_q = atoi(argv[7]), thresh = atoi(argv[8]);
-  uint32_t exclude = 3328;
-  const char* region = nullptr;  // --region REG: `samtools view -F N X.bam REG` in front of both passes (BamIngest::set_region)
-  for (int a = 10; a < argc; ++a) {
-    if (strcmp(argv[a], "--bam-exclude") == 0 && a + 1 < argc) exclude = (uint32_t)strtoul(argv[++a], nullptr, 0);
-    else if (strcmp(argv[a], "--region") == 0 && a + 1 < argc) {
-      if (region) die(std::string(TOOL) + ": --bam: --region given twice: one region per run");
-      region = argv[++a];
-    } else die(std::string(TOOL) + ": --bam: unknown argument " + argv[a]);
-  }
-  std::string text;
-  {
-    std::ifstream f(hashlist, std::ios::binary);
-    if (!f.is_open()) {
-      printf("Error, ParentHashFile could not be opened");
-      return 0;
-    }
-    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-  }
-  const int fd = ::open(bam, O_RDONLY);
-  if (fd < 0) {
-    printf("Error, MutFile could not be opened");
-    return 0;
-  }
-  struct stat sb;
-  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode))
-    die(std::string(TOOL) + ": --bam needs a regular file, not a pipe: the BAM is mapped and read " + (SINGLE ? "once" : "twice"));
-  if (!is_bgzf(fd, true, (uint64_t)sb.st_size)) die(std::string(TOOL) + ": --bam: '" + bam + "' is not BGZF");
-  if (k < 1 || k > 32) die(std::string(TOOL) + ": hash size must be 1..32");
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, nullptr, 0);
-  if (nk < 0) die("rufus_amd: cannot parse the hash list");
-  std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, SINGLE, keys.data(), keys.size());
-  printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
-  const std::vector<int> gpus = gpu_list();
-  if (gpus.size() != 1)
-    die(std::string(TOOL) + ": --bam finds, scans and pulls the records on the device, which needs one device (RUFUS_GPUS names "
-        "more)");
-  FILE* chr = fopen(chr_path, "w");
-#ifdef RFX_SINGLE_END
-  std::ofstream out1((stub + ".Mutations.fastq").c_str(), std::ios::binary);
-  if (!chr || !out1.is_open()) {
-#else
-  std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
-  std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
-  if (!chr || !out1.is_open() || !out2.is_open()) {
-#endif
-    printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
-    return 0;
-  }
-  rfx_ctx* ctx = open_ctxs(gpus)[0];
-  rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
-  if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
-  trace("filter --bam: device open, set built");
-  void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  if (m == MAP_FAILED) die(std::string(TOOL) + ": --bam: cannot map the input: " + strerror(errno));
-  (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
-  const size_t arena = env_arena("RFX_BAM_ARENA"), piece = env_piece((size_t)8 << 20);
-#ifdef RFX_SINGLE_END
-  {
-    BamSingleFilter route(
-        ctx, set, min_q, thresh, exclude, [&](const char* p, size_t n) { out1.write(p, (std::streamsize)n); }, arena, piece);
-    if (region) route.set_region(region, bam);
-    route.run((const char*)m, (size_t)sb.st_size);
-    for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
-    fclose(chr);
-    out1.close();
-    trace(route.counts().c_str());
-    printf("\nDone running RUFUS.Filter.cpp\n");
-    leave(0);  // (outputs closed: see the text route's end)
-  }
-#else
-  {
-    BamPairFilter route(ctx, set, min_q, thresh, exclude, arena, piece);
-    if (region) route.set_region(region, bam);
-    route.run((const char*)m, (size_t)sb.st_size);
-    for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
-    fclose(chr);
-    out1.write(route.mate1().data(), (std::streamsize)route.mate1().size());
-    out2.write(route.mate2().data(), (std::streamsize)route.mate2().size());
-    out1.close();
-    out2.close();
-    trace(route.counts().c_str());
-    printf("\nDone running RUFUS.Filter.cpp\n");
-    leave(0);  // (outputs closed: see the text route's end)
-  }
-#endif
-  rfx_set_free(set);
-  rfx_close(ctx);
-  return 0;
-}
-
-#ifndef RFX_SINGLE_END
-// `RUFUS.Filter --packed CACHE CHRFILE PreBuiltMutHash X.bam firstpassfile hashsize MinQ HashCountThreshold threads` with the
-// BAM-kind cache `jellyfish count --bam CHR --keep-packed CACHE X.bam` left (rfx_bam_cache.hpp): what `--bam` writes, byte
-// for byte, without a pass over the file -- the cache is scanned, and only the BGZF blocks that hold the hit names' records
-// are read and inflated (rfx_ingest.hpp BamCachePull).  Replaces the two inflates of runRufus.sh:964-967's generator that
-// `--bam` still does.  A cache that read_cache refuses, one made for another MinQ or other exclude flags than `--bam`'s
-// 3328, an X.bam that is not a regular BGZF file of the recorded size, or a fetched record that is not the record the cache
-// describes: one line on stderr and the two-pass `--bam` route in this process, with the same arguments.  One device.
-static int run_cached(int argc, char** argv) {
-  const char *cache_path = argv[2], *chr_path = argv[3], *hashlist = argv[4], *bam = argv[5];
-  const std::string stub = argv[6];
-  const int k = atoi(argv[7]), min_q = atoi(argv[8]), thresh = atoi(argv[9]);
-  const std::vector<int> gpus = gpu_list();
-  if (gpus.size() != 1)
-    die("rufus_amd RUFUS.Filter: --packed with a BAM's cache scans and fetches on the device, which needs one device (RUFUS_GPUS "
-        "names more)");
-  auto two_pass = [&]() {
-    fprintf(stderr, "rufus_amd RUFUS.Filter: %s is not a usable packed-read cache of %s for MinQ %d: reading the BAM twice\n", cache_path,
-            bam, min_q);
-    std::vector<std::string> a{argv[0], "--bam", chr_path, hashlist, bam, argv[6], argv[7], argv[8], argv[9], argv[10]};
-    std::vector<char*> av;
-    for (std::string& x : a) av.push_back(&x[0]);
-    return run((int)av.size(), av.data());
-  };
-  // the cache, mapped and checked
-  rfxbamcache::Cache cache;
-  {
-    const int fd = ::open(cache_path, O_RDONLY);
-    struct stat sb;
-    void* m = MAP_FAILED;
-    if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (fd >= 0) ::close(fd);
-    if (m == MAP_FAILED || !rfxbamcache::read_cache((const char*)m, (size_t)sb.st_size, cache) || cache.h.min_q != min_q ||
-        cache.h.exclude_flags != 3328u)
-      return two_pass();
-  }
-  struct stat bs;
-  if (stat(bam, &bs) != 0 || !S_ISREG(bs.st_mode) || (uint64_t)bs.st_size != cache.h.bam_bytes) return two_pass();
-  std::string text;
-  {
-    std::ifstream f(hashlist, std::ios::binary);
-    if (!f.is_open()) {
-      printf("Error, ParentHashFile could not be opened");
-      return 0;
-    }
-    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-  }
-  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, 0, nullptr, 0);
-  if (nk < 0) die("rufus_amd: cannot parse the hash list");
-  std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, 0, keys.data(), keys.size());
-  printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
-  const size_t arena = env_arena("RFX_BAM_ARENA"), piece = env_piece((size_t)8 << 20);
-  rfx_ctx* ctx = open_ctxs(gpus)[0];
-  rfx_set* set = rfx_set_build(ctx, keys.data(), (uint64_t)nk, k);
-  if (!set) die(std::string("rufus_amd: ") + rfx_last_error());
-  trace("filter --packed: device open, set built");
-  bool same = true;
-  {
-    // (the fetch arena is a quarter of RFX_BAM_ARENA, the size of BamIngest's runs: it holds the few blocks of the selection,
-    // not a stretch of the file)
-    BamCachePull route(ctx, set, thresh, arena / 4, piece);
-    route.scan(cache);
-    trace("filter --packed: cache scanned");
-    if (route.hits()) {  // (no hit: the BAM is not opened)
-      const int fd = ::open(bam, O_RDONLY);
-      struct stat sb;
-      void* m = MAP_FAILED;
-      same = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && (uint64_t)sb.st_size == cache.h.bam_bytes &&
-             is_bgzf(fd, true, (uint64_t)sb.st_size);
-      if (same) m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (fd >= 0) ::close(fd);
-      same = same && m != MAP_FAILED && route.pull(cache, (const char*)m, (size_t)sb.st_size);
-      if (m != MAP_FAILED) munmap(m, (size_t)sb.st_size);
-    }
-    if (same) {
-      FILE* chr = fopen(chr_path, "w");
-      std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
-      std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
-      if (!chr || !out1.is_open() || !out2.is_open()) {
-        printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
-        return 0;
-      }
-      for (const std::string& name : route.chr_log()) fprintf(chr, "%s\n", name.c_str());
-      fclose(chr);
-      out1.write(route.mate1().data(), (std::streamsize)route.mate1().size());
-      out2.write(route.mate2().data(), (std::streamsize)route.mate2().size());
-      out1.close();
-      out2.close();
-      trace(route.counts().c_str());
-      printf("\nDone running RUFUS.Filter.cpp\n");
-      leave(0);  // (outputs closed: see the text route's end)
-    }
-  }
-  rfx_set_free(set);
-  rfx_close(ctx);
-  return same ? 0 : two_pass();  // (a fetched record was not the cache's: nothing has been written)
-}
-#endif
-}  // namespace bamf
-
-int main(int argc, char** argv) {
-  if (argc > 1 && strcmp(argv[1], "--sam") == 0) return samf::run(argc, argv);
-  if (argc > 1 && strcmp(argv[1], "--bam") == 0) return bamf::run(argc, argv);
-#ifndef RFX_SINGLE_END
-  if (argc > 1 && strcmp(argv[1], "--packed") == 0) return samf::run_packed(argc, argv);
-#else
-  if (argc > 1 && strcmp(argv[1], "--packed") == 0)
-    die("rufus_amd RUFUS.Filter.single: --packed is for paired subjects only (RUFUS.Filter --packed): use --bam or --sam");
-#endif
-#ifdef RFX_SINGLE_END
-  const int need = 8;
-  printf("Call is PreBuiltMutHash Mutant.fq|stdin firstpassfile hashsize MinQ HashCountThreshold threads\n");
-#else
-  const int need = 9;
-  printf("Call is PreBuiltMutHash Mutant.Mate1.fq Mutant.Mate2.fq firstpassfile hashsize MinQ HashCountThreshold threads \n");
-#endif
+// ---- RUFUS.Filter HashList Mate1.fq Mate2.fq STUB ... / RUFUS.Filter.single HashList FQ|stdin STUB ...: FASTQ text --------
+// Pipeline (the device scans ~1000x faster than one core parses, so the host side is what counts):
+//   one reader per mate stream cuts it into pieces of PIECE_RECS records (4 lines each, counted blindly like the
+//   reference's getline x 4); the two pipes are always being drained, so a writer in lock step
+//   (PassThroughSamCheck.stranded, runRufus.sh:966) never blocks on the one while we wait on the other;
+//   workers take piece i of both streams, find the lines, pack bases + quality mask of both mates
+//   (rfx_pack_spans), run the scan (k_filter; device calls are serialised, they take microseconds) and format
+//   the pulled records;
+//   the main thread writes the formatted pieces in input order.
+// The device is opened (0.1 - 0.25 s of runtime start-up) and the set built beside the readers and the workers' first
+// pieces: a worker needs them when its first piece is packed (RFX_SYNC_OPEN=1: before anything else, as it used to be).
+// A reader or a worker that has to refuse the input does so through refuse(): exit() while the opener thread is inside
+// the runtime's start can end in the C library's abort instead of status 1, so the opener is waited for first.
+namespace textf {
+static bool parse(int argc, char** argv, FilterArgs& a) {
+  const int need = SINGLE ? 8 : 9;
+  fputs(SINGLE ? "Call is PreBuiltMutHash Mutant.fq|stdin firstpassfile hashsize MinQ HashCountThreshold threads\n"
+               : "Call is PreBuiltMutHash Mutant.Mate1.fq Mutant.Mate2.fq firstpassfile hashsize MinQ HashCountThreshold threads \n",
+        stdout);
   if (argc < need) {
     printf("ERROR: expected %d arguments\n", need - 1);
-    return 0;  // the reference tools report on stdout and exit 0; the shell checks for empty outputs
+    return false;
   }
-  int a = 1;
-  const char* hashlist = argv[a++];
-  const char* m1 = argv[a++];
-#ifndef RFX_SINGLE_END
-  const char* m2 = argv[a++];
-#endif
-  const std::string stub = argv[a++];
-  const int k = atoi(argv[a++]), min_q = atoi(argv[a++]), thresh = atoi(argv[a++]);
+  int i = 1;
+  a.hashlist = argv[i++];
+  a.in1 = argv[i++];
+  if (!SINGLE) a.in2 = argv[i++];
+  a.stub = argv[i++];
+  a.k = atoi(argv[i++]);
+  a.min_q = atoi(argv[i++]);
+  a.thresh = atoi(argv[i++]);
+  a.threads = atoi(argv[i]);
+  return true;
+}
 
+static const size_t PIECE_RECS = 1u << 16;
+// A piece: PIECE_RECS records (the last one of a stream: fewer) = 4 * recs lines of text, each ending in '\n'.
+// Its bytes are the piece's own buffer (filled by read()) or lie in the mapping of a regular input file.
+struct Piece {
+  const char* data = nullptr;
+  size_t size = 0, recs = 0;
+  std::unique_ptr<char[]> own;
+  size_t cap = 0;
+};
+struct Stream {
+  int fd = -1;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<Piece*> q;
+  bool done = false;
+  bool abort = false;         // mate 1 ended: nobody takes this stream's pieces any more
+  const char* map = nullptr;  // regular file: mapped
+  size_t map_size = 0;
+};
+struct Result { std::string out1, out2; unsigned long long recs = 0, found = 0; bool ready = false; };
+
+static int run(const FilterArgs& a) {
+  const int min_q = a.min_q, thresh = a.thresh;
+  const int n_streams = SINGLE ? 1 : 2;
   std::string text;
-  {
-    std::ifstream f(hashlist, std::ios::binary);
-    if (!f.is_open()) {
-      printf("Error, ParentHashFile could not be opened");
-      return 0;
-    }
-    text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-  }
-  const int fd1 = strcmp(m1, "stdin") == 0 || strcmp(m1, "/dev/stdin") == 0 ? 0 : ::open(m1, O_RDONLY);
-  if (fd1 < 0) {
-    printf("Error, MutFile could not be opened");
-    return 0;
-  }
-#ifdef RFX_SINGLE_END
-  const int single = 1;
-  std::ofstream out1((stub + ".Mutations.fastq").c_str(), std::ios::binary);
-#else
-  const int single = 0;
-  const int fd2 = ::open(m2, O_RDONLY);
-  if (fd2 < 0) {
-    printf("Error, MutFile could not be opened");
-    return 0;
-  }
-  std::ofstream out1((stub + ".Mutations.Mate1.fastq").c_str(), std::ios::binary);
-  std::ofstream out2((stub + ".Mutations.Mate2.fastq").c_str(), std::ios::binary);
-  if (!out2.is_open()) {
-    printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
-    return 0;
-  }
-#endif
-  if (!out1.is_open()) {
-    printf("ERROR, Output file could not be opened -%s\n", stub.c_str());
-    return 0;
-  }
-  if (k < 1 || k > 32) die("rufus_amd RUFUS.Filter: hash size must be 1..32");
-
-  const long nk = rfx_hashlist_keys(text.data(), text.size(), k, single, nullptr, 0);
-  if (nk < 0) die("rufus_amd: cannot parse the hash list");
-  std::vector<uint64_t> keys((size_t)nk + 1);
-  rfx_hashlist_keys(text.data(), text.size(), k, single, keys.data(), keys.size());
-  printf("\nDone Hash Files\n\t Mutations Hash size is %ld\n", nk);
-
+  if (!read_hash_list(a.hashlist, text)) return 0;
+  Stream st[2];
+  if ((st[0].fd = open_input(a.in1, 2)) < 0) return 0;
+  if (!SINGLE && (st[1].fd = open_input(a.in2, 0)) < 0) return 0;
+  Outputs out;
+  if (!out.open(nullptr, a.stub)) return 0;
+  const std::vector<uint64_t> keys = load_keys(text, a.k, "rufus_amd RUFUS.Filter");
   trace("filter: hash list parsed");
-#ifndef RFX_SINGLE_END
-  {  // two bgzip'd mate files: the device inflates them (namespace bgzff); one of the two is a mistake
-    struct stat sb[2];
-    const int fds[2] = {fd1, fd2};
+  if constexpr (!SINGLE) {  // two bgzip'd mate files: the device inflates them (namespace bgzff); one of the two is a mistake
     bool z[2];
     for (int m = 0; m < 2; ++m) {
-      const bool regular = fds[m] != 0 && fstat(fds[m], &sb[m]) == 0 && S_ISREG(sb[m].st_mode);
-      z[m] = is_bgzf(fds[m], regular, regular ? (uint64_t)sb[m].st_size : 0);
+      struct stat sb;
+      const bool regular = st[m].fd != 0 && fstat(st[m].fd, &sb) == 0 && S_ISREG(sb.st_mode);
+      z[m] = is_bgzf(st[m].fd, regular, regular ? (uint64_t)sb.st_size : 0);
     }
     if (z[0] != z[1])
-      die(std::string("rufus_amd RUFUS.Filter: ") + (z[0] ? m1 : m2) + " is BGZF and " + (z[0] ? m2 : m1) +
+      die(std::string("rufus_amd RUFUS.Filter: ") + (z[0] ? a.in1 : a.in2) + " is BGZF and " + (z[0] ? a.in2 : a.in1) +
           " is not: give both mates compressed or both as text");
-    if (z[0]) return bgzff::run(fd1, (size_t)sb[0].st_size, fd2, (size_t)sb[1].st_size, keys, nk, k, min_q, thresh, out1, out2);
+    if (z[0]) return bgzff::run(a, st[0].fd, st[1].fd, keys, out);
   }
-#endif
   // RUFUS_GPUS: the pieces are dealt to the devices by worker thread (the filter shards by read block)
   const std::vector<int> gpus = gpu_list();
-  const int n_gpu = (int)gpus.size();
-  // The device is opened (0.1 - 0.25 s of runtime start-up) and the set built beside the readers and the workers' first
-  // pieces: a worker needs them when its first piece is packed (RFX_SYNC_OPEN=1: before anything else, as it used to be).
-  std::vector<rfx_ctx*> ctxs;
-  std::vector<rfx_set*> sets;
+  const size_t n_gpu = gpus.size();
+  Devices dv;
   std::mutex open_mu;
   std::condition_variable open_cv;
   bool dev_ready = false;
   std::thread opener([&] {
-    std::vector<rfx_ctx*> cs = open_ctxs(gpus);
-    std::vector<rfx_set*> ss;
-    for (rfx_ctx* c : cs) {
-      rfx_set* st = rfx_set_build(c, keys.data(), (uint64_t)nk, k);
-      if (!st) die(std::string("rufus_amd: ") + rfx_last_error());
-      ss.push_back(st);
-    }
-    trace("filter: device open, set built");
+    Devices opened;
+    opened.open(gpus, keys, a.k, "filter: device open, set built");
     std::lock_guard<std::mutex> g(open_mu);
-    ctxs = std::move(cs);
-    sets = std::move(ss);
+    dv = std::move(opened);
     dev_ready = true;
     open_cv.notify_all();
   });
@@ -1067,55 +1001,19 @@ int main(int argc, char** argv) {
     std::unique_lock<std::mutex> g(open_mu);
     open_cv.wait(g, [&] { return dev_ready; });
   };
+  auto refuse = [&](const std::string& msg) {  // die() from a reader or a worker: not while the opener is in the runtime's start
+    wait_device();
+    die(msg);
+  };
   if (getenv("RFX_SYNC_OPEN")) wait_device();
 
-  // Pipeline (the device scans ~1000x faster than one core parses, so the host side is what counts):
-  //   one reader per mate stream cuts it into pieces of PIECE_RECS records (4 lines each, counted blindly like the
-  //   reference's getline x 4); the two pipes are always being drained, so a writer in lock step
-  //   (PassThroughSamCheck.stranded, runRufus.sh:966) never blocks on the one while we wait on the other;
-  //   workers take piece i of both streams, find the lines, pack bases + quality mask of both mates
-  //   (rfx_pack_spans), run the scan (k_filter; device calls are serialised, they take microseconds) and format
-  //   the pulled records;
-  //   the main thread writes the formatted pieces in input order.
-  const size_t PIECE_RECS = 1u << 16;
-  // A piece: PIECE_RECS records (the last one of a stream: fewer) = 4 * recs lines of text, each ending in '\n'.
-  // Its bytes are the piece's own buffer (filled by read()) or lie in the mapping of a regular input file.
-  struct Piece {
-    const char* data = nullptr;
-    size_t size = 0, recs = 0;
-    std::unique_ptr<char[]> own;
-    size_t cap = 0;
-  };
-  struct Stream {
-    int fd = -1;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Piece*> q;
-    bool done = false;
-    bool abort = false;         // mate 1 ended: nobody takes this stream's pieces any more
-    const char* map = nullptr;  // regular file: mapped
-    size_t map_size = 0;
-  };
-  const int n_streams = single ? 1 : 2;
-  Stream st[2];
-  st[0].fd = fd1;
-#ifndef RFX_SINGLE_END
-  st[1].fd = fd2;
-#endif
   for (int i = 0; i < n_streams; ++i) {
-    struct stat sb;
-    if (fstat(st[i].fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0 && !getenv("RFX_FILTER_NO_MMAP")) {
-      void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, st[i].fd, 0);
-      if (m != MAP_FAILED) {
-        (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
-        st[i].map = (const char*)m;
-        st[i].map_size = (size_t)sb.st_size;
-      }
-    } else {
+    const Mapped m = getenv("RFX_FILTER_NO_MMAP") ? Mapped() : map_regular(st[i].fd, true);
+    st[i].map = m.p;
+    st[i].map_size = m.n;
 #ifdef F_SETPIPE_SZ
-      (void)fcntl(st[i].fd, F_SETPIPE_SZ, 1 << 20);  // a pipe: fewer, larger reads (ignored on anything else)
+    if (!m.ok) (void)fcntl(st[i].fd, F_SETPIPE_SZ, 1 << 20);  // a pipe: fewer, larger reads (ignored on anything else)
 #endif
-    }
   }
   const skip_lines_fn skip_lines = pick_skip_lines();
   const index_lines_fn index_lines = pick_index_lines();
@@ -1195,7 +1093,7 @@ int main(int argc, char** argv) {
       if (cur->cap - cur->size < RD) grow(cur, cur->cap + cur->cap / 2 + RD);
       const ssize_t n = ::read(S.fd, cur->own.get() + cur->size, RD);
       if (n < 0 && errno == EINTR) continue;
-      if (n < 0) die(std::string("read error on input: ") + strerror(errno));
+      if (n < 0) refuse(std::string("read error on input: ") + strerror(errno));
       if (n == 0) break;
       cur->size += (size_t)n;
       while (scanned < cur->size) {
@@ -1220,16 +1118,14 @@ int main(int argc, char** argv) {
   std::thread readers[2];
   for (int i = 0; i < n_streams; ++i) readers[i] = std::thread(reader, std::ref(st[i]));
 
-  struct Result { std::string out1, out2; unsigned long long recs = 0, found = 0; bool ready = false; };
   std::mutex res_mu, take_mu;
-  std::vector<std::mutex> dev_mu((size_t)n_gpu);
   std::condition_variable res_cv;
   std::map<uint64_t, Result> results;
   uint64_t next_seq = 0;
   bool input_done = false;
-  auto take = [&](Piece*& a, Piece*& b, uint64_t& seq) -> bool {  // piece `seq` of both streams, in order
+  auto take = [&](Piece*& p1, Piece*& p2, uint64_t& seq) -> bool {  // piece `seq` of both streams, in order
     std::lock_guard<std::mutex> tg(take_mu);
-    a = b = nullptr;
+    p1 = p2 = nullptr;
     {
       std::unique_lock<std::mutex> g(st[0].mu);
       st[0].cv.wait(g, [&] { return !st[0].q.empty() || st[0].done; });
@@ -1246,7 +1142,7 @@ int main(int argc, char** argv) {
         }
         return false;
       }
-      a = st[0].q.front();
+      p1 = st[0].q.front();
       st[0].q.pop_front();
       st[0].cv.notify_all();
     }
@@ -1254,46 +1150,23 @@ int main(int argc, char** argv) {
       std::unique_lock<std::mutex> g(st[1].mu);
       st[1].cv.wait(g, [&] { return !st[1].q.empty() || st[1].done; });
       if (!st[1].q.empty()) {
-        b = st[1].q.front();
+        p2 = st[1].q.front();
         st[1].q.pop_front();
         st[1].cv.notify_all();
       } else {
-        b = new Piece();  // mate 2 ran out: its records read as empty (lock step: one per record of mate 1)
+        p2 = new Piece();  // mate 2 ran out: its records read as empty (lock step: one per record of mate 1)
       }
     }
     seq = next_seq++;
     return true;
   };
   auto worker = [&](unsigned me) {
-    const size_t dev = (size_t)me % (size_t)n_gpu;
-    rfx_ctx* ctx = nullptr;  // (known once the opener is done: wait_device() before the first upload)
-    rfx_set* set = nullptr;
+    const size_t dev = (size_t)me % n_gpu;
+    bool up = false;  // the opener is done: known by the first upload at the latest (wait_device() before it)
     std::vector<uint64_t> ls[2], ss[2], qs[2], mask;  // line starts, sequence / quality starts
     std::vector<uint32_t> sl[2], hits;
     std::vector<char> fix;  // private copies of quality strings that are shorter than their read
-    // packed reads go up from page-locked memory (a pageable source costs a staging copy inside the runtime, under
-    // the device lock)
-    // (while the device is still being opened the buffers are plain memory, page-locked before their first upload)
-    struct Pinned {
-      void* p = nullptr;
-      size_t cap = 0;
-      bool locked = false;
-      void* need(size_t bytes, bool device_up = true) {
-        if (bytes > cap) {
-          if (p) rfx_host_free(p);
-          cap = bytes + bytes / 4;
-          p = device_up ? rfx_host_alloc(cap) : rfx_host_alloc_lazy(cap);
-          locked = device_up;
-          if (!p) die("rufus_amd: cannot allocate pinned staging memory");
-        }
-        return p;
-      }
-      void lock() {
-        if (p && !locked) (void)rfx_host_pin(p);  // (refused: the upload stages the pageable buffer itself)
-        locked = true;
-      }
-      ~Pinned() { if (p) rfx_host_free(p); }
-    } pin_codes, pin_good, pin_woff, pin_lens;
+    Staging stage;
     for (;;) {
       Piece *pc[2];
       uint64_t seq;
@@ -1320,7 +1193,7 @@ int main(int argc, char** argv) {
           sl[m][i] = len_of(4 * i + 1);
           qs[m][i] = ls[m][4 * i + 3];
           if (m == 0 && sl[m][i] == 0)
-            die("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
+            refuse("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
         }
       }
       // pack: reads of mate 1, then of mate 2, into one block
@@ -1328,15 +1201,12 @@ int main(int argc, char** argv) {
       uint64_t words = 0;
       for (int m = 0; m < n_streams; ++m)
         for (size_t i = 0; i < n; ++i) words += (sl[m][i] + 31) / 32;
-      const bool up = ctx != nullptr;
-      uint64_t* codes = (uint64_t*)pin_codes.need((words + 1) * 8, up);
-      uint32_t* good = (uint32_t*)pin_good.need((words + 1) * 4, up);
-      uint32_t* woff = (uint32_t*)pin_woff.need((nr + 1) * 4, up);
-      uint32_t* lens = (uint32_t*)pin_lens.need((nr + 1) * 4, up);
+      if (!stage.need(words, nr, up)) refuse(NO_STAGING);
       uint32_t w0 = 0;
       for (int m = 0; m < n_streams; ++m) {
         const char* t = pc[m]->data;
-        woff[m * n] = w0;
+        uint32_t *woff = stage.woff + m * n, *lens = stage.lens + m * n;
+        woff[0] = w0;
         // Runs of ordinary reads are packed in place.  A quality line shorter than its read would make the packer
         // read the next line's bytes: such a read is packed on its own from a private copy of its sequence and
         // quality string, the latter padded with '\0' (= bad, what the reference's missing chars are).
@@ -1350,44 +1220,32 @@ int main(int argc, char** argv) {
           while (run < n && qlen(run) >= sl[m][run]) ++run;
           if (run > at &&
               rfx_pack_spans(t, ss[m].data() + at, sl[m].data() + at, qs[m].data() + at, (uint32_t)(run - at), min_q,
-                             RFX_PACK_FILTER, codes, nullptr, good, woff + m * n + at, lens + m * n + at) != RFX_OK)
-            die("rufus_amd: pack failed");
+                             RFX_PACK_FILTER, stage.codes, nullptr, stage.good, woff + at, lens + at) != RFX_OK)
+            refuse("rufus_amd: pack failed");
           if (run < n) {
             const uint32_t L = sl[m][run], ql = qlen(run);
             fix.assign((size_t)2 * L, '\0');
             memcpy(fix.data(), t + ss[m][run], L);
             memcpy(fix.data() + L, t + qs[m][run], ql);
             const uint64_t s0 = 0, q0 = L;
-            if (rfx_pack_spans(fix.data(), &s0, &L, &q0, 1, min_q, RFX_PACK_FILTER, codes, nullptr, good,
-                               woff + m * n + run, lens + m * n + run) != RFX_OK)
-              die("rufus_amd: pack failed");
+            if (rfx_pack_spans(fix.data(), &s0, &L, &q0, 1, min_q, RFX_PACK_FILTER, stage.codes, nullptr, stage.good, woff + run,
+                               lens + run) != RFX_OK)
+              refuse("rufus_amd: pack failed");
             ++run;
           }
           at = run;
         }
-        w0 = woff[(m + 1) * n];
+        w0 = woff[n];
       }
       mask.assign((nr + 63) / 64, 0);
-      if (single) hits.assign(nr, 0);
-      if (!ctx) {
+      if (SINGLE) hits.assign(nr, 0);
+      if (!up) {
         wait_device();
-        ctx = ctxs[dev];
-        set = sets[dev];
-        pin_codes.lock();
-        pin_good.lock();
-        pin_woff.lock();
-        pin_lens.lock();
+        up = true;
+        stage.lock();
       }
-      {
-        std::lock_guard<std::mutex> g(dev_mu[dev]);
-        rfx_reads* rd = rfx_reads_upload(ctx, codes, nullptr, good, woff, lens, (uint32_t)nr);
-        if (!rd) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
-        uint64_t nh = 0;
-        // paired tool: `i < length()-1`, the last base is never examined (src/RUFUS.Filter.cpp:203)
-        const int rc = rfx_filter(set, rd, thresh, single ? 0 : 1, single ? hits.data() : nullptr, mask.data(), &nh);
-        rfx_reads_free(rd);
-        if (rc) die(std::string("rufus_amd: filter failed: ") + rfx_last_error());
-      }
+      dv.scan_block(dev, stage.codes, stage.good, stage.woff, stage.lens, (uint32_t)nr, thresh, SINGLE ? hits.data() : nullptr,
+                    mask.data());
       Result res;
       res.recs = n;
       auto bit = [&](size_t r) { return (mask[r >> 6] >> (r & 63)) & 1; };
@@ -1402,7 +1260,7 @@ int main(int argc, char** argv) {
         }
       };
       for (size_t i = 0; i < n; ++i) {
-        if (single) {
+        if (SINGLE) {
           if (bit(i)) {
             const std::string suffix = ":MH" + std::to_string(hits[i]);
             put(res.out1, 0, i, suffix.c_str());
@@ -1424,7 +1282,7 @@ int main(int argc, char** argv) {
       res_cv.notify_all();
     }
   };
-  unsigned nthreads = (unsigned)std::max(1, atoi(argv[a]));
+  unsigned nthreads = (unsigned)std::max(1, a.threads);
   nthreads = std::min(nthreads, rfx_host_cpus());
   if (const char* ev = getenv("RFX_HOST_THREADS")) nthreads = (unsigned)std::max(1, atoi(ev));
   nthreads = std::max(nthreads, (unsigned)n_gpu);
@@ -1440,28 +1298,33 @@ int main(int argc, char** argv) {
       res = std::move(results[want]);
       results.erase(want);
     }
-    out1.write(res.out1.data(), (std::streamsize)res.out1.size());
-#ifndef RFX_SINGLE_END
-    out2.write(res.out2.data(), (std::streamsize)res.out2.size());
-#endif
+    out.out1.write(res.out1.data(), (std::streamsize)res.out1.size());
+    out.out2.write(res.out2.data(), (std::streamsize)res.out2.size());
     total += res.recs;
     found += res.found;
     printf("Read in %llu lines: Found %llu \r", total * 4, found);
   }
   trace("filter: all pieces written");
-  out1.close();
-#ifndef RFX_SINGLE_END
-  out2.close();
-#endif
-  printf("\nDone running RUFUS.Filter.cpp\n");
   opener.join();
-  // Everything the caller will read is on disk: the process leaves here (rfx_cli.hpp leave(): unmapping 20 GB of input,
-  // unpinning the staging blocks and the runtime's own teardown took 0.5 s of a 1.5 s run).  RFX_CLEAN_EXIT=1: the orderly way.
-  leave(0);
+  out.finish({}, "", "", "");
   for (auto& w : workers) w.join();
   for (int i = 0; i < n_streams; ++i) readers[i].join();
-  for (rfx_set* st : sets) rfx_set_free(st);
-  for (rfx_ctx* c : ctxs) rfx_close(c);
+  dv.close();
   trace("filter: closed");
   return 0;
+}
+}  // namespace textf
+
+int main(int argc, char** argv) {
+  const char* flag = argc > 1 ? argv[1] : "";
+  FilterArgs a;
+  if (strcmp(flag, "--sam") == 0) return samf::parse(argc, argv, a) ? samf::run(a) : 0;
+  if (strcmp(flag, "--bam") == 0) return bamf::parse(argc, argv, a) ? bamf::run(a) : 0;
+  if (strcmp(flag, "--packed") == 0) {
+    if constexpr (SINGLE)
+      die("rufus_amd RUFUS.Filter.single: --packed is for paired subjects only (RUFUS.Filter --packed): use --bam or --sam");
+    else
+      return samf::parse_packed(argc, argv, a) ? samf::run_packed(a) : 0;
+  }
+  return textf::parse(argc, argv, a) ? textf::run(a) : 0;
 }
