@@ -11,41 +11,20 @@
 // the HIP kernels behind include/rufus_hip.h.  No CPU fallback.
 #include <getopt.h>
 
-#include <atomic>
-#include <chrono>
-#include <mutex>
-#include <limits>
-#include <memory>
-
-#include <functional>
-
 #include "rfx_ingest.hpp"
 
 using namespace rfxcli;
 
-static double secs_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+static double now() {  // seconds on the steady clock
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // ---------------------------------------------------------------------------------------------
-// Does the BGZF file begin with a BAM header?  (rfx_bam_header refuses BGZF whose first bytes are not BAM's magic; a header
-// that is not whole in the first 64 KiB is still BAM.)  What turns `jellyfish count X.bam` without --bam into a message
-// that says --bam instead of the FASTQ one.
-static bool is_bam(int fd, uint64_t size) {
-  if (!rfx_bam_header) return false;
-  const std::vector<uint8_t> head = read_head(fd, size, 1u << 16);
-  int complete = 0;
-  int32_t n_ref = 0;
-  uint64_t names_bytes = 0, first_block = 0;
-  uint32_t skip = 0;
-  return rfx_bam_header(head.data(), head.size(), &complete, &n_ref, nullptr, 0, &names_bytes, &first_block, &skip) == RFX_OK;
-}
-
-static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
-  const auto t_start = std::chrono::steady_clock::now();
-  int k = 0, threads = 1, out_counter_len = 4;
-  uint64_t size = 0, lower = 0, upper = std::numeric_limits<uint64_t>::max();
-  bool canonical = false, size_given = false;
+// `jellyfish count`: count_main, at the end of this section, reads as its steps.
+struct CountArgs {
+  int k = 0, threads = 1, out_counter_len = 4, lsize = 1;  // lsize: -s SIZE as a power of two, rounded up
+  uint64_t lower = 0, upper = std::numeric_limits<uint64_t>::max();
+  bool canonical = false;
   const char* out = "mer_counts.jf";
   const char* timing = nullptr;
   // --sam CHR_FILE (not in jellyfish): the input is SAM text and this process does what
@@ -71,12 +50,22 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   // scripts/RunJellyForRUFUS.sh:28-29; N defaults to 3328) -- BGZF inflated, the records found and their sequences packed
   // on the device (rfx_ingest.hpp BamIngest; csrc/rfx_bam.hip), the chromosome log written.  Goes with --keep-packed
   // (above), not with --sam or --spool.
+  const char* bam_chr = nullptr;
+  uint32_t bam_exclude = 3328;
   // --region REG (with --bam, ONE input; not in jellyfish): `samtools view -F N X.bam REG`, what runRufus.sh -R puts into the
   // generator -- only the records that overlap CHR[:BEG[-END]] are counted and logged; X.bam.bai / X.bai, when there, limits
   // what is inflated (rfx_bai.hpp, BamIngest::set_region).  Not with --keep-packed: the cache does not record a region.
-  const char* bam_chr = nullptr;
   const char* bam_region = nullptr;
-  uint32_t bam_exclude = 3328;
+  std::vector<const char*> inputs;
+  bool plain() const { return !sam_chr && !spool_path && !keep_path; }  // no route-limiting option but --bam
+};
+static const char* const BAM_ALONE = "rufus_amd jellyfish count: --bam finds and packs the records on the device, which needs one "
+                                     "device and none of --sam, --spool, --keep-packed";
+
+// The option table and every refusal that needs neither an input nor a device.
+static void parse_count(int argc, char** argv, CountArgs& a) {
+  uint64_t size = 0;
+  bool size_given = false;
   enum { OPT_DISK = 1000, OPT_OCL, OPT_TIMING, OPT_TEXT, OPT_SAM, OPT_SPOOL, OPT_KEEP, OPT_KEEPQ, OPT_BAM, OPT_BAMX, OPT_REGION };
   static option lo[] = {{"mer-len", 1, 0, 'm'},      {"size", 1, 0, 's'},        {"threads", 1, 0, 't'},
                         {"output", 1, 0, 'o'},       {"counter-len", 1, 0, 'c'}, {"out-counter-len", 1, 0, OPT_OCL},
@@ -89,564 +78,551 @@ static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
   int ch;
   while ((ch = getopt_long(argc, argv, "m:s:t:o:c:CL:U:p:", lo, nullptr)) != -1) {
     switch (ch) {
-      case 'm': k = atoi(optarg); break;
+      case 'm': a.k = atoi(optarg); break;
       case 's': if (!parse_si(optarg, size)) die(std::string("Invalid size '") + optarg + "'"); size_given = true; break;
-      case 't': threads = atoi(optarg); break;
-      case 'o': out = optarg; break;
+      case 't': a.threads = atoi(optarg); break;
+      case 'o': a.out = optarg; break;
       case 'c': break;  // in-memory counter width of the reference table: no meaning here
       case 'p': break;
-      case 'C': canonical = true; break;
-      case 'L': if (!parse_si(optarg, lower)) die("Invalid lower count"); break;
-      case 'U': if (!parse_si(optarg, upper)) die("Invalid upper count"); break;
+      case 'C': a.canonical = true; break;
+      case 'L': if (!parse_si(optarg, a.lower)) die("Invalid lower count"); break;
+      case 'U': if (!parse_si(optarg, a.upper)) die("Invalid upper count"); break;
       case OPT_DISK: break;  // table growth / merging is internal
-      case OPT_OCL: out_counter_len = atoi(optarg); break;
-      case OPT_TIMING: timing = optarg; break;
-      case OPT_SAM: sam_chr = optarg; break;
-      case OPT_SPOOL: spool_path = optarg; break;
-      case OPT_KEEP: keep_path = optarg; break;
-      case OPT_KEEPQ: keep_minq = atoi(optarg); break;
-      case OPT_BAM: bam_chr = optarg; break;
-      case OPT_BAMX: bam_exclude = (uint32_t)strtoul(optarg, nullptr, 0); break;
+      case OPT_OCL: a.out_counter_len = atoi(optarg); break;
+      case OPT_TIMING: a.timing = optarg; break;
+      case OPT_SAM: a.sam_chr = optarg; break;
+      case OPT_SPOOL: a.spool_path = optarg; break;
+      case OPT_KEEP: a.keep_path = optarg; break;
+      case OPT_KEEPQ: a.keep_minq = atoi(optarg); break;
+      case OPT_BAM: a.bam_chr = optarg; break;
+      case OPT_BAMX: a.bam_exclude = (uint32_t)strtoul(optarg, nullptr, 0); break;
       case OPT_REGION:
-        if (bam_region) die("rufus_amd jellyfish count: --region given twice: one region per run");
-        bam_region = optarg;
+        if (a.bam_region) die("rufus_amd jellyfish count: --region given twice: one region per run");
+        a.bam_region = optarg;
         break;
       case OPT_TEXT: die("rufus_amd jellyfish: --text output is not on the RUFUS path");
       default: die("Usage: jellyfish count -m K -s SIZE [-C] [-L n] [-U n] [-t T] [-o OUT] [--disk] file...");
     }
   }
-  if (k < 1 || !size_given) die("Missing required switch: -m, --mer-len and -s, --size");
-  if (optind >= argc) die("Missing sequence file");
-  static const char* const bam_alone =
-      "rufus_amd jellyfish count: --bam finds and packs the records on the device, which needs one device and none of --sam, "
-      "--spool, --keep-packed";
-  if (bam_chr && (sam_chr || spool_path)) die(bam_alone);
-  if (bam_region && !bam_chr) die("rufus_amd jellyfish count: --region goes with --bam CHR_FILE: only a BAM's records carry a position");
-  if (bam_region && keep_path)
+  a.inputs.assign(argv + optind, argv + argc);
+  if (a.k < 1 || !size_given) die("Missing required switch: -m, --mer-len and -s, --size");
+  if (a.inputs.empty()) die("Missing sequence file");
+  if (a.bam_chr && (a.sam_chr || a.spool_path)) die(BAM_ALONE);
+  if (a.bam_region && !a.bam_chr) die("rufus_amd jellyfish count: --region goes with --bam CHR_FILE: only a BAM's records carry a position");
+  if (a.bam_region && a.keep_path)
     die("rufus_amd jellyfish count: --region does not go with --keep-packed: the cache does not record a region");
-  if (bam_region && argc - optind != 1) die("rufus_amd jellyfish count: --region goes with ONE input: the region names one file's references");
-  int lsize = 0;
-  while ((1ull << lsize) < size) ++lsize;
-  if (lsize < 1) lsize = 1;
+  if (a.bam_region && a.inputs.size() != 1) die("rufus_amd jellyfish count: --region goes with ONE input: the region names one file's references");
+  while ((1ull << a.lsize) < size) ++a.lsize;
+}
 
-  // RUFUS_GPUS: one sample over several devices (include/rufus_hip.h rfx_count_set_peers) -- a device
-  // gets every N-th read block and partitions it; the owners of the minimizer bins pull their records, the survivors
-  // change hands by output position; the file is the devices' slices one after the other.  Needs the super-k-mer path
-  // (23 <= k <= 31): else the first device alone.
-  std::vector<int> gpus = gpu_list();
-  if (gpus.size() > 1 && !(k >= 23 && k <= 31)) {
-    fprintf(stderr, "rufus_amd jellyfish: k = %d is counted on one device (RUFUS_GPUS needs 23 <= k <= 31)\n", k);
-    gpus.resize(1);
-  }
-  const int n_gpu = (int)gpus.size();
-  // The devices are opened (HIP runtime start, context, arena: 0.1 - 0.25 s) on a thread of their own while this one
-  // looks at the inputs, starts the output's page allocation and the parser threads: the staging blocks are plain memory
-  // until their first upload (rfx_host_alloc_lazy / rfx_host_pin), so parsing needs no device.  Everything that touches
-  // a ctx or a table goes through device_ready() first.  (Round 6: ~0.3 s of a 1.3 s count of 64 M reads.)
+// Inputs: regular files are mapped (their size is known), pipes are streamed.  When the input is a pipe (its size is unknown:
+// RUFUS feeds 30x genomes through FIFOs, scripts/RunJellyForRUFUS.sh:23-31) or a big file, the packed read blocks stay in HBM
+// and are counted in minimizer-shard passes at finish (rfx_count_set_passes: bounded HBM, the analogue of --disk).
+struct Input { std::string path; int fd; bool regular; size_t size; };
+
+// The devices of a count: contexts, tables, the peer group and the read blocks that stay in HBM for the shard passes.
+// open() runs on the opener thread (rfx_cli.hpp Opener) while the main thread starts the output's page allocation and the
+// parser threads: the staging blocks are plain memory until their first upload (rfx_host_alloc_lazy / rfx_host_pin), so
+// parsing needs no device (round 6: ~0.3 s of a 1.3 s count of 64 M reads).  What touches a ctx or a table passes
+// Opener::wait() first.  RUFUS_GPUS: one sample over several devices (rfx_count_set_peers).
+struct CountDevices {
+  const std::vector<int> gpus;
+  bool defer = false;  // count in shard passes at finish: survey() says, before open()
   std::vector<rfx_ctx*> ctxs;
   std::vector<rfx_table*> tabs;
   rfx_peers* peers = nullptr;
-  rfx_ctx* ctx = nullptr;
-  rfx_table* tab = nullptr;
-  bool defer = false;  // (decided below, before the opener looks at it)
-  std::atomic<bool> inputs_known{false};
-  std::mutex open_mu;
-  std::condition_variable open_cv;
-  std::thread opener([&] {
-    ctxs = open_ctxs(gpus);
-    peers = n_gpu > 1 ? rfx_peers_create(n_gpu) : nullptr;
-    for (int g = 0; g < n_gpu; ++g) {
-      rfx_table* tb = rfx_count_begin(ctxs[g], k, canonical, lsize, 0, 0, 0);
-      if (!tb) die(std::string("rufus_amd: ") + rfx_last_error());
-      tabs.push_back(tb);
-    }
-    ctx = ctxs[0];
-    tab = tabs[0];
-    trace("count: device open, table made");
-    {  // (the passes / peers settings depend on what the inputs are: wait for the main thread's look at them)
-      std::unique_lock<std::mutex> g(open_mu);
-      open_cv.wait(g, [&] { return inputs_known.load(); });
-    }
-    for (int g = 0; g < n_gpu; ++g) {
-      if (defer && rfx_count_set_passes(tabs[g], 0) != RFX_OK) die(std::string("rufus_amd: ") + rfx_last_error());
-      if (peers && rfx_count_set_peers(tabs[g], peers, g) != RFX_OK) die(std::string("rufus_amd: ") + rfx_last_error());
-    }
-  });
-  auto device_ready = [&] {
-    if (opener.joinable()) opener.join();
-  };
-  // What the main thread refuses while it looks at the inputs: exit() must not run the HIP runtime's exit handlers while
-  // the opener is still inside the runtime's start (the heap is found damaged and the exit status is an abort's, not 1)
-  auto refuse = [&](const std::string& msg) {
-    device_ready();
-    die(msg);
-  };
-  const bool sync_open = getenv("RFX_SYNC_OPEN") != nullptr;  // (A/B: the device opened before anything else, as until round 6)
-  const auto t_init = std::chrono::steady_clock::now();
-
-  // Inputs: regular files are mapped (their size is known), pipes are streamed.  When the input is a pipe
-  // (its size is unknown: RUFUS feeds 30x genomes through FIFOs, scripts/RunJellyForRUFUS.sh:23-31) or a big
-  // file, the packed read blocks stay in HBM and the table counts them in minimizer-shard passes at finish
-  // (rfx_count_set_passes: bounded HBM, the analogue of --disk); small inputs are counted block by block.
-  struct Input { std::string path; int fd; bool regular; size_t size; };
-  std::vector<Input> inputs;
-  size_t known_bytes = 0;
-  bool any_stream = false;
-  for (int i = optind; i < argc; ++i) {
-    Input in{argv[i], -1, false, 0};
-    in.fd = strcmp(argv[i], "stdin") == 0 || strcmp(argv[i], "/dev/stdin") == 0 ? 0 : ::open(argv[i], O_RDONLY);
-    if (in.fd < 0) die(std::string("Failed to open input file '") + argv[i] + "'");
-    struct stat st;
-    if (fstat(in.fd, &st) == 0 && S_ISREG(st.st_mode)) {
-      in.regular = true;
-      in.size = (size_t)st.st_size;
-      known_bytes += in.size;
-    } else {
-      any_stream = true;
-    }
-    inputs.push_back(in);
-  }
-  // ~11 bytes of output per distinct solid k-mer: 0.18 of the FASTQ bytes at 30x, less on shallow or filtered input
-  OutputPrealloc prealloc;
-  double prealloc_frac = 0;
-  size_t prealloc_min = 0;
-  {
-    size_t min_bytes = 256u << 20;  // RFX_PREALLOC_MIN / RFX_PREALLOC_FRAC: the tests reach both sides of the guess
-    double frac = 0.19;
-    if (const char* ev = getenv("RFX_PREALLOC_MIN")) min_bytes = (size_t)strtoull(ev, nullptr, 10);
-    if (const char* ev = getenv("RFX_PREALLOC_FRAC")) frac = atof(ev);
-    if (!any_stream && known_bytes > min_bytes && !getenv("RFX_NO_PREALLOC"))
-      prealloc.start(out, (uint64_t)((double)known_bytes * frac));
-    // a piped input (scripts/RunJellyForRUFUS.sh:28: samtools view | ... | jellyfish count /dev/fd/0): the guess follows
-    // the bytes that have come in (profiles/r03_cli_w_trio.txt: 8.5 s of page faults after the device had finished)
-    else if (any_stream && inputs.size() == 1 && !getenv("RFX_NO_PREALLOC"))
-      prealloc.start_growing(out);
-    prealloc_frac = frac;
-    prealloc_min = min_bytes;
-  }
-  if (keep_path && bam_chr && inputs.size() != 1)
-    die("rufus_amd jellyfish count: --bam --keep-packed goes with ONE input: the cache describes one file's records");
-  if (keep_path && !bam_chr && (!sam_chr || inputs.size() != 1))
-    die("rufus_amd jellyfish count: --keep-packed goes with --sam and ONE input (a pipe with --spool, or a SAM file)");
-  if (keep_path && any_stream && !spool_path)  // (the cache points into the stream: without a copy of it there is nothing to point into)
-    die("rufus_amd jellyfish count: --keep-packed of a piped input needs --spool FILE (the cache refers to lines of the stream)");
-  if (spool_path && (!any_stream || inputs.size() != 1))
-    die("rufus_amd jellyfish count: --spool copies ONE piped input; a regular file can be given to the next stage as it is");
-  unsigned nthreads = (unsigned)std::max(1, threads);
-  nthreads = std::min(nthreads, rfx_host_cpus());  // -t 40 on a 16-CPU cgroup: 16 parsers
-  if (const char* ev = getenv("RFX_HOST_THREADS")) nthreads = (unsigned)std::max(1, atoi(ev));
-  const bool msp_ok = k >= 23 && k <= 31;  // the super-k-mer path (rfx_count_set_passes needs it)
-  defer = msp_ok && (any_stream || known_bytes > (16ull << 30) || getenv("RFX_COUNT_PASSES"));
-  if (const char* ev = getenv("RFX_COUNT_DEFER")) defer = msp_ok && atoi(ev) != 0;
-  if (n_gpu > 1) defer = true;
-  {
-    std::lock_guard<std::mutex> g(open_mu);
-    inputs_known = true;
-    open_cv.notify_all();
-  }
-  if (sync_open) device_ready();
-  std::vector<std::vector<rfx_reads*>> resident((size_t)n_gpu);
+  std::vector<std::vector<rfx_reads*>> resident;
   // A sample counted in shard passes at finish needs ~3 bytes of device memory per byte of packed reads beside them
   // (records of a pass, survivors): it is mapped while the input is still parsed, a few GiB per uploaded block -- in a fresh
   // process mapping 130 GB took 0.6 s of the time between "input parsed" and "finished on the device".
-  std::vector<uint64_t> reserved((size_t)n_gpu, 0);
-  auto sink_to = [&](int g, rfx_reads* r) {
-    device_ready();
-    if (!r) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
-    const int rc = rfx_count_add(tabs[g], r);
-    if (rc) die(std::string("rufus_amd: count failed: ") + rfx_strerror(rc) + " " + rfx_last_error());
-    if (defer) {
-      resident[(size_t)g].push_back(r);
-      if (!getenv("RFX_NO_RESERVE")) {
-        uint64_t used = 0, peak = 0, mapped = 0;
-        rfx_ctx* c = n_gpu == 1 ? ctx : ctxs[g];
-        if (rfx_mem_stats(c, &used, &peak, &mapped) == RFX_OK) {
-          const uint64_t want = std::min<uint64_t>(used * 4, 200ull << 30);
-          if (want > reserved[(size_t)g] + (4ull << 30)) {  // (in steps of >= 4 GiB; a refusal is no error: mapped when needed)
-            if (rfx_mem_reserve(c, want) == RFX_OK) reserved[(size_t)g] = want;
-            else reserved[(size_t)g] = ~0ull >> 1;
-          }
-        }
-      }
-    } else {
-      rfx_reads_free(r);
-    }
-  };
-  // Several devices: block b of packed reads goes to device b mod N -- each device partitions its blocks, the owners of
-  // the minimizer bins pull their record runs at finish (rfx_count_set_peers).  RFX_PEERS_REPLICATE=1: round 3's scheme,
-  // every block to EVERY device (each over its own PCIe link: one thread per device).
+  std::vector<uint64_t> reserved;
+  std::vector<std::mutex> mu;  // (one upload at a time per device: the table of a device is not re-entrant)
+  // Several devices: block b of packed reads goes to device b mod N; the owners of the minimizer bins pull their record runs at
+  // finish (rfx_count_set_peers).  RFX_PEERS_REPLICATE=1: round 3's scheme, every block to EVERY device, one thread per device.
   const bool replicate = getenv("RFX_PEERS_REPLICATE") != nullptr;
   std::atomic<uint64_t> next_block{0};
-  auto to_all = [&](const std::function<rfx_reads*(rfx_ctx*)>& up) {
-    device_ready();
-    if (n_gpu == 1) {
-      sink_to(0, up(ctx));
-      return;
-    }
-    if (!replicate) {
-      const int g = (int)(next_block.fetch_add(1) % (uint64_t)n_gpu);
-      static std::mutex dev_mu[128];  // (one upload at a time per device: the table of a device is not re-entrant)
-      std::lock_guard<std::mutex> lk(dev_mu[g]);
-      sink_to(g, up(ctxs[g]));
-      return;
-    }
-    std::vector<std::thread> th;
-    for (int g = 0; g < n_gpu; ++g) th.emplace_back([&, g] { sink_to(g, up(ctxs[g])); });
-    for (auto& t : th) t.join();
-  };
 
-  ReadBatch batch;
-  PackedBatch packed;
-  auto flush = [&]() {
-    if (batch.n() == 0) return;
-    int rc = packed.pack(batch, RFX_PACK_COUNT, 0);
-    if (rc) die(std::string("rufus_amd: pack failed: ") + rfx_strerror(rc));
-    to_all([&](rfx_ctx* c) { return packed.upload(c, batch.n(), RFX_PACK_COUNT); });
-    batch.clear();
-  };
-  auto sequential = [&](LineReader& in) {  // the reference's grammar: FASTA, multi-line FASTQ
-    const bool ok = parse_sequences(in, [&](const char* s, size_t n) {
-      batch.add(s, n);
-      if (batch.seq.size() >= (256u << 20) || batch.n() >= (1u << 22)) flush();
-    });
-    if (!ok) die("Unsupported format");
-    flush();  // k-mers never span files
-  };
-  std::unique_ptr<CountIngest> ingest;  // (kept to the end: its page-locked blocks serve the output drain)
-  // Round 6 (kernel K1): a regular FASTQ file counted on one device need not be parsed on the host at
-  // all -- its text can go to the device as it lies and be parsed and packed there (rfx_ingest.hpp TextIngest,
-  // csrc/rfx_text.hip): RFX_DEVICE_PARSE=1.  It is NOT the default, because on the GPU box it is no faster
-  // (profiles/r06_text_route.txt, 20 GB of FASTQ, 16-CPU quota): 16 parser threads parse and pack at 30 - 35 GB/s and
-  // upload 68 bytes per read; the text route has to move 330 bytes per read over PCIe and reaches ~30 GB/s with 8 MB
-  // pieces from 16 threads on one copy stream -- a draw for one count (0.6 - 0.8 s of ingest either way), and a draw for the
-  // three counts of `runRufus.sh -pj` at once (2.5 s both; with pread instead of the mapping the text route takes 4.1 s:
-  // three processes' readers on one tmpfs file system get in each other's way).  The route stays: it is what a host
-  // with fewer cores per GPU than this box wants (it needs a memcpy per read where the parser needs a microsecond).
-  const bool text_ok = n_gpu == 1 && nthreads > 1 && !sam_chr && !spool_path && !keep_path;
-  const bool device_text = text_ok && getenv("RFX_DEVICE_PARSE") && !getenv("RFX_HOST_PARSE");
-  std::unique_ptr<TextIngest> text_ingest;
-  // A bgzip'd FASTQ (a regular file whose first block rfx_bgzf_scan accepts) is inflated, parsed and packed on the device
-  // (rfx_ingest.hpp BgzfIngest; csrc/rfx_bgzf.hip) whether or not RFX_DEVICE_PARSE is set: compressed, the text is ~80
-  // bytes per read over PCIe and the host only reads the file.  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160).
-  // Plain gzip (no `BC` subfield) is not BGZF and goes where it went before.
-  std::unique_ptr<BgzfIngest> bgzf_ingest;
-  // A bgzip'd FASTA (its first inflated byte is '>': `ref.fa.gz` as `samtools faidx` wants it) takes the same route with
-  // the FASTA carry and parse (rfx_ingest.hpp BgzfIngest, fasta; csrc/rfx_fasta.hip).  Replaces the `zcat ref.fa.gz |`
-  // in front of the -e / -f databases (runRufus.sh:77, :115).
-  std::unique_ptr<BgzfIngest> fasta_ingest;
-  // A plain-gzip FASTQ (a regular file that begins 1f 8b 08 and is not BGZF: what a sequencer or an archive hands out) is
-  // inflated on the device too (rfx_ingest.hpp GzipIngest; csrc/rfx_gzip.hip: the stream cut speculatively, a chain rule on
-  // the host).  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160, :229-232).  On by default since it was measured
-  // against the pipe on a whole sample (5.4 s against 58 s); RFX_GZIP_DEVICE=0 sends plain gzip where
-  // it went before.
-  const bool gzip_device = !(getenv("RFX_GZIP_DEVICE") && atoi(getenv("RFX_GZIP_DEVICE")) == 0);
-  std::unique_ptr<GzipIngest> gzip_ingest;
-  // --bam: every input is a BAM file (rfx_ingest.hpp BamIngest).  One device, a regular file, neither --sam nor --spool;
-  // --keep-packed with one input leaves the BAM-kind cache (rfx_bam_cache.hpp).
-  std::unique_ptr<BamIngest> bam_ingest;
-  if (bam_chr && n_gpu != 1) refuse(bam_alone);
-  // a regular input of one of the three routes above: mapped, fed whole, unmapped, the route's counts traced
-  auto feed_whole = [&](auto& route, Input& in) {
-    void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
-    if (m == MAP_FAILED) refuse(std::string("cannot map '") + in.path + "': " + strerror(errno));
-    (void)madvise(m, in.size, MADV_SEQUENTIAL);
-    route.feed_mapped((const char*)m, in.size);
-    munmap(m, in.size);
-    trace(("count: " + route.counts()).c_str());
-    if (in.fd > 0) ::close(in.fd);
-  };
-  {
-    for (Input& in : inputs) {
-      bool done = false;
-      if (bam_chr) {
-        if (!in.regular) refuse("rufus_amd jellyfish count: --bam needs a regular file, not a pipe: the BAM is mapped");
-        if (!is_bgzf(in.fd, in.regular, in.size)) refuse(std::string("rufus_amd jellyfish count: --bam: '") + in.path + "' is not BGZF");
-        if (!bam_ingest) {
-          device_ready();
-          bam_ingest.reset(new BamIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, bam_exclude, env_arena("RFX_BAM_ARENA"), env_piece((size_t)8 << 20)));
-          if (keep_path) {
-            const int kfd = ::open(keep_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (kfd < 0) refuse(std::string("Can't open the packed-read cache '") + keep_path + "'");
-            bam_ingest->set_keep_packed(kfd, keep_minq);
-          }
-          if (bam_region) bam_ingest->set_region(bam_region, in.path);
-          trace("count: bam route, arenas open");
-        }
-        feed_whole(*bam_ingest, in);
-        if (keep_path) {  // (one input: checked above) the file is a cache only from here on
-          bam_ingest->finish_keep_packed();
-          trace(("count: " + bam_ingest->keep_counts()).c_str());
-        }
-        continue;
-      }
-      if (is_bgzf(in.fd, in.regular, in.size) && is_bam(in.fd, in.size))
-        refuse(std::string("rufus_amd jellyfish count: '") + in.path + "' is a BAM file: count it with --bam CHR_FILE");
-      if (is_bgzf(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
-        if (n_gpu != 1 || sam_chr || spool_path || keep_path)
-          refuse("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
-                 "--spool, --keep-packed: inflate it and pipe it in");
-        // every input decides for itself: a first inflated byte '>' is a reference FASTA (the FASTA route), anything else
-        // goes where it went before
-        const bool fasta = bgzf_first_byte(in.fd, in.size) == '>';
-        std::unique_ptr<BgzfIngest>& route = fasta ? fasta_ingest : bgzf_ingest;
-        if (!route) {
-          device_ready();
-          // (the FASTQ mode has no arena knob; RFX_FASTA_ARENA: >= 1 MiB, < 4 GiB)
-          route.reset(new BgzfIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, env_arena(fasta ? "RFX_FASTA_ARENA" : nullptr, 1ll << 20, ARENA_MAX),
-              env_piece((size_t)8 << 20), fasta));
-          trace(fasta ? "count: fasta route, text arenas open" : "count: bgzf route, text arenas open");
-        }
-        feed_whole(*route, in);
-        continue;
-      }
-      if (gzip_device && is_plain_gzip(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
-        if (n_gpu != 1 || sam_chr || spool_path || keep_path)
-          refuse("rufus_amd jellyfish count: plain-gzip input is inflated on the device, which needs one device and none of --sam, "
-                 "--spool, --keep-packed: inflate it and pipe it in");
-        if (gzip_first_byte(in.fd, in.size) != '@')
-          refuse(std::string("rufus_amd jellyfish count: '") + in.path + "' is plain gzip and its first inflated byte is not '@': only "
-                 "FASTQ is inflated on the device; pipe anything else in through zcat");
-        if (!gzip_ingest) {
-          device_ready();
-          gzip_ingest.reset(new GzipIngest(
-              ctx, [&](rfx_reads* r) { sink_to(0, r); }, env_arena("RFX_GZIP_ARENA", 1ll << 20, ARENA_MAX), env_piece((size_t)128 << 20)));
-          trace("count: gzip route, text arenas open");
-        }
-        feed_whole(*gzip_ingest, in);
-        continue;
-      }
-      if (device_text && in.regular && in.size > 0) {
-        if (!text_ingest) {
-          device_ready();
-          text_ingest.reset(new TextIngest(
-              ctx, nthreads, [&](rfx_reads* r) { sink_to(0, r); },
-              [&](const char* text, size_t n) {  // refused by the device (not strict 4-line FASTQ): the reference's grammar
-                LineReader lr(n + (1u << 20));
-                lr.preload(text, n);
-                lr.close_input();
-                sequential(lr);
-              },
-              (size_t)1 << 30, env_piece((size_t)8 << 20)));
-          trace("count: text arenas open, copiers up");
-        }
-        if (!getenv("RFX_TEXT_PREAD")) {  // (the mapped route; RFX_TEXT_PREAD=1: the workers pread their ranges -- faster for one
-                                          // count, 0.69 against 0.92 s per 20 GB, much slower for three at once)
-          void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
-          if (m != MAP_FAILED) {
-            (void)madvise(m, in.size, MADV_SEQUENTIAL);
-            done = text_ingest->feed_mapped((const char*)m, in.size);
-            trace("count: text fed");
-            munmap(m, in.size);
-            trace("count: input unmapped");
-          }
-        } else {
-          done = text_ingest->feed_file(in.fd, in.size);
-          trace("count: text fed");
-        }
-        if (done) {
-          if (in.fd > 0) ::close(in.fd);
-          continue;
-        }
-      }
-      if (nthreads > 1 || sam_chr || spool_path || keep_path) {
-        if (!ingest) {
-          ingest.reset(new CountIngest(nthreads, [&](const StageBlock& b) {
-            to_all([&](rfx_ctx* c) { return rfx_reads_upload(c, b.codes, b.acgt, nullptr, b.word_off, b.len, b.n_reads); });
-          }, sync_open ? rfx_host_alloc : rfx_host_alloc_lazy, rfx_host_free, 4u << 20, 24ull << 20, sync_open ? nullptr : rfx_host_pin));
-          ingest->set_sam(sam_chr != nullptr);
-          if (spool_path) {
-            const int sfd = ::open(spool_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (sfd < 0) refuse(std::string("Can't open spool file '") + spool_path + "'");
-            ingest->set_spool(sfd);
-          }
-          if (keep_path) {
-            const int kfd = ::open(keep_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (kfd < 0) refuse(std::string("Can't open the packed-read cache '") + keep_path + "'");
-            ingest->set_keep_packed(kfd, keep_minq);
-          }
-          if (getenv("RFX_INGEST_PIECE")) ingest->set_piece_bytes(env_piece(0));
-          if (prealloc.growing())
-            ingest->on_stream_bytes = [&prealloc, prealloc_frac, prealloc_min](uint64_t so_far) {
-              if (so_far > prealloc_min) prealloc.want((uint64_t)((double)so_far * prealloc_frac));
-            };
-          trace("count: staging blocks pinned, workers up");
-        }
-        if (in.regular) {
-          if (in.size == 0) { if (in.fd > 0) ::close(in.fd); continue; }
-          // mapped, not pread: measured on the 256-core box (20 GB FASTQ in tmpfs, 64 workers) 1.1 s against 3.2 s
-          // with every worker pread-ing its range into a private buffer (RFX_INGEST_PREAD=1 keeps that path testable)
-          if (getenv("RFX_INGEST_PREAD") && !sam_chr) {
-            done = ingest->feed_file(in.fd, in.size);
-          } else {
-            void* m = mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0);
-            if (m != MAP_FAILED) {
-              (void)madvise(m, in.size, MADV_SEQUENTIAL);
-              done = ingest->feed_mapped((const char*)m, in.size);
-              munmap(m, in.size);
-            }
-          }
-          if (!done) {
-            LineReader lr;
-            lr.attach(in.fd);
-            in.fd = -1;  // closed by the reader
-            sequential(lr);
-            done = true;
-          }
-        } else {
-          std::vector<char> head(1u << 16);
-          size_t got = 0;
-          for (;;) {
-            const ssize_t n = ::read(in.fd, head.data() + got, head.size() - got);
-            if (n < 0 && errno == EINTR) continue;
-            if (n < 0) refuse(std::string("read error on input: ") + strerror(errno));
-            if (n == 0) break;
-            got += (size_t)n;
-            if (got == head.size()) break;
-          }
-          head.resize(got);
-          if (gzip_device && got >= 3 && (unsigned char)head[0] == 0x1f && (unsigned char)head[1] == 0x8b && head[2] == 0x08)
-            refuse("rufus_amd jellyfish count: gzip input needs a regular file, not a pipe: the file is mapped; or inflate it and pipe the text in");
-          done = got == 0 || ingest->feed_stream(in.fd, head);
-          if (!done && spool_path) refuse("rufus_amd jellyfish count: --spool needs SAM (--sam) or strict 4-line FASTQ on the pipe");
-          if (!done) {
-            LineReader lr;
-            lr.preload(head.data(), head.size());
-            lr.attach(in.fd);
-            in.fd = -1;
-            sequential(lr);
-            done = true;
-          }
-        }
-      } else {
-        LineReader lr;
-        lr.attach(in.fd);
-        in.fd = -1;
-        sequential(lr);
-      }
-      if (in.fd > 0) ::close(in.fd);
+  explicit CountDevices(const std::vector<int>& g) : gpus(g), resident(g.size()), reserved(g.size(), 0), mu(g.size()) {}
+  int n() const { return (int)gpus.size(); }
+  void open(const CountArgs& a) {
+    ctxs = open_ctxs(gpus);
+    peers = n() > 1 ? rfx_peers_create(n()) : nullptr;
+    for (int g = 0; g < n(); ++g) {
+      rfx_table* tb = rfx_count_begin(ctxs[(size_t)g], a.k, a.canonical, a.lsize, 0, 0, 0);
+      if (!tb) die(std::string("rufus_amd: ") + rfx_last_error());
+      tabs.push_back(tb);
+    }
+    trace("count: device open, table made");
+    for (int g = 0; g < n(); ++g) {
+      if (defer && rfx_count_set_passes(tabs[(size_t)g], 0) != RFX_OK) die(std::string("rufus_amd: ") + rfx_last_error());
+      if (peers && rfx_count_set_peers(tabs[(size_t)g], peers, g) != RFX_OK) die(std::string("rufus_amd: ") + rfx_last_error());
     }
   }
-  // the packed-read cache is a cache only from here on: its header now says how many chunks describe how long a stream
-  if (keep_path && ingest) ingest->finish_keep_packed(inputs[0].regular ? inputs[0].size : ingest->spooled_bytes());
-  if (bam_chr) {
-    FILE* cf = fopen(bam_chr, "w");
-    if (!cf) {  // src/PassThroughSamCheck.cpp:37-44
-      printf("ERROR, Output file could not be opened -%s\n", bam_chr);
+  // one uploaded block into device g's table: counted and freed, or kept for the passes with room reserved beside it
+  void sink_to(int g, rfx_reads* r) {
+    Opener::wait();
+    if (!r) die(std::string("rufus_amd: upload failed: ") + rfx_last_error());
+    const int rc = rfx_count_add(tabs[(size_t)g], r);
+    if (rc) die(std::string("rufus_amd: count failed: ") + rfx_strerror(rc) + " " + rfx_last_error());
+    if (!defer) return rfx_reads_free(r);
+    resident[(size_t)g].push_back(r);
+    uint64_t used = 0, peak = 0, mapped = 0;
+    if (getenv("RFX_NO_RESERVE") || rfx_mem_stats(ctxs[(size_t)g], &used, &peak, &mapped) != RFX_OK) return;
+    const uint64_t want = std::min<uint64_t>(used * 4, 200ull << 30);
+    if (want > reserved[(size_t)g] + (4ull << 30))  // (in steps of >= 4 GiB; a refusal is no error: mapped when needed)
+      reserved[(size_t)g] = rfx_mem_reserve(ctxs[(size_t)g], want) == RFX_OK ? want : ~0ull >> 1;
+  }
+  // a block of the host parsers, uploaded by `up`: to the one device, to the next in turn, or to every one
+  void to_all(const std::function<rfx_reads*(rfx_ctx*)>& up) {
+    Opener::wait();
+    if (n() == 1) {
+      sink_to(0, up(ctxs[0]));
+    } else if (!replicate) {
+      const int g = (int)(next_block.fetch_add(1) % (uint64_t)n());
+      std::lock_guard<std::mutex> lk(mu[(size_t)g]);
+      sink_to(g, up(ctxs[(size_t)g]));
     } else {
-      if (bam_ingest)
-        for (const std::string& name : bam_ingest->chr_log()) fprintf(cf, "%s\n", name.c_str());
-      else fprintf(cf, "notachr\n");
-      fclose(cf);
+      std::vector<std::thread> th;
+      for (int g = 0; g < n(); ++g) th.emplace_back([&, g] { sink_to(g, up(ctxs[(size_t)g])); });
+      for (auto& t : th) t.join();
     }
   }
-  bam_ingest.reset();
-  if (sam_chr) {
-    FILE* cf = fopen(sam_chr, "w");
-    if (!cf) {  // src/PassThroughSamCheck.cpp:37-44
-      printf("ERROR, Output file could not be opened -%s\n", sam_chr);
+  // one record set per device (several: the finishes meet at the survivor exchange, one thread each); `hist`: null, or zeroed bins
+  std::vector<rfx_records*> finish(uint64_t lower, uint64_t upper, uint64_t* hist) {
+    std::vector<rfx_records*> recs((size_t)n(), nullptr);
+    if (n() == 1) {
+      recs[0] = rfx_count_finish(tabs[0], lower, upper, hist);
     } else {
-      if (ingest)
-        for (const std::string& name : ingest->chr_log()) fprintf(cf, "%s\n", name.c_str());
-      else fprintf(cf, "notachr\n");
-      fclose(cf);
+      std::vector<std::vector<uint64_t>> hs((size_t)n(), std::vector<uint64_t>(hist ? RFX_HISTO_BINS : 0));
+      std::vector<std::thread> th;
+      for (int g = 0; g < n(); ++g)
+        th.emplace_back([&, g] { recs[(size_t)g] = rfx_count_finish(tabs[(size_t)g], lower, upper, hist ? hs[(size_t)g].data() : nullptr); });
+      for (auto& t : th) t.join();
+      for (int i = 0; hist && i < RFX_HISTO_BINS; ++i)
+        for (int g = 0; g < n(); ++g) hist[i] += hs[(size_t)g][(size_t)i];
     }
+    for (rfx_records* r : recs)
+      if (!r) die(std::string("rufus_amd: finish failed: ") + rfx_last_error());
+    trace("count: finished on the device");
+    for (auto& v : resident)
+      for (rfx_reads* r : v) rfx_reads_free(r);
+    return recs;
   }
-  // (device-parsed input: no staging blocks to lend to the output drain -- its ring of page-locked buffers is made now,
-  // beside the device's finish, instead of in front of the first write)
-  std::vector<std::pair<char*, size_t>> out_ring;
-  std::thread out_ring_pinner;
-  bgzf_ingest.reset();
-  fasta_ingest.reset();
-  gzip_ingest.reset();
-  if (!ingest && text_ingest) {
-    trace(("count: text route, " + text_ingest->timing()).c_str());
-    text_ingest.reset();  // (its page-locked text buffers go first)
-    out_ring_pinner = std::thread([&out_ring] {
-      for (int i = 0; i < 8; ++i)
-        if (char* p = (char*)rfx_host_alloc(48u << 20)) out_ring.emplace_back(p, (size_t)48u << 20);
-    });
-  }
-  device_ready();  // (an empty input: nobody asked for the device yet)
-  const auto t_count = std::chrono::steady_clock::now();
-  trace("count: input parsed and queued");
-  if (getenv("RFX_CLI_TRACE")) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "write: output pages wanted %llu, allocated %llu, in the page table %llu",
-             (unsigned long long)prealloc.wanted(), (unsigned long long)prealloc.reached(), (unsigned long long)prealloc.populated());
-    trace(msg);
-  }
-
-  // RFX_COUNT_HISTO=1 (opt-in, not jellyfish behaviour): also write OUT.histo, byte for byte what
-  // `jellyfish histo -f -o OUT.histo OUT` would -- the count has the histogram anyway, and
-  // scripts/RunJellyForRUFUS.sh:36-38 runs histo only when that file is missing (a 35 GB re-read saved per sample).
-  const bool side_histo = getenv("RFX_COUNT_HISTO") != nullptr;
-  std::vector<uint64_t> hist(side_histo ? RFX_HISTO_BINS : 0);
-  std::vector<rfx_records*> recs((size_t)n_gpu, nullptr);
-  if (n_gpu == 1) {
-    recs[0] = rfx_count_finish(tab, lower, upper, side_histo ? hist.data() : nullptr);
-  } else {  // the finishes meet at the survivor exchange: one thread each
-    std::vector<std::vector<uint64_t>> hs((size_t)n_gpu, std::vector<uint64_t>(side_histo ? RFX_HISTO_BINS : 0));
-    std::vector<std::thread> th;
-    for (int g = 0; g < n_gpu; ++g)
-      th.emplace_back([&, g] { recs[(size_t)g] = rfx_count_finish(tabs[g], lower, upper, side_histo ? hs[(size_t)g].data() : nullptr); });
-    for (auto& t : th) t.join();
-    if (side_histo)
-      for (int g = 0; g < n_gpu; ++g)
-        for (int i = 0; i < RFX_HISTO_BINS; ++i) hist[(size_t)i] += hs[(size_t)g][(size_t)i];
-  }
-  for (rfx_records* r : recs)
-    if (!r) die(std::string("rufus_amd: finish failed: ") + rfx_last_error());
-  rfx_records* rec = recs[0];
-  trace("count: finished on the device");
-  for (auto& v : resident)
-    for (rfx_reads* r : v) rfx_reads_free(r);
-  std::vector<uint64_t> cols(2 * (size_t)k);
-  rfx_jf_matrix(lsize, k, cols.data());
-  if (side_histo && rec) {
-    const std::string hp = std::string(out) + ".histo";
-    if (FILE* hf = fopen(hp.c_str(), "w")) {
-      for (int i = 0; i < RFX_HISTO_BINS; ++i) fprintf(hf, "%d %llu\n", i, (unsigned long long)hist[(size_t)i]);
-      fclose(hf);
-    }
-  }
-  const int out_fd = prealloc.take();
-  if (getenv("RFX_CLI_TRACE")) {
-    char msg[128];
-    snprintf(msg, sizeof msg, "write: %llu bytes preallocated, %llu in the mapping's page table",
-             (unsigned long long)prealloc.reached(), (unsigned long long)prealloc.populated());
-    trace(msg);
-  }
-  if (out_ring_pinner.joinable()) out_ring_pinner.join();
-  write_jhash(out, recs, cols.data(), canonical, out_counter_len, full_argc, full_argv,
-              ingest ? ingest->lend_buffers(48u << 20) : out_ring, out_fd, prealloc.reached(), prealloc.take_mapping());
-  trace("count: output closed");
-  if (!timing && !getenv("RFX_CLEAN_EXIT")) {
-    // The device memory goes back BEFORE the process leaves (0.15 s for the 200 GB a 30x sample maps), not with the
-    // kernel's teardown of an exited process: the tool that runs next then takes 1.86 instead of 2.0 s (`histo` of a 30x
-    // database, three A/B pairs in one box) -- and on some boxes its first device allocation had waited 1 s (after a
-    // 64 M-read count) or 6 s (after a 30x sample) for memory that was still on its way back; that wait could not be
-    // reproduced at will, so this is a precaution with a measured small gain.  RFX_LEAVE_NO_CLOSE=1: as it was.
+  // The two teardowns.  leave_closed(): the device memory goes back BEFORE the process leaves (0.15 s for the 200 GB a 30x
+  // sample maps), not with the kernel's teardown of an exited process: the tool that runs next starts sooner (DESIGN.md
+  // section 4.11 has the measurements).  RFX_LEAVE_NO_CLOSE=1: as it was.
+  void leave_closed() {
     if (!getenv("RFX_LEAVE_NO_CLOSE")) {
       for (rfx_ctx* c : ctxs) rfx_close(c);
       trace("count: device closed");
     }
     leave(0);
   }
-  ingest.reset();
-  for (auto& b : out_ring) rfx_host_free(b.first);
-  for (rfx_records* r : recs) rfx_records_free(r);
-  for (rfx_table* tb : tabs) rfx_count_free(tb);
-  if (peers) rfx_peers_free(peers);
-  for (rfx_ctx* c : ctxs) rfx_close(c);
-  trace("count: closed");
-  if (timing) {
-    if (FILE* f = fopen(timing, "w")) {
-      fprintf(f, "Init     %g\nCounting %g\nWriting  %g\n", std::chrono::duration<double>(t_init - t_start).count(),
-              std::chrono::duration<double>(t_count - t_init).count(), secs_since(t_count));
-      fclose(f);
+  void close(const std::vector<rfx_records*>& recs) {  // --timing, RFX_CLEAN_EXIT=1: everything handed back piece by piece
+    for (rfx_records* r : recs) rfx_records_free(r);
+    for (rfx_table* tb : tabs) rfx_count_free(tb);
+    if (peers) rfx_peers_free(peers);
+    for (rfx_ctx* c : ctxs) rfx_close(c);
+    trace("count: closed");
+  }
+};
+
+// One run: what survey() finds out about the inputs, and what the routes share.
+struct CountRun {
+  const CountArgs& a;
+  CountDevices dv;
+  std::vector<Input> inputs;
+  size_t known_bytes = 0;
+  bool any_stream = false;
+  unsigned nthreads = 1;  // parser threads
+  OutputPrealloc prealloc;
+  double prealloc_frac = 0.19;  // RFX_PREALLOC_FRAC / RFX_PREALLOC_MIN: the tests reach both sides of the guess
+  size_t prealloc_min = 256u << 20;
+  const bool sync_open = getenv("RFX_SYNC_OPEN") != nullptr;  // (A/B: the device opened before anything else, as until round 6)
+  ReadBatch batch;  // the sequential parser's reads
+  PackedBatch packed;
+  std::unique_ptr<CountIngest> ingest;  // (kept to the end: its page-locked blocks serve the output drain)
+  std::unique_ptr<TextIngest> text;
+  std::unique_ptr<BgzfIngest> bgzf, fasta;
+  std::unique_ptr<GzipIngest> gzip;
+  std::unique_ptr<BamIngest> bam;
+  CountRun(const CountArgs& a_, const std::vector<int>& gpus) : a(a_), dv(gpus) {}
+  std::function<void(rfx_reads*)> sink() { return [this](rfx_reads* r) { dv.sink_to(0, r); }; }  // (the device-side routes: one device)
+};
+
+// Every input opened and sized, and what follows from that, before a device is asked for: an open and an fstat per input.
+static void survey(CountRun& run) {
+  const CountArgs& a = run.a;
+  for (const char* path : a.inputs) {
+    Input in{path, strcmp(path, "stdin") == 0 || strcmp(path, "/dev/stdin") == 0 ? 0 : ::open(path, O_RDONLY), false, 0};
+    if (in.fd < 0) die(std::string("Failed to open input file '") + path + "'");
+    struct stat st;
+    if (fstat(in.fd, &st) == 0 && S_ISREG(st.st_mode)) {
+      in.regular = true;
+      in.size = (size_t)st.st_size;
+      run.known_bytes += in.size;
+    } else {
+      run.any_stream = true;
     }
+    run.inputs.push_back(in);
+  }
+  if (a.keep_path && a.bam_chr && run.inputs.size() != 1)
+    die("rufus_amd jellyfish count: --bam --keep-packed goes with ONE input: the cache describes one file's records");
+  if (a.keep_path && !a.bam_chr && (!a.sam_chr || run.inputs.size() != 1))
+    die("rufus_amd jellyfish count: --keep-packed goes with --sam and ONE input (a pipe with --spool, or a SAM file)");
+  if (a.keep_path && run.any_stream && !a.spool_path)  // (the cache points into the stream: without a copy of it there is nothing to point into)
+    die("rufus_amd jellyfish count: --keep-packed of a piped input needs --spool FILE (the cache refers to lines of the stream)");
+  if (a.spool_path && (!run.any_stream || run.inputs.size() != 1))
+    die("rufus_amd jellyfish count: --spool copies ONE piped input; a regular file can be given to the next stage as it is");
+  run.nthreads = std::min((unsigned)std::max(1, a.threads), rfx_host_cpus());  // -t 40 on a 16-CPU cgroup: 16 parsers
+  if (const char* ev = getenv("RFX_HOST_THREADS")) run.nthreads = (unsigned)std::max(1, atoi(ev));
+  const bool msp_ok = a.k >= 23 && a.k <= 31;  // the super-k-mer path (rfx_count_set_passes needs it)
+  run.dv.defer = msp_ok && (run.any_stream || run.known_bytes > (16ull << 30) || getenv("RFX_COUNT_PASSES"));
+  if (const char* ev = getenv("RFX_COUNT_DEFER")) run.dv.defer = msp_ok && atoi(ev) != 0;
+  if (run.dv.n() > 1) run.dv.defer = true;
+}
+
+// ~11 bytes of output per distinct solid k-mer: 0.18 of the FASTQ bytes at 30x, less on shallow or filtered input
+static void start_prealloc(CountRun& run) {
+  if (const char* ev = getenv("RFX_PREALLOC_MIN")) run.prealloc_min = (size_t)strtoull(ev, nullptr, 10);
+  if (const char* ev = getenv("RFX_PREALLOC_FRAC")) run.prealloc_frac = atof(ev);
+  if (getenv("RFX_NO_PREALLOC")) return;
+  if (!run.any_stream && run.known_bytes > run.prealloc_min)
+    run.prealloc.start(run.a.out, (uint64_t)((double)run.known_bytes * run.prealloc_frac));
+  // a piped input (scripts/RunJellyForRUFUS.sh:28: samtools view | ... | jellyfish count /dev/fd/0): the guess follows
+  // the bytes that have come in (profiles/r03_cli_w_trio.txt: 8.5 s of page faults after the device had finished)
+  else if (run.any_stream && run.inputs.size() == 1)
+    run.prealloc.start_growing(run.a.out);
+}
+
+enum class Route { BAM, BGZF_FASTQ, BGZF_FASTA, GZIP, DEVICE_TEXT, HOST_PARALLEL, SEQUENTIAL };
+
+// Does the BGZF file begin with a BAM header?  (rfx_bam_header refuses BGZF whose first bytes are not BAM's magic; a header
+// that is not whole in the first 64 KiB is still BAM.)  What turns `jellyfish count X.bam` without --bam into a message
+// that says --bam instead of the FASTQ one.
+static bool is_bam(int fd, uint64_t size) {
+  if (!rfx_bam_header) return false;
+  const std::vector<uint8_t> head = read_head(fd, size, 1u << 16);
+  int complete = 0;
+  int32_t n_ref = 0;
+  uint64_t names_bytes = 0, first_block = 0;
+  uint32_t skip = 0;
+  return rfx_bam_header(head.data(), head.size(), &complete, &n_ref, nullptr, 0, &names_bytes, &first_block, &skip) == RFX_OK;
+}
+// Plain gzip is inflated on the device by default since it was measured against the pipe on a whole sample (DESIGN.md
+// section 4.20: 5.4 s against 58 s); RFX_GZIP_DEVICE=0 sends plain gzip where it went before.
+static bool gzip_on_device() { return !(getenv("RFX_GZIP_DEVICE") && atoi(getenv("RFX_GZIP_DEVICE")) == 0); }
+
+// Which route an input takes, or why it takes none.  Every input decides for itself, by these tests in this order.
+static Route route_of(const CountArgs& a, const Input& in, int n_gpu, unsigned nthreads) {
+  if (a.bam_chr) {  // every input is a BAM file: one device, a regular file, neither --sam nor --spool
+    if (!in.regular) die("rufus_amd jellyfish count: --bam needs a regular file, not a pipe: the BAM is mapped");
+    if (!is_bgzf(in.fd, in.regular, in.size)) die(std::string("rufus_amd jellyfish count: --bam: '") + in.path + "' is not BGZF");
+    return Route::BAM;
+  }
+  const bool alone = n_gpu == 1 && a.plain();  // what the routes that inflate or parse on the device need
+  if (is_bgzf(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
+    if (is_bam(in.fd, in.size))
+      die(std::string("rufus_amd jellyfish count: '") + in.path + "' is a BAM file: count it with --bam CHR_FILE");
+    if (!alone)
+      die("rufus_amd jellyfish count: BGZF input is inflated on the device, which needs one device and none of --sam, "
+          "--spool, --keep-packed: inflate it and pipe it in");
+    // a first inflated byte '>' is a reference FASTA (`ref.fa.gz` as `samtools faidx` wants it), anything else is taken for FASTQ
+    return bgzf_first_byte(in.fd, in.size) == '>' ? Route::BGZF_FASTA : Route::BGZF_FASTQ;
+  }
+  if (gzip_on_device() && is_plain_gzip(in.fd, in.regular, in.size)) {  // (rfx_cli.hpp)
+    if (!alone)
+      die("rufus_amd jellyfish count: plain-gzip input is inflated on the device, which needs one device and none of --sam, "
+          "--spool, --keep-packed: inflate it and pipe it in");
+    if (gzip_first_byte(in.fd, in.size) != '@')
+      die(std::string("rufus_amd jellyfish count: '") + in.path + "' is plain gzip and its first inflated byte is not '@': only "
+          "FASTQ is inflated on the device; pipe anything else in through zcat");
+    return Route::GZIP;
+  }
+  // RFX_DEVICE_PARSE=1 (kernel K1): a regular FASTQ file's text is parsed and packed on the device (rfx_ingest.hpp TextIngest,
+  // csrc/rfx_text.hip).  Not the default: with 16 parser threads a draw (profiles/r06_text_route.txt).
+  if (alone && nthreads > 1 && getenv("RFX_DEVICE_PARSE") && !getenv("RFX_HOST_PARSE") && in.regular && in.size > 0)
+    return Route::DEVICE_TEXT;
+  return nthreads > 1 || !a.plain() ? Route::HOST_PARALLEL : Route::SEQUENTIAL;
+}
+
+static int open_side_file(const char* what, const char* path) {  // the --keep-packed cache, the --spool copy
+  const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (fd < 0) die(std::string("Can't open ") + what + " '" + path + "'");
+  return fd;
+}
+
+// a regular input of the BAM, BGZF and gzip routes: mapped, fed whole, unmapped, the route's counts traced
+template <typename R>
+static void feed_whole(R& route, Input& in) {
+  const Mapped m = map_regular(in.fd, true);
+  if (!m.ok) die(std::string("cannot map '") + in.path + "': " + strerror(errno));
+  route.feed_mapped(m.p, m.n);
+  munmap((void*)m.p, m.n);
+  trace(("count: " + route.counts()).c_str());
+}
+
+// --bam (rfx_ingest.hpp BamIngest); --keep-packed with the one input leaves the BAM-kind cache (rfx_bam_cache.hpp)
+static void route_bam(CountRun& run, Input& in) {
+  const CountArgs& a = run.a;
+  if (!run.bam) {
+    Opener::wait();
+    run.bam.reset(new BamIngest(run.dv.ctxs[0], run.sink(), a.bam_exclude, env_arena("RFX_BAM_ARENA"), env_piece((size_t)8 << 20)));
+    if (a.keep_path) run.bam->set_keep_packed(open_side_file("the packed-read cache", a.keep_path), a.keep_minq);
+    if (a.bam_region) run.bam->set_region(a.bam_region, in.path);
+    trace("count: bam route, arenas open");
+  }
+  feed_whole(*run.bam, in);
+  if (a.keep_path) {  // (one input: checked by survey()) the file is a cache only from here on
+    run.bam->finish_keep_packed();
+    trace(("count: " + run.bam->keep_counts()).c_str());
+  }
+}
+
+// A bgzip'd FASTQ is inflated, parsed and packed on the device (rfx_ingest.hpp BgzfIngest; csrc/rfx_bgzf.hip) whether or not
+// RFX_DEVICE_PARSE is set: compressed, the text is ~80 bytes per read over PCIe and the host only reads the file.  Replaces
+// `zcat F.fastq.gz | ...` (runRufus.sh:157-160).  A bgzip'd FASTA takes the same route with the FASTA carry and parse
+// (csrc/rfx_fasta.hip): replaces the `zcat ref.fa.gz |` in front of the -e / -f databases (runRufus.sh:77, :115).
+static void route_bgzf(CountRun& run, Input& in, bool fasta) {
+  std::unique_ptr<BgzfIngest>& route = fasta ? run.fasta : run.bgzf;
+  if (!route) {
+    Opener::wait();
+    // (the FASTQ mode has no arena knob; RFX_FASTA_ARENA: >= 1 MiB, < 4 GiB)
+    route.reset(new BgzfIngest(run.dv.ctxs[0], run.sink(), env_arena(fasta ? "RFX_FASTA_ARENA" : nullptr, 1ll << 20, ARENA_MAX),
+                               env_piece((size_t)8 << 20), fasta));
+    trace(fasta ? "count: fasta route, text arenas open" : "count: bgzf route, text arenas open");
+  }
+  feed_whole(*route, in);
+}
+
+// A plain-gzip FASTQ is inflated on the device too (rfx_ingest.hpp GzipIngest; csrc/rfx_gzip.hip: the stream cut
+// speculatively, a chain rule on the host).  Replaces `zcat F.fastq.gz | ...` (runRufus.sh:157-160, :229-232).
+static void route_gzip(CountRun& run, Input& in) {
+  if (!run.gzip) {
+    Opener::wait();
+    run.gzip.reset(new GzipIngest(run.dv.ctxs[0], run.sink(), env_arena("RFX_GZIP_ARENA", 1ll << 20, ARENA_MAX), env_piece((size_t)128 << 20)));
+    trace("count: gzip route, text arenas open");
+  }
+  feed_whole(*run.gzip, in);
+}
+
+static void flush(CountRun& run) {
+  if (run.batch.n() == 0) return;
+  const int rc = run.packed.pack(run.batch, RFX_PACK_COUNT, 0);
+  if (rc) die(std::string("rufus_amd: pack failed: ") + rfx_strerror(rc));
+  run.dv.to_all([&](rfx_ctx* c) { return run.packed.upload(c, run.batch.n(), RFX_PACK_COUNT); });
+  run.batch.clear();
+}
+// the reference's grammar: FASTA, multi-line FASTQ
+static void sequential(CountRun& run, LineReader& lr) {
+  const bool ok = parse_sequences(lr, [&](const char* s, size_t n) {
+    run.batch.add(s, n);
+    if (run.batch.seq.size() >= (256u << 20) || run.batch.n() >= (1u << 22)) flush(run);
+  });
+  if (!ok) die("Unsupported format");
+  flush(run);  // k-mers never span files
+}
+// the input from its descriptor, behind what a parallel parser had already read of it
+static void route_sequential(CountRun& run, Input& in, const std::vector<char>& head) {
+  LineReader lr;
+  if (!head.empty()) lr.preload(head.data(), head.size());
+  lr.attach(in.fd);
+  in.fd = -1;  // closed by the reader
+  sequential(run, lr);
+}
+
+// false: the device refused the file; the host parser takes it
+static bool route_device_text(CountRun& run, Input& in) {
+  if (!run.text) {
+    Opener::wait();
+    run.text.reset(new TextIngest(
+        run.dv.ctxs[0], run.nthreads, run.sink(),
+        [&run](const char* text, size_t n) {  // refused by the device (not strict 4-line FASTQ): the reference's grammar
+          LineReader lr(n + (1u << 20));
+          lr.preload(text, n);
+          lr.close_input();
+          sequential(run, lr);
+        },
+        (size_t)1 << 30, env_piece((size_t)8 << 20)));
+    trace("count: text arenas open, copiers up");
+  }
+  bool done = false;
+  if (getenv("RFX_TEXT_PREAD")) {  // (the workers pread their ranges: 0.69 against 0.92 s per 20 GB, much slower for three at once)
+    done = run.text->feed_file(in.fd, in.size);
+    trace("count: text fed");
+  } else if (const Mapped m = map_regular(in.fd, true); m.ok) {
+    done = run.text->feed_mapped(m.p, m.n);
+    trace("count: text fed");
+    munmap((void*)m.p, m.n);
+    trace("count: input unmapped");
+  }
+  return done;
+}
+
+// The parallel host parser (rfx_ingest.hpp CountIngest) on a file or a pipe.  false: it refused the file, or the pipe's head
+// (`head`: what it had read of the pipe by then); the sequential parser takes the input -- unless --spool forbids that.
+static bool route_host_parallel(CountRun& run, Input& in, std::vector<char>& head) {
+  const CountArgs& a = run.a;
+  if (!run.ingest) {
+    run.ingest.reset(new CountIngest(
+        run.nthreads,
+        [&run](const StageBlock& b) {
+          run.dv.to_all([&](rfx_ctx* c) { return rfx_reads_upload(c, b.codes, b.acgt, nullptr, b.word_off, b.len, b.n_reads); });
+        },
+        run.sync_open ? rfx_host_alloc : rfx_host_alloc_lazy, rfx_host_free, 4u << 20, 24ull << 20, run.sync_open ? nullptr : rfx_host_pin));
+    run.ingest->set_sam(a.sam_chr != nullptr);
+    if (a.spool_path) run.ingest->set_spool(open_side_file("spool file", a.spool_path));
+    if (a.keep_path) run.ingest->set_keep_packed(open_side_file("the packed-read cache", a.keep_path), a.keep_minq);
+    if (getenv("RFX_INGEST_PIECE")) run.ingest->set_piece_bytes(env_piece(0));
+    if (run.prealloc.growing())
+      run.ingest->on_stream_bytes = [&run](uint64_t so_far) {
+        if (so_far > run.prealloc_min) run.prealloc.want((uint64_t)((double)so_far * run.prealloc_frac));
+      };
+    trace("count: staging blocks pinned, workers up");
+  }
+  if (in.regular) {
+    if (in.size == 0) return true;
+    // mapped, not pread: measured on the 256-core box (20 GB FASTQ in tmpfs, 64 workers) 1.1 s against 3.2 s
+    // with every worker pread-ing its range into a private buffer (RFX_INGEST_PREAD=1 keeps that path testable)
+    if (getenv("RFX_INGEST_PREAD") && !a.sam_chr) return run.ingest->feed_file(in.fd, in.size);
+    const Mapped m = map_regular(in.fd, true);
+    if (!m.ok) return false;
+    const bool done = run.ingest->feed_mapped(m.p, m.n);
+    munmap((void*)m.p, m.n);
+    return done;
+  }
+  head.resize(1u << 16);
+  size_t got = 0;
+  while (got < head.size()) {
+    const ssize_t n = ::read(in.fd, head.data() + got, head.size() - got);
+    if (n < 0 && errno == EINTR) continue;
+    if (n < 0) die(std::string("read error on input: ") + strerror(errno));
+    if (n == 0) break;
+    got += (size_t)n;
+  }
+  head.resize(got);
+  if (gzip_on_device() && got >= 3 && (unsigned char)head[0] == 0x1f && (unsigned char)head[1] == 0x8b && head[2] == 0x08)
+    die("rufus_amd jellyfish count: gzip input needs a regular file, not a pipe: the file is mapped; or inflate it and pipe the text in");
+  const bool done = got == 0 || run.ingest->feed_stream(in.fd, head);
+  if (!done && a.spool_path) die("rufus_amd jellyfish count: --spool needs SAM (--sam) or strict 4-line FASTQ on the pipe");
+  return done;
+}
+
+// One input down its route.  Device text that refuses a file falls through to the host parser, a host parser that refuses
+// a file or a pipe's head to the sequential one.
+static void feed(CountRun& run, Input& in) {
+  std::vector<char> head;
+  switch (route_of(run.a, in, run.dv.n(), run.nthreads)) {
+    case Route::BAM: route_bam(run, in); break;
+    case Route::BGZF_FASTQ: route_bgzf(run, in, false); break;
+    case Route::BGZF_FASTA: route_bgzf(run, in, true); break;
+    case Route::GZIP: route_gzip(run, in); break;
+    case Route::DEVICE_TEXT:
+      if (route_device_text(run, in)) break;
+      [[fallthrough]];
+    case Route::HOST_PARALLEL:
+      if (route_host_parallel(run, in, head)) break;
+      [[fallthrough]];
+    case Route::SEQUENTIAL: route_sequential(run, in, head);
+  }
+  if (in.fd > 0) ::close(in.fd);
+}
+
+// src/PassThroughSamCheck.cpp:37-44: the names the route logged, or, when no input took the route, its "notachr"
+template <typename R>
+static void write_chr_log(const char* path, const std::unique_ptr<R>& route) {
+  FILE* cf = fopen(path, "w");
+  if (!cf) {
+    printf("ERROR, Output file could not be opened -%s\n", path);
+    return;
+  }
+  if (route)
+    for (const std::string& name : route->chr_log()) fprintf(cf, "%s\n", name.c_str());
+  else fprintf(cf, "notachr\n");
+  fclose(cf);
+}
+
+// The caches and logs of the fed inputs closed, the device-side routes' arenas handed back.
+static void close_routes(CountRun& run) {
+  const CountArgs& a = run.a;
+  // the packed-read cache is a cache only from here on: its header now says how many chunks describe how long a stream
+  if (a.keep_path && run.ingest) run.ingest->finish_keep_packed(run.inputs[0].regular ? run.inputs[0].size : run.ingest->spooled_bytes());
+  if (a.bam_chr) write_chr_log(a.bam_chr, run.bam);
+  run.bam.reset();
+  if (a.sam_chr) write_chr_log(a.sam_chr, run.ingest);
+  run.bgzf.reset();
+  run.fasta.reset();
+  run.gzip.reset();
+}
+
+static void trace_pages(const char* fmt, uint64_t x, uint64_t y, uint64_t z = 0) {  // (fmt: two or three %llu; only when traced)
+  if (!getenv("RFX_CLI_TRACE")) return;
+  char msg[160];
+  snprintf(msg, sizeof msg, fmt, (unsigned long long)x, (unsigned long long)y, (unsigned long long)z);
+  trace(msg);
+}
+
+static int count_main(int argc, char** argv, int full_argc, char** full_argv) {
+  const double t_start = now();
+  CountArgs a;
+  parse_count(argc, argv, a);
+  // RUFUS_GPUS needs the super-k-mer path (23 <= k <= 31): else the first device alone
+  std::vector<int> gpus = gpu_list();
+  if (gpus.size() > 1 && !(a.k >= 23 && a.k <= 31)) {
+    fprintf(stderr, "rufus_amd jellyfish: k = %d is counted on one device (RUFUS_GPUS needs 23 <= k <= 31)\n", a.k);
+    gpus.resize(1);
+  }
+  CountRun run(a, gpus);
+  survey(run);
+  Opener opener([&run] { run.dv.open(run.a); });
+  const double t_init = now();
+  start_prealloc(run);
+  if (run.sync_open) Opener::wait();
+  if (a.bam_chr && run.dv.n() != 1) die(BAM_ALONE);
+  for (Input& in : run.inputs) feed(run, in);
+  close_routes(run);
+  // (device-parsed input: no staging blocks to lend to the output drain -- its ring of page-locked buffers is made now,
+  // beside the device's finish, instead of in front of the first write)
+  std::vector<std::pair<char*, size_t>> out_ring;
+  std::thread out_ring_pinner;
+  if (!run.ingest && run.text) {
+    trace(("count: text route, " + run.text->timing()).c_str());
+    run.text.reset();  // (its page-locked text buffers go first)
+    out_ring_pinner = std::thread([&out_ring] {
+      for (int i = 0; i < 8; ++i)
+        if (char* p = (char*)rfx_host_alloc(48u << 20)) out_ring.emplace_back(p, (size_t)48u << 20);
+    });
+  }
+  opener.join();  // (an empty input: nobody asked for the device yet)
+  const double t_count = now();
+  trace("count: input parsed and queued");
+  trace_pages("write: output pages wanted %llu, allocated %llu, in the page table %llu", run.prealloc.wanted(), run.prealloc.reached(),
+              run.prealloc.populated());
+
+  // RFX_COUNT_HISTO=1 (opt-in, not jellyfish behaviour): also write OUT.histo, byte for byte what `jellyfish histo -f -o OUT.histo OUT`
+  // would: scripts/RunJellyForRUFUS.sh:36-38 runs histo only when that file is missing (a 35 GB re-read saved per sample).
+  std::vector<uint64_t> hist(getenv("RFX_COUNT_HISTO") ? RFX_HISTO_BINS : 0);
+  const std::vector<rfx_records*> recs = run.dv.finish(a.lower, a.upper, hist.empty() ? nullptr : hist.data());
+  std::vector<uint64_t> cols(2 * (size_t)a.k);
+  rfx_jf_matrix(a.lsize, a.k, cols.data());
+  if (!hist.empty())
+    if (FILE* hf = fopen((std::string(a.out) + ".histo").c_str(), "w")) {
+      for (int i = 0; i < RFX_HISTO_BINS; ++i) fprintf(hf, "%d %llu\n", i, (unsigned long long)hist[(size_t)i]);
+      fclose(hf);
+    }
+  const int out_fd = run.prealloc.take();
+  trace_pages("write: %llu bytes preallocated, %llu in the mapping's page table", run.prealloc.reached(), run.prealloc.populated());
+  if (out_ring_pinner.joinable()) out_ring_pinner.join();
+  write_jhash(a.out, recs, cols.data(), a.canonical, a.out_counter_len, full_argc, full_argv,
+              run.ingest ? run.ingest->lend_buffers(48u << 20) : out_ring, out_fd, run.prealloc.reached(), run.prealloc.take_mapping());
+  trace("count: output closed");
+  if (!a.timing && !getenv("RFX_CLEAN_EXIT")) run.dv.leave_closed();
+  run.ingest.reset();
+  for (auto& b : out_ring) rfx_host_free(b.first);
+  run.dv.close(recs);
+  if (FILE* f = a.timing ? fopen(a.timing, "w") : nullptr) {
+    fprintf(f, "Init     %g\nCounting %g\nWriting  %g\n", t_init - t_start, t_count - t_init, now() - t_count);
+    fclose(f);
   }
   return 0;
 }

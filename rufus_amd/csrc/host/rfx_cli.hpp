@@ -23,6 +23,8 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -31,11 +33,51 @@
 
 namespace rfxcli {
 
+// What die() runs between its message and exit(1): one hook for the process (Opener below sets it).
+inline std::atomic<void (*)()> die_hook{nullptr};
+
 [[noreturn]] inline void die(const std::string& msg) {
   // jellyfish's err::die: message on stderr, non-zero exit (jf/include/jellyfish/err.hpp)
   fprintf(stderr, "%s\n", msg.c_str());
+  if (void (*hook)() = die_hook.load()) hook();
   exit(1);
 }
+
+// The devices are opened (HIP runtime start, context, arena: 0.1 - 0.25 s) on a thread of their own while the tool looks at
+// its input.  exit() must not run the runtime's exit handlers while that thread is still inside the runtime's start (the heap
+// is found damaged and the exit status is an abort's, not 1: profiles/ingest_refactor.txt), so while an Opener lives, die() on
+// any other thread waits for the work to end before it exits.  On the opener thread itself ("no MI355X device") it does not
+// wait; the work never ends then, and whoever waits stays blocked until that exit() has ended the process.  One Opener at a
+// time (the state is the process's: a second one is refused); wait() may be called from any thread, join() by the owner.
+class Opener {
+  struct State { std::mutex mu; std::condition_variable cv; bool running; };
+  static inline State& state = *new State{};  // (never destroyed: exit() on one thread must not take it from under a waiter on another)
+  static inline thread_local bool on_opener = false;
+  static void set_running(bool on) {
+    std::lock_guard<std::mutex> g(state.mu);
+    state.running = on;
+    state.cv.notify_all();
+  }
+  std::thread th_;
+
+ public:
+  template <typename F>
+  explicit Opener(F work) {
+    if (die_hook.load()) die("rufus_amd: internal error: a second Opener beside a live one");
+    set_running(true);
+    die_hook = [] { if (!on_opener) wait(); };
+    th_ = std::thread([work] { on_opener = true; work(); set_running(false); });
+  }
+  static void wait() {
+    std::unique_lock<std::mutex> g(state.mu);
+    state.cv.wait(g, [] { return !state.running; });
+  }
+  void join() {
+    if (th_.joinable()) th_.join();
+    die_hook = nullptr;
+  }
+  ~Opener() { join(); }
+};
 
 inline rfx_ctx* open_ctx() {
   const char* dev = getenv("RUFUS_GPU");

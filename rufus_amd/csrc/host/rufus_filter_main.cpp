@@ -913,8 +913,8 @@ static int run_packed(const FilterArgs& a) {
 //   the main thread writes the formatted pieces in input order.
 // The device is opened (0.1 - 0.25 s of runtime start-up) and the set built beside the readers and the workers' first
 // pieces: a worker needs them when its first piece is packed (RFX_SYNC_OPEN=1: before anything else, as it used to be).
-// A reader or a worker that has to refuse the input does so through refuse(): exit() while the opener thread is inside
-// the runtime's start can end in the C library's abort instead of status 1, so the opener is waited for first.
+// A reader or a worker that has to refuse the input just calls die(): while the Opener lives, die() waits for the opener
+// thread before it exits (rfx_cli.hpp).
 namespace textf {
 static bool parse(int argc, char** argv, FilterArgs& a) {
   const int need = SINGLE ? 8 : 9;
@@ -985,27 +985,9 @@ static int run(const FilterArgs& a) {
   // RUFUS_GPUS: the pieces are dealt to the devices by worker thread (the filter shards by read block)
   const std::vector<int> gpus = gpu_list();
   const size_t n_gpu = gpus.size();
-  Devices dv;
-  std::mutex open_mu;
-  std::condition_variable open_cv;
-  bool dev_ready = false;
-  std::thread opener([&] {
-    Devices opened;
-    opened.open(gpus, keys, a.k, "filter: device open, set built");
-    std::lock_guard<std::mutex> g(open_mu);
-    dv = std::move(opened);
-    dev_ready = true;
-    open_cv.notify_all();
-  });
-  auto wait_device = [&] {
-    std::unique_lock<std::mutex> g(open_mu);
-    open_cv.wait(g, [&] { return dev_ready; });
-  };
-  auto refuse = [&](const std::string& msg) {  // die() from a reader or a worker: not while the opener is in the runtime's start
-    wait_device();
-    die(msg);
-  };
-  if (getenv("RFX_SYNC_OPEN")) wait_device();
+  Devices dv;  // (the opener's until Opener::wait() has returned)
+  Opener opener([&] { dv.open(gpus, keys, a.k, "filter: device open, set built"); });
+  if (getenv("RFX_SYNC_OPEN")) Opener::wait();
 
   for (int i = 0; i < n_streams; ++i) {
     const Mapped m = getenv("RFX_FILTER_NO_MMAP") ? Mapped() : map_regular(st[i].fd, true);
@@ -1093,7 +1075,7 @@ static int run(const FilterArgs& a) {
       if (cur->cap - cur->size < RD) grow(cur, cur->cap + cur->cap / 2 + RD);
       const ssize_t n = ::read(S.fd, cur->own.get() + cur->size, RD);
       if (n < 0 && errno == EINTR) continue;
-      if (n < 0) refuse(std::string("read error on input: ") + strerror(errno));
+      if (n < 0) die(std::string("read error on input: ") + strerror(errno));
       if (n == 0) break;
       cur->size += (size_t)n;
       while (scanned < cur->size) {
@@ -1162,7 +1144,7 @@ static int run(const FilterArgs& a) {
   };
   auto worker = [&](unsigned me) {
     const size_t dev = (size_t)me % n_gpu;
-    bool up = false;  // the opener is done: known by the first upload at the latest (wait_device() before it)
+    bool up = false;  // the opener is done: known by the first upload at the latest (Opener::wait() before it)
     std::vector<uint64_t> ls[2], ss[2], qs[2], mask;  // line starts, sequence / quality starts
     std::vector<uint32_t> sl[2], hits;
     std::vector<char> fix;  // private copies of quality strings that are shorter than their read
@@ -1193,7 +1175,7 @@ static int run(const FilterArgs& a) {
           sl[m][i] = len_of(4 * i + 1);
           qs[m][i] = ls[m][4 * i + 3];
           if (m == 0 && sl[m][i] == 0)
-            refuse("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
+            die("rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected");
         }
       }
       // pack: reads of mate 1, then of mate 2, into one block
@@ -1201,7 +1183,7 @@ static int run(const FilterArgs& a) {
       uint64_t words = 0;
       for (int m = 0; m < n_streams; ++m)
         for (size_t i = 0; i < n; ++i) words += (sl[m][i] + 31) / 32;
-      if (!stage.need(words, nr, up)) refuse(NO_STAGING);
+      if (!stage.need(words, nr, up)) die(NO_STAGING);
       uint32_t w0 = 0;
       for (int m = 0; m < n_streams; ++m) {
         const char* t = pc[m]->data;
@@ -1221,7 +1203,7 @@ static int run(const FilterArgs& a) {
           if (run > at &&
               rfx_pack_spans(t, ss[m].data() + at, sl[m].data() + at, qs[m].data() + at, (uint32_t)(run - at), min_q,
                              RFX_PACK_FILTER, stage.codes, nullptr, stage.good, woff + at, lens + at) != RFX_OK)
-            refuse("rufus_amd: pack failed");
+            die("rufus_amd: pack failed");
           if (run < n) {
             const uint32_t L = sl[m][run], ql = qlen(run);
             fix.assign((size_t)2 * L, '\0');
@@ -1230,7 +1212,7 @@ static int run(const FilterArgs& a) {
             const uint64_t s0 = 0, q0 = L;
             if (rfx_pack_spans(fix.data(), &s0, &L, &q0, 1, min_q, RFX_PACK_FILTER, stage.codes, nullptr, stage.good, woff + run,
                                lens + run) != RFX_OK)
-              refuse("rufus_amd: pack failed");
+              die("rufus_amd: pack failed");
             ++run;
           }
           at = run;
@@ -1240,7 +1222,7 @@ static int run(const FilterArgs& a) {
       mask.assign((nr + 63) / 64, 0);
       if (SINGLE) hits.assign(nr, 0);
       if (!up) {
-        wait_device();
+        Opener::wait();
         up = true;
         stage.lock();
       }

@@ -22,10 +22,23 @@ struct rfx_reads {
   std::vector<uint32_t> good, woff, len;
 };
 
+// (as in jellyfish_harness.cpp: the device's start takes RFX_TEST_OPEN_MS milliseconds, and an exit beside it is reported)
+static std::atomic<int> g_opening{0};
+static const char EXIT_BESIDE_OPEN[] = "HARNESS: exit() while rfx_open is running\n";
+static const int g_exit_watch = atexit([] {
+  if (g_opening.load()) (void)!::write(2, EXIT_BESIDE_OPEN, sizeof EXIT_BESIDE_OPEN - 1);
+});
+
 extern "C" {
 
 const char* rfx_last_error(void) { return "host stand-in"; }
-rfx_ctx* rfx_open(int device, size_t) { return new rfx_ctx{device}; }
+rfx_ctx* rfx_open(int device, size_t) {
+  const char* ms = getenv("RFX_TEST_OPEN_MS");
+  ++g_opening;
+  if (ms) std::this_thread::sleep_for(std::chrono::milliseconds(atoi(ms)));
+  --g_opening;
+  return new rfx_ctx{device};
+}
 void rfx_close(rfx_ctx* c) { delete c; }
 int rfx_ctx_allow_peers(rfx_ctx*, const int*, int) { return RFX_OK; }
 void* rfx_host_alloc(size_t bytes) { return malloc(bytes); }

@@ -63,10 +63,24 @@ static rfx_records* make_records(int k, int lsize, const uint64_t* cols, std::ve
   return r;
 }
 
+// The device's start takes RFX_TEST_OPEN_MS milliseconds here (default 0), and a process that exits while a thread is inside
+// it says so on stderr: the real runtime's exit handlers beside its own start are what once ended a refusal in an abort.
+static std::atomic<int> g_opening{0};
+static const char EXIT_BESIDE_OPEN[] = "HARNESS: exit() while rfx_open is running\n";
+static const int g_exit_watch = atexit([] {
+  if (g_opening.load()) (void)!::write(2, EXIT_BESIDE_OPEN, sizeof EXIT_BESIDE_OPEN - 1);
+});
+
 extern "C" {
 
 const char* rfx_last_error(void) { return g_stand_in_err.c_str(); }
-rfx_ctx* rfx_open(int device, size_t) { return new rfx_ctx{device}; }
+rfx_ctx* rfx_open(int device, size_t) {
+  const char* ms = getenv("RFX_TEST_OPEN_MS");
+  ++g_opening;
+  if (ms) std::this_thread::sleep_for(std::chrono::milliseconds(atoi(ms)));
+  --g_opening;
+  return new rfx_ctx{device};
+}
 void rfx_close(rfx_ctx* c) { delete c; }
 int rfx_ctx_allow_peers(rfx_ctx*, const int*, int) { return RFX_OK; }
 void* rfx_host_alloc(size_t bytes) { return malloc(bytes); }

@@ -319,3 +319,8 @@ def test_empty_sequence_line_is_refused_with_status_1(harness, packed_dir, tmp_p
     assert r.returncode == 1
     assert r.stderr == b"rufus_amd RUFUS.Filter: empty sequence line (undefined behaviour in the reference) -- rejected\n"
     assert r.stdout.startswith(CALL_TEXT + DONE_HASH)
+    # the same with a device that takes 300 ms to start (the stand-in's rfx_open): die() waits for the opener thread
+    # (rfx_cli.hpp Opener), so the harness does not see an exit beside a running rfx_open
+    slow = _run(harness, d, [f"{packed_dir}/hl", "m1.fq", "m2.fq", "o"] + T, RFX_TEST_OPEN_MS="300",
+                **({"RFX_SYNC_OPEN": "1"} if sync_open else {}))
+    assert (slow.returncode, slow.stderr) == (r.returncode, r.stderr)

@@ -306,3 +306,138 @@ def test_count_text_route_and_what_it_hands_back(jf, jf_san, small_trio, tmp_pat
     open(f"{d}/wrapped.fq", "wb").write(wrapped)
     r = sh(base + ["-o", "w.jf", "wrapped.fq"], d, env={"RFX_DEVICE_PARSE": "1"})
     assert r.returncode == 0 and _payload(f"{d}/w.jf") == want, r.stderr[-400:]
+
+
+# ---- the refusals of `count`: status, stdout and stderr as the executable gave them before count_main was cut into
+# CountArgs / survey / route_of / the routes (recorded from that build), and none of them an exit beside a starting device
+
+def _bgzf_block(data):
+    import struct
+    import zlib
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    raw = c.compress(data) + c.flush()
+    return (b"\x1f\x8b\x08\x04" + bytes(4) + b"\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(raw) + 25) + raw +
+            struct.pack("<II", zlib.crc32(data), len(data)))
+
+
+ONE_FQ = b"@r\n" + b"ACGTTGCA" * 6 + b"\n+\n" + b"I" * 48 + b"\n"
+ONE_SAM = b"\t".join([b"r", b"0", b"chr1", b"1", b"60", b"48M", b"*", b"0", b"0", b"ACGTTGCA" * 6, b"I" * 48]) + b"\n"
+
+
+def _refusal_inputs(d):
+    import gzip
+    files = {"one.fq": ONE_FQ, "one.fq.gz": gzip.compress(ONE_FQ, mtime=0), "one.bgzf.gz": _bgzf_block(ONE_FQ) + _bgzf_block(b""),
+             "junk.txt": b"neither\nFASTA nor FASTQ\n", "hdr.sam": b"@HD\tVN:1.6\n" + ONE_SAM}
+    for name, blob in files.items():
+        open(os.path.join(d, name), "wb").write(blob)
+    return dict(files, **{"one.fa": b">s\n" + b"ACGTTGCA" * 6 + b"\n", "one.sam": ONE_SAM, "": b""})
+
+
+C = ["count", "-m", "25", "-s", "1M", "-C", "-t", "2"]
+USAGE = b"Usage: jellyfish count -m K -s SIZE [-C] [-L n] [-U n] [-t T] [-o OUT] [--disk] file...\n"
+ONE_DEVICE = b", which needs one device and none of --sam, --spool, --keep-packed"
+J, JC = b"rufus_amd jellyfish: ", b"rufus_amd jellyfish count: "
+KEEP_SAM_ONE = JC + b"--keep-packed goes with --sam and ONE input (a pipe with --spool, or a SAM file)\n"
+MISSING_SWITCH = b"Missing required switch: -m, --mer-len and -s, --size\n"
+# name: the whole of stderr; stdout is empty and the status 1 every time
+STDERR = {
+    "keep_without_sam": KEEP_SAM_ONE,
+    "keep_two_inputs": KEEP_SAM_ONE,
+    "keep_pipe_without_spool": JC + b"--keep-packed of a piped input needs --spool FILE (the cache refers to lines of the stream)\n",
+    "bam_keep_two_inputs": JC + b"--bam --keep-packed goes with ONE input: the cache describes one file's records\n",
+    "spool_regular_file": JC + b"--spool copies ONE piped input; a regular file can be given to the next stage as it is\n",
+    "missing_input": b"Failed to open input file 'nothere.fq'\n",
+    "several_devices_small_k_missing_input": J + b"k = 15 is counted on one device (RUFUS_GPUS needs 23 <= k <= 31)\n"
+                                             b"Failed to open input file 'nothere.fq'\n",
+    "sam_on_bgzf": JC + b"BGZF input is inflated on the device" + ONE_DEVICE + b": inflate it and pipe it in\n",
+    "sam_on_gzip": JC + b"plain-gzip input is inflated on the device" + ONE_DEVICE + b": inflate it and pipe it in\n",
+    "sam_header_first": J + b"--sam: a line has fewer than 10 tab-separated fields (a header? feed `samtools view` without -h)\n",
+    "bam_on_text": JC + b"--bam: 'one.fq' is not BGZF\n",
+    "bam_on_bgzf": JC + b"this library cannot read BAM input\n",
+    "bam_on_pipe": JC + b"--bam needs a regular file, not a pipe: the BAM is mapped\n",
+    "bam_two_devices": JC + b"--bam finds and packs the records on the device" + ONE_DEVICE + b"\n",
+    "bam_with_sam": JC + b"--bam finds and packs the records on the device" + ONE_DEVICE + b"\n",
+    "region_without_bam": JC + b"--region goes with --bam CHR_FILE: only a BAM's records carry a position\n",
+    "region_twice": JC + b"--region given twice: one region per run\n",
+    "region_with_keep": JC + b"--region does not go with --keep-packed: the cache does not record a region\n",
+    "region_two_inputs": JC + b"--region goes with ONE input: the region names one file's references\n",
+    "unsupported_format": b"Unsupported format\n",
+    "unsupported_format_one_thread": b"Unsupported format\n",
+    "bare_bgzf": JC + b"this library cannot inflate BGZF input\n",
+    "bare_gzip": JC + b"this library cannot inflate plain-gzip input\n",
+    "gzip_on_pipe": JC + b"gzip input needs a regular file, not a pipe: the file is mapped; or inflate it and pipe the text in\n",
+    "spool_fasta_on_pipe": JC + b"--spool needs SAM (--sam) or strict 4-line FASTQ on the pipe\n",
+    "missing_mer_len": MISSING_SWITCH,
+    "missing_size": MISSING_SWITCH,
+    "no_input": b"Missing sequence file\n",
+    "invalid_size": b"Invalid size '1Q'\n",
+    "text_output": J + b"--text output is not on the RUFUS path\n",
+    "unknown_option": b"count: unrecognized option '--what'\n" + USAGE,
+}
+# name: (arguments, environment, what is piped into stdin (a key of _refusal_inputs) or None)
+REFUSALS = {
+    "keep_without_sam": (C + ["--keep-packed", "kp", "one.fq"], {}, None),
+    "keep_two_inputs": (C + ["--sam", "c.chr", "--keep-packed", "kp", "one.fq", "one.fq"], {}, None),
+    "keep_pipe_without_spool": (C + ["--sam", "c.chr", "--keep-packed", "kp", "/dev/stdin"], {}, "one.sam"),
+    "bam_keep_two_inputs": (C + ["--bam", "c.chr", "--keep-packed", "kp", "one.bgzf.gz", "one.bgzf.gz"], {}, None),
+    "spool_regular_file": (C + ["--spool", "sp", "one.fq"], {}, None),
+    "missing_input": (C + ["one.fq", "nothere.fq"], {}, None),
+    "several_devices_small_k_missing_input": (["count", "-m", "15", "-s", "1M", "nothere.fq"], {"RUFUS_GPUS": "0,0"}, None),
+    "sam_on_bgzf": (C + ["--sam", "c.chr", "one.bgzf.gz"], {}, None),
+    "sam_on_gzip": (C + ["--sam", "c.chr", "one.fq.gz"], {}, None),
+    "sam_header_first": (C + ["--sam", "c.chr", "hdr.sam"], {}, None),
+    "bam_on_text": (C + ["--bam", "c.chr", "one.fq"], {}, None),
+    "bam_on_bgzf": (C + ["--bam", "c.chr", "one.bgzf.gz"], {}, None),
+    "bam_on_pipe": (C + ["--bam", "c.chr", "/dev/stdin"], {}, ""),
+    "bam_two_devices": (C + ["--bam", "c.chr", "one.bgzf.gz"], {"RUFUS_GPUS": "0,0"}, None),
+    "bam_with_sam": (C + ["--bam", "c.chr", "--sam", "s.chr", "one.bgzf.gz"], {}, None),
+    "region_without_bam": (C + ["--region", "chr1", "one.fq"], {}, None),
+    "region_twice": (C + ["--bam", "c.chr", "--region", "chr1", "--region", "chr2", "one.bgzf.gz"], {}, None),
+    "region_with_keep": (C + ["--bam", "c.chr", "--region", "chr1", "--keep-packed", "kp", "one.bgzf.gz"], {}, None),
+    "region_two_inputs": (C + ["--bam", "c.chr", "--region", "chr1", "one.bgzf.gz", "one.bgzf.gz"], {}, None),
+    "unsupported_format": (C + ["junk.txt"], {}, None),
+    "unsupported_format_one_thread": (C + ["-t", "1", "junk.txt"], {}, None),
+    "bare_bgzf": (C + ["one.bgzf.gz"], {}, None),
+    "bare_gzip": (C + ["one.fq.gz"], {}, None),
+    "gzip_on_pipe": (C + ["/dev/stdin"], {}, "one.fq.gz"),
+    "spool_fasta_on_pipe": (C + ["--spool", "sp", "/dev/stdin"], {}, "one.fa"),
+    "missing_mer_len": (["count", "-s", "1M", "one.fq"], {}, None),
+    "missing_size": (["count", "-m", "25", "one.fq"], {}, None),
+    "no_input": (C, {}, None),
+    "invalid_size": (["count", "-m", "25", "-s", "1Q", "one.fq"], {}, None),
+    "text_output": (C + ["--text", "one.fq"], {}, None),
+    "unknown_option": (C + ["--what", "one.fq"], {}, None),
+}
+# the refusals that come after the thread that opens the device has been started
+BESIDE_THE_OPENER = ["missing_input", "keep_without_sam", "keep_two_inputs", "keep_pipe_without_spool", "bam_keep_two_inputs",
+                     "spool_regular_file", "unsupported_format", "unsupported_format_one_thread", "sam_header_first",
+                     "spool_fasta_on_pipe"]
+EXIT_BESIDE_OPEN = b"HARNESS: exit() while rfx_open is running\n"
+
+
+def _refuse(exe, d, name, **env):
+    args, case_env, piped = REFUSALS[name]
+    files = _refusal_inputs(d)
+    r = sh([exe] + args, d, env=dict(case_env, **env), timeout=60, input=b"" if piped is None else files[piped])
+    return (r.returncode, r.stdout, r.stderr), (1, b"", STDERR[name])
+
+
+@pytest.mark.parametrize("name", sorted(REFUSALS))
+def test_count_refusals_are_what_they_were(jf, tmp_path, name):
+    got, want = _refuse(jf, str(tmp_path), name)
+    assert got == want
+
+
+@pytest.mark.parametrize("name", BESIDE_THE_OPENER)
+def test_count_never_exits_beside_a_starting_device(jf, tmp_path, name):
+    """The harness's rfx_open takes 300 ms and its exit handler reports an exit() that runs meanwhile: what, with the real
+    runtime, ended in the C library's abort (status 134) instead of status 1.  die() waits for the opener thread
+    (rfx_cli.hpp Opener) whichever thread refuses."""
+    got, want = _refuse(jf, str(tmp_path), name, RFX_TEST_OPEN_MS="300")
+    assert EXIT_BESIDE_OPEN not in got[2] and got == want
+
+
+@pytest.mark.parametrize("name", BESIDE_THE_OPENER)
+def test_count_never_exits_beside_a_starting_device_under_sanitizers(jf_san, tmp_path, name):
+    got, want = _refuse(jf_san, str(tmp_path), name, RFX_TEST_OPEN_MS="300")
+    assert EXIT_BESIDE_OPEN not in got[2] and got == want
